@@ -8,15 +8,27 @@ pass of c2d_sat_rect_pairs_verts over the rank's 10^7 pairs.  With N > 1 every
 rank owns its own 10^7 pairs (weak scaling, no data-path collective) and one
 RCCL all-reduce of the colliding-pair count closes the timed region.
 
-The same JSON line also carries
-  roofline     — HBM roofline of the SAT kernel (HIP events on its stream),
+A plain run sets up, warms up, times the K steps and prints the line, which also carries
+the HBM roofline of the SAT kernel from the timed steps' own HIP events.  With --full the
+same line also carries
+  the headline leg's per-step distribution and (N > 1) the closing reduce by itself,
+                 each in a separate untimed pass,
   cpu_baseline — the CPU oracle (OpenMP port of the reference arithmetic) timed on
                  a bounded sample of the same workload on this host, rank 0, N = 1,
   mc           — Monte-Carlo samples/s of BASELINE config 3 (1 scene, 10^8
                  samples per GPU, sample ranges sharded over ranks, one all-reduce
-                 of the hit count), with its VALU-roofline note.
+                 of the hit count), with its VALU-roofline note,
+  and the bit-mask, pose-format, host-resident, polygon Monte-Carlo, config-4 scenes and
+  config-5 polygon legs; a plain run reports those fields as null.
 
-Launch: `python bench.py [--gpus N --steps K --warmup W]`.  With N > 1 and no launcher
+--dump-outputs DIR writes what the timed steps computed (rank 0's shard) as .npy files:
+  collide.npy       float32[n] — the u8 booleans of the last timed step (every stride-th pair
+                    when n would exceed the 64 MiB budget),
+  collide_count.npy float64[1] — colliding pairs of one step, summed over the ranks.
+The inputs are a function of the arguments alone (seeded per rank), so two builds can be
+compared output for output.
+
+Launch: `python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]`.  With N > 1 and no launcher
 environment (RANK / WORLD_SIZE unset) the process starts the N ranks itself — before it
 imports torch or touches a GPU — as children of `python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 ...`, relays rank 0's JSON line and exits with
@@ -29,7 +41,7 @@ RCCL counts another number of ranks than the launcher, every rank exits non-zero
 curve of some other reduce is never reported (`--reduce torch` asks for torch's all_reduce
 explicitly).
 
-Parity in the same run (rank 0, N = 1): ALL booleans of the config-2 and config-5 batches are
+Parity in the same --full run (rank 0, N = 1): ALL booleans of the config-2 and config-5 batches are
 compared with the CPU oracle, and the first scenes of the config-4 shard with the oracle's
 adaptive loop (hits and sample counts); each of those legs carries its own `cpu_baseline`.
 """
@@ -231,6 +243,24 @@ def torch_random_convex_polygons(torch, dev, n, seed, kmin=3, kmax=KMAX, extent=
 class Run:
     """What the legs of one bench run share: setup() puts the rank, the device, the engine, the stream and the reduce on it, every leg reads what it
     needs from it at its top and leaves what later legs and the result line read at its bottom (the data flow between the legs is those lines)."""
+    # what the result line reads from the legs that only a --full run starts
+    cpu_baseline = host_leg = mask_leg = mc = mc_poly = poly_leg = pose_leg = scenes_leg = None
+
+
+DUMP_MAX_BYTES = 64 * 2**20  # --dump-outputs budget, all files together
+
+
+def dump_outputs(out_dir, out, count_per_step) -> None:
+    """--dump-outputs: the booleans of the last timed step as float32 (every stride-th pair beyond the budget) and the
+    colliding-pair count of one step as float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = out.numel()
+    stride = -(-n * 4 // (DUMP_MAX_BYTES - 4096))  # (ceil; 4 KiB left for the headers and the count)
+    collide = out[::stride].cpu().numpy().astype(np.float32)
+    np.save(os.path.join(out_dir, "collide.npy"), collide)
+    np.save(os.path.join(out_dir, "collide_count.npy"), np.array([count_per_step], dtype=np.float64))
+    print(f"[bench] outputs written to {out_dir}: collide.npy ({collide.size} of {n} pairs, stride {stride}), collide_count.npy",
+          file=sys.stderr, flush=True)
 
 
 def setup(args, R) -> None:
@@ -487,10 +517,12 @@ def leg_pairs(R) -> None:
     elapsed = shd.max_over_ranks(t1 - t0, dev)
     kernel_ms = ev0.elapsed_time(ev1) / args.steps  # average launch duration on the kernel's stream
     count_after_timed = int(total_count.item())
-    step_ms = step_distribution(step, min(args.steps, 100))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, count_after_timed // args.steps)
+    step_ms = step_distribution(step, min(args.steps, 100)) if args.full else None
     pairs_total = n * world * args.steps
     value = pairs_total / elapsed
-    reduce_us = R.time_reduce(1, before=step)
+    reduce_us = R.time_reduce(1, before=step) if args.full else None
     collide_rate = count_after_timed / (n * world * args.steps)
 
     achieved_gbs = BYTES_PER_PAIR * n / (kernel_ms * 1e-3) / 1e9
@@ -1274,7 +1306,15 @@ def main() -> None:
     ap.add_argument("--poly-reps", type=int, default=20)
     ap.add_argument("--poly-bin-granularity", type=int, default=1,
                     help="binned polygon leg: polygon sizes rounded up to this many rows per bin (1 = one bin per (ka, kb): the exact bytes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (bit-mask, pose format, host-resident, Monte-Carlo, scenes, polygons), the CPU baselines "
+                         "with the full-size oracle parity, and the headline leg's separate per-step and reduce passes; without it a run "
+                         "measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     launched = "WORLD_SIZE" in os.environ or "RANK" in os.environ
     if args.gpus > 1 and not launched:
@@ -1282,7 +1322,8 @@ def main() -> None:
 
     R = Run()
     setup(args, R)
-    for leg in (leg_pairs, leg_mask_output, leg_pose_format, leg_host_resident, leg_mc, leg_mc_poly, leg_scenes, leg_poly, cpu_baselines_and_parity, emit):
+    legs = (leg_mask_output, leg_pose_format, leg_host_resident, leg_mc, leg_mc_poly, leg_scenes, leg_poly, cpu_baselines_and_parity) if args.full else ()
+    for leg in (leg_pairs,) + legs + (emit,):
         leg(R)
 
 

@@ -8,10 +8,10 @@ R=$PWD
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
-SMALL="--steps 20 --warmup 2 --prewarm-ms 0 --no-cpu-baseline --mc-reps 2 --poly-reps 3 --poly-scenes 0"
+SMALL="--full --steps 20 --warmup 2 --prewarm-ms 0 --no-cpu-baseline --mc-reps 2 --poly-reps 3 --poly-scenes 0"
 cd /tmp
-echo "== un-profiled bench"; timeout -k 10 500 python3 $R/bench.py > $O/bench.json 2> $O/bench.err
-echo "== kernel trace + stats"; timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.err
+echo "== un-profiled bench"; timeout -k 10 500 python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err
+echo "== kernel trace + stats"; timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.err
 echo "== pmc FETCH_SIZE"; timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py $SMALL --no-mc --scenes 0 > /dev/null 2> $O/pmc_fetch.err
 echo "== pmc WRITE_SIZE"; timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python3 $R/bench.py $SMALL --no-mc --scenes 0 > /dev/null 2> $O/pmc_write.err
 echo "== pmc SQ"; timeout -k 10 600 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_sq -- python3 $R/bench.py $SMALL --poly-scenes 200000 > /dev/null 2> $O/pmc_sq.err
@@ -21,7 +21,7 @@ echo "== pmc SQ LDS (polygon kernel)"; timeout -k 10 400 rocprofv3 --pmc SQ_INST
 # probe's prices, then each leg's own mix as a probe stream (generated, compiled here, run)
 TYPES="SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT"
 BUSY="SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_INST_CYCLES_SALU SQ_WAIT_INST_LDS SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_SALU GRBM_GUI_ACTIVE"
-MCLEGS="--steps 20 --warmup 2 --prewarm-ms 0 --no-cpu-baseline --mc-reps 2 --poly-scenes 200000 --no-pose --poly-pairs 0"
+MCLEGS="--full --steps 20 --warmup 2 --prewarm-ms 0 --no-cpu-baseline --mc-reps 2 --poly-scenes 200000 --no-pose --poly-pairs 0"
 PROBE=$R/convex-2d-gpu-collision-detection_amd/csrc/tools/instr_probe
 echo "== pmc VALU types (Monte-Carlo legs)"; timeout -k 10 400 rocprofv3 --pmc $TYPES --output-format csv -d $O/pmc_valu_types -- python3 $R/bench.py $MCLEGS > /dev/null 2> $O/pmc_valu_types.err
 echo "== pmc VALU busy / SALU / LDS wait (Monte-Carlo legs)"; timeout -k 10 400 rocprofv3 --pmc $BUSY --output-format csv -d $O/pmc_valu_busy -- python3 $R/bench.py $MCLEGS > /dev/null 2> $O/pmc_valu_busy.err
@@ -52,7 +52,7 @@ if [ -f convex-2d-gpu-collision-detection_amd/lib/libc2d_mcstats.so ]; then echo
 if [ -f convex-2d-gpu-collision-detection_amd/lib/libc2d_mcclock.so ]; then echo "== held clock"; timeout -k 10 400 python3 tests/tools/mc_clock.py --record $TAG > profiles/${TAG}_mc_clock.txt 2>&1 || echo "clock failed"; fi
 # the bench line quotes measured_counts.json (instruction counts, PMC traffic): run it again now that the file is this tag's own,
 # so that the committed line never carries the previous collection's counts for a kernel that has changed since
-echo "== un-profiled bench again, with this tag's counts"; (cd /tmp && timeout -k 10 500 python3 $R/bench.py > $O/bench.json 2> $O/bench.err)
+echo "== un-profiled bench again, with this tag's counts"; (cd /tmp && timeout -k 10 500 python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err)
 cp $O/bench.json profiles/${TAG}_bench.json
 mkdir -p $R/gpurun_out/${TAG}_profiles && cp profiles/${TAG}_* profiles/measured_counts.json $R/gpurun_out/${TAG}_profiles/   # (only gpurun_out/ travels back from the GPU box)
 # the raw traces are large: keep only what the digests came from, compressed

@@ -10,9 +10,9 @@ O=$R/gpurun_out/r05_rehearsal
 mkdir -p $O
 N=5
 echo "== bench.py --gpus $N, shared device"
-timeout -k 10 900 python3 bench.py --gpus $N --share-device --backend gloo --steps 20 --warmup 5 > $O/bench_n${N}.json 2> $O/bench_n${N}.err; echo "rc=$?"
+timeout -k 10 900 python3 bench.py --full --gpus $N --share-device --backend gloo --steps 20 --warmup 5 > $O/bench_n${N}.json 2> $O/bench_n${N}.err; echo "rc=$?"
 echo "== bench.py, one rank, same flags"
-timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_n1.json 2> $O/bench_n1.err; echo "rc=$?"
+timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_n1.json 2> $O/bench_n1.err; echo "rc=$?"
 export LD_LIBRARY_PATH=$R/convex-2d-gpu-collision-detection_amd/lib-rehearsal:$LD_LIBRARY_PATH
 export C2D_SHARE_DEVICE=1
 N=6

@@ -3,7 +3,7 @@
 # pattern (csrc/tools/load_policy_probe).  build/prio1/libc2d.so: s_setprio 3 while a wave forms its addresses and issues its sixteen
 # loads; build/prio2: s_setprio 3 once a wave's data has arrived (-DC2D_SAT_PRIO=1 / 2 on c2d_sat.hip; see the kernel).
 # bash profiles/r05_sat_prio_ab.sh > profiles/r05_sat_prio_ab.txt     (same box, builds interleaved, twice)
-LEG="--no-mc --scenes 0 --poly-pairs 0 --no-cpu-baseline"
+LEG="--full --no-mc --scenes 0 --poly-pairs 0 --no-cpu-baseline"
 timeout -k 10 200 convex-2d-gpu-collision-detection_amd/csrc/tools/load_policy_probe | grep "product\|again\|^#"
 for round in 1 2; do
   for lib in convex-2d-gpu-collision-detection_amd/lib/libc2d.so build/prio1/libc2d.so build/prio2/libc2d.so; do

@@ -12,7 +12,7 @@ TYPES="SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_F
 BUSY="SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_INST_CYCLES_SALU SQ_WAIT_INST_LDS SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_SALU GRBM_GUI_ACTIVE"
 timeout -k 10 200 rocprofv3 --pmc $TYPES --output-format csv -d $O/probe_types -- $R/$T/instr_probe > $O/probe_types.out 2>&1; echo probe types rc=$?
 timeout -k 10 200 rocprofv3 --pmc $BUSY --output-format csv -d $O/probe_busy -- $R/$T/instr_probe > $O/probe_busy.out 2>&1; echo probe busy rc=$?
-SMALL="--steps 20 --warmup 2 --prewarm-ms 0 --no-cpu-baseline --mc-reps 2 --poly-reps 3 --poly-scenes 200000 --no-pose --poly-pairs 0"
+SMALL="--full --steps 20 --warmup 2 --prewarm-ms 0 --no-cpu-baseline --mc-reps 2 --poly-reps 3 --poly-scenes 200000 --no-pose --poly-pairs 0"
 timeout -k 10 400 rocprofv3 --pmc $TYPES --output-format csv -d $O/mc_types -- python3 $R/bench.py $SMALL > /dev/null 2> $O/mc_types.err; echo mc types rc=$?
 timeout -k 10 400 rocprofv3 --pmc $BUSY --output-format csv -d $O/mc_busy -- python3 $R/bench.py $SMALL > /dev/null 2> $O/mc_busy.err; echo mc busy rc=$?
 cd $R

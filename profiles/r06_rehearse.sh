@@ -9,9 +9,9 @@ O=$R/gpurun_out/r06_rehearsal
 mkdir -p $O
 N=5
 echo "== bench.py --gpus $N, shared device"
-timeout -k 10 900 python3 bench.py --gpus $N --share-device --backend gloo --steps 20 --warmup 5 > $O/bench_n${N}.json 2> $O/bench_n${N}.err; echo "rc=$?"
+timeout -k 10 900 python3 bench.py --full --gpus $N --share-device --backend gloo --steps 20 --warmup 5 > $O/bench_n${N}.json 2> $O/bench_n${N}.err; echo "rc=$?"
 echo "== bench.py, one rank, real RCCL in the reduce (--force-dist)"
-timeout -k 10 600 python3 bench.py --force-dist --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_force_dist.json 2> $O/bench_force_dist.err; echo "rc=$?"
+timeout -k 10 600 python3 bench.py --full --force-dist --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_force_dist.json 2> $O/bench_force_dist.err; echo "rc=$?"
 python3 - <<PY
 import json
 for f in ("bench_n$N", "bench_force_dist"):
