@@ -11,7 +11,7 @@ SRCS := $(CSRC)/c2d_api.hip $(CSRC)/c2d_host.hip $(CSRC)/c2d_sat.hip $(CSRC)/c2d
 OBJS := $(SRCS:.hip=.o)
 HDRS := $(CSRC)/c2d_math.hpp $(CSRC)/c2d_mc_core.hpp $(CSRC)/c2d_count.hpp $(CSRC)/c2d_internal.hpp include/c2d.h include/utils.h
 
-all: lib oracle drivers lib-fmad lib-nopretest lib-rehearsal lib-movecheck
+all: lib oracle drivers lib-fmad lib-nopretest lib-rehearsal lib-movecheck lib-splitcheck
 
 lib: $(LIBDIR)/libc2d.so
 
@@ -38,7 +38,7 @@ clean:
 	rm -f $(OBJS) $(LIBDIR)/libc2d.so $(BINDIR)/generate_dataset $(BINDIR)/compute_collision_probability $(BINDIR)/ztest
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib oracle drivers tools clean lib-fmad lib-nopretest lib-rehearsal lib-mcstats lib-mcclock lib-ab-stamps lib-movecheck
+.PHONY: all lib oracle drivers tools clean lib-fmad lib-nopretest lib-rehearsal lib-mcstats lib-mcclock lib-ab-stamps lib-movecheck lib-splitcheck
 
 # developer tools (not shipped in libc2d.so)
 TOOLS := $(CSRC)/tools/sat_tune $(CSRC)/tools/pose_probe $(CSRC)/tools/clock_probe $(CSRC)/tools/instr_probe $(CSRC)/tools/store_pattern_probe $(CSRC)/tools/stream_lifetime_probe $(CSRC)/tools/load_policy_probe
@@ -82,6 +82,15 @@ $(CSRC)/c2d_poly_binned_movecheck.o: $(CSRC)/c2d_poly_binned.hip $(HDRS)
 $(LIBDIR)/libc2d_movecheck.so: $(OBJS) $(CSRC)/c2d_poly_binned_movecheck.o
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $(filter-out $(CSRC)/c2d_poly_binned.o,$(OBJS)) $(CSRC)/c2d_poly_binned_movecheck.o -ldl
+
+# test build: the index-checked binning pass with a plane limit of 32 KiB instead of 4 GiB (C2D_FROM_PADDED_PLANE_MAX), so that
+# c2d_poly_bins_from_padded splits classes of a few hundred to a few thousand pairs into several bins (tests/test_gpu_poly_binned.py)
+lib-splitcheck: $(LIBDIR)/libc2d_splitcheck.so
+$(CSRC)/c2d_poly_binned_splitcheck.o: $(CSRC)/c2d_poly_binned.hip $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -DC2D_MOVE_CHECK -DC2D_FROM_PADDED_PLANE_MAX=32768 -c $< -o $@
+$(LIBDIR)/libc2d_splitcheck.so: $(OBJS) $(CSRC)/c2d_poly_binned_splitcheck.o
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $(filter-out $(CSRC)/c2d_poly_binned.o,$(OBJS)) $(CSRC)/c2d_poly_binned_splitcheck.o -ldl
 
 # census build (developer tool, not part of `all`): Monte-Carlo kernels that count where their samples go (C2D_MC_STATS in c2d_mc.hip);
 # tests/tools/mc_stats.py reads the counters and records the evaluated-sample fraction the bench quotes

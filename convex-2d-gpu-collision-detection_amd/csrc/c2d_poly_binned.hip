@@ -478,6 +478,8 @@ struct BinMoveArgs {
     uint32_t tiles_per_xcd;        // ceil(n_tiles / 8): block b takes tile (b % 8) * tiles_per_xcd + b / 8
     uint32_t* index;               // [n] out: position of input pair i; 0xffffffff = bad counts
     float* base;                   // the block every plane of every bin lives in: a plane position is an element offset from here
+    const uint8_t* class_lg;       // [256], read by the SPLIT instance only: log2 of the pairs per bin of a class split into several bins
+                                   // (slot s is pair s & (2^lg - 1) of bin class_to_bin[c] + (s >> lg)); 31 = the class is one bin
 #ifdef C2D_MOVE_CHECK  // (developer build: every index of the move kernel is checked against its array; the first offender is recorded and skipped)
     unsigned long long lim_in, lim_k, lim_block, lim_prefix, lim_bins;
     unsigned long long* chk;  // [0] = kind (0 none), [1] = index, [2] = limit, [3] = tile << 32 | thread
@@ -550,7 +552,10 @@ C2D_DEV unsigned long long wave_match_class(uint32_t c, bool ok)
     return peers;
 }
 
-template <typename Off>
+// SPLIT: some class is several bins (c2d_poly_bins_from_padded, kFromPaddedPlaneMax): a consumer takes the plane offsets and the
+// stride of each position from the descriptor of the bin its slot falls into.  Batches without such a class run the instance
+// without it, which never reads A.class_lg.
+template <typename Off, bool SPLIT>
 __global__ __launch_bounds__(kBinBlock, (kMoveTile <= 4096 ? 2 : 1) * kBinWaves / 4) void poly_bin_move_kernel(BinMoveArgs A)
 {
     // two stages, each one vertex row of the tile as (x, y) pairs.  Until the rows start they hold the tables of the slot
@@ -684,6 +689,11 @@ __global__ __launch_bounds__(kBinBlock, (kMoveTile <= 4096 ? 2 : 1) * kBinWaves 
                 const uint32_t c = s_cls[li];
                 d_slot[j] = s_slot[li];
                 d_stride[j] = s_stride[c];
+                if constexpr (SPLIT) {  // the bin of the slot: its own stride, and the slot's position within it
+                    const uint32_t lg = A.class_lg[c];
+                    const uint32_t bin = A.class_to_bin[c] + (d_slot[j] >> lg);
+                    if (C2D_MOVE_OK(12, bin, A.lim_bins)) d_stride[j] = A.table[bin].stride;
+                }
                 d_meta[j] = li | (c << 16) | ((uint32_t)(s_rows[0][c] - 1) << 24) | ((uint32_t)(s_rows[1][c] - 1) << 28);
                 live |= 1u << j;
             }
@@ -695,8 +705,19 @@ __global__ __launch_bounds__(kBinBlock, (kMoveTile <= 4096 ? 2 : 1) * kBinWaves 
 #pragma unroll
             for (int j = 0; j < kMovePos; j++) {
                 const uint32_t c = (d_meta[j] >> 16) & 0xffu;
-                d_x[j] = s_plane[2 * poly][c] + d_slot[j];
-                d_y[j] = s_plane[2 * poly + 1][c] + d_slot[j];
+                if constexpr (SPLIT) {
+                    const uint32_t lg = A.class_lg[c];
+                    const uint32_t bin = A.class_to_bin[c] + (d_slot[j] >> lg), s = d_slot[j] & ((1u << lg) - 1u);
+                    d_x[j] = d_y[j] = 0;
+                    if (((live >> j) & 1u) && C2D_MOVE_OK(12, bin, A.lim_bins)) {
+                        const BinDesc& D = A.table[bin];
+                        d_x[j] = (Off)((poly ? D.bx : D.ax) - A.base) + s;
+                        d_y[j] = (Off)((poly ? D.by : D.ay) - A.base) + s;
+                    }
+                } else {
+                    d_x[j] = s_plane[2 * poly][c] + d_slot[j];
+                    d_y[j] = s_plane[2 * poly + 1][c] + d_slot[j];
+                }
             }
 #pragma nounroll
             for (int r = 0; r < A.rows; r++) {
@@ -794,6 +815,23 @@ __global__ __launch_bounds__(kBinBlock, (kMoveTile <= 4096 ? 2 : 1) * kBinWaves 
     };
     if (here == (uint32_t)kMoveTile) produce(std::true_type{});
     else produce(std::false_type{});
+}
+
+// The largest vertex plane c2d_poly_bins_from_padded gives a bin: the test kernel addresses a plane through a buffer resource of
+// at most 2^32 - 1 bytes (plane_rsrc), so a class whose plane would be larger is split into several bins.  A build may set it
+// lower (make lib-splitcheck) to run the split on small batches; c2d_poly_bins_create keeps the 4 GiB rule whatever it is.
+#ifndef C2D_FROM_PADDED_PLANE_MAX
+#define C2D_FROM_PADDED_PLANE_MAX 0xffffffffull
+#endif
+constexpr uint64_t kFromPaddedPlaneMax = C2D_FROM_PADDED_PLANE_MAX;
+static_assert(kFromPaddedPlaneMax <= 0xffffffffull && kFromPaddedPlaneMax >= 4ull * C2D_POLY_KMAX * 64, "a plane of 64 pairs of C2D_POLY_KMAX rows fits");
+
+// pairs per bin of a split class whose larger polygon has `rows` vertex rows: the largest power of two whose plane fits
+inline uint32_t split_lg(uint32_t rows)
+{
+    uint32_t lg = 6;
+    while ((uint64_t)rows * (2ull << lg) * 4 <= kFromPaddedPlaneMax) lg++;
+    return lg;
 }
 
 __global__ __launch_bounds__(256) void poly_bins_results_kernel(const uint8_t* __restrict__ out_all, const uint32_t* __restrict__ index, size_t n,
@@ -1013,7 +1051,10 @@ int c2d_poly_bins_from_padded(c2d_ctx* ctx, const float* d_vx, const float* d_vy
     // [n_tiles][256] counts -> prefixes | [256] totals + 1 word of bad-count waves | [n_chunks][256] chunk sums | the move kernel's table
     const size_t hist_words = n_tiles * 256 + 257 + n_chunks * 256;
     const size_t off_plain = (hist_words * sizeof(uint32_t) + 255) / 256 * 256;
-    const size_t scratch_need = off_plain + 256 * sizeof(BinDesc);
+    // the move kernel's table has an entry per bin: one per class, and one more per 2^split_lg(rows) pairs of a split class
+    const size_t max_bins = 256 + (n >> split_lg((uint32_t)rows));
+    const size_t off_lg = off_plain + max_bins * sizeof(BinDesc);
+    const size_t scratch_need = off_lg + 256;
     if (int rc = workspace_acquire(ctx, s, true)) return fail(rc);
     if (ctx->scratch_bytes < scratch_need) {
         if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
@@ -1034,46 +1075,72 @@ int c2d_poly_bins_from_padded(c2d_ctx* ctx, const float* d_vx, const float* d_vy
     C2D_BIN_HIP(hipStreamSynchronize(s));
     lap("count + scan + read-back");
     B->had_bad_counts = hist[256] != 0;
-    // ---- 2. layout of the block: per bin ax, ay, bx, by (stride = n rounded up to 64 elements, every plane 256-byte
-    // aligned), counts (only when a bin can hold different sizes); then every bin's results back to back; then the index
+    // ---- 2. layout of the block: per class ax, ay, bx, by (stride = n rounded up to 64 elements, every plane 256-byte
+    // aligned), counts (only when a bin can hold different sizes); then every bin's results back to back; then the index.
+    // A class whose plane would exceed kFromPaddedPlaneMax becomes several bins of 2^lg pairs (the last one: the rest), each
+    // with a plane of its own; the bins' planes of each of ax, ay, bx, by lie back to back, its counts are one array
+    // (the move kernel writes them at the class's slot), and so are its results.
     const int g_ = granularity;
     const bool counted = g_ > 1;
     std::vector<uint16_t> class_to_bin(256, 0xffff);
+    std::vector<uint8_t> class_lg(256, 31);
     std::vector<uint32_t> pair_base;
     size_t bytes = 0, pairs = 0;
+    bool split = false;
     auto align_up = [](size_t v, size_t a) { return (v + a - 1) / a * a; };
     struct Plan { size_t ax, ay, bx, by, ka, kb; uint32_t stride; };
     std::vector<Plan> plan;
     for (int c = 0; c < 256; c++) {
         if (!hist[c]) continue;
-        c2d_poly_bin b{};
-        b.rows_a = (uint32_t)std::min(rows, (c / 16 + 1) * g_);
-        b.rows_b = (uint32_t)std::min(rows, (c % 16 + 1) * g_);
-        b.n = hist[c];
-        const uint32_t stride = (uint32_t)align_up(b.n, 64);
-        Plan p{};
-        p.stride = stride;
-        const size_t plane_a = (size_t)b.rows_a * stride * 4, plane_b = (size_t)b.rows_b * stride * 4;
-        p.ax = bytes; bytes = align_up(bytes + plane_a, 256);
-        p.ay = bytes; bytes = align_up(bytes + plane_a, 256);
-        p.bx = bytes; bytes = align_up(bytes + plane_b, 256);
-        p.by = bytes; bytes = align_up(bytes + plane_b, 256);
-        if (counted) {
-            p.ka = bytes; bytes = align_up(bytes + b.n, 256);
-            p.kb = bytes; bytes = align_up(bytes + b.n, 256);
+        const uint32_t rows_a = (uint32_t)std::min(rows, (c / 16 + 1) * g_), rows_b = (uint32_t)std::min(rows, (c % 16 + 1) * g_);
+        const size_t n_c = hist[c];
+        size_t cap = n_c;  // pairs per bin of the class
+        if ((uint64_t)std::max(rows_a, rows_b) * align_up(n_c, 64) * 4 > kFromPaddedPlaneMax) {
+            class_lg[c] = (uint8_t)split_lg(std::max(rows_a, rows_b));
+            cap = (size_t)1 << class_lg[c];
+            split = true;
         }
+        const size_t n_sub = (n_c + cap - 1) / cap;
+        std::vector<uint32_t> strides(n_sub);
+        size_t elems = 0;  // rows of one polygon's planes over all bins of the class, in elements per row
+        for (size_t j = 0; j < n_sub; j++) {
+            strides[j] = (uint32_t)align_up(std::min(cap, n_c - j * cap), 64);
+            elems += strides[j];
+        }
+        Plan p{};
+        p.ax = bytes; bytes = align_up(bytes + (size_t)rows_a * elems * 4, 256);
+        p.ay = bytes; bytes = align_up(bytes + (size_t)rows_a * elems * 4, 256);
+        p.bx = bytes; bytes = align_up(bytes + (size_t)rows_b * elems * 4, 256);
+        p.by = bytes; bytes = align_up(bytes + (size_t)rows_b * elems * 4, 256);
+        if (counted) {
+            p.ka = bytes; bytes = align_up(bytes + n_c, 256);
+            p.kb = bytes; bytes = align_up(bytes + n_c, 256);
+        }
+        if (B->bins.size() + n_sub > 0xffff) return fail(fail_arg(ctx, "c2d_poly_bins_from_padded: more than 65535 bins"));
         class_to_bin[c] = (uint16_t)B->bins.size();
-        pair_base.push_back((uint32_t)pairs);
-        pairs += b.n;
-        B->bins.push_back(b);
-        B->strides.push_back(stride);
-        plan.push_back(p);
+        for (size_t j = 0; j < n_sub; j++) {
+            c2d_poly_bin b{};
+            b.rows_a = rows_a;
+            b.rows_b = rows_b;
+            b.n = std::min(cap, n_c - j * cap);
+            pair_base.push_back((uint32_t)pairs);
+            pairs += b.n;
+            B->bins.push_back(b);
+            B->strides.push_back(strides[j]);
+            p.stride = strides[j];
+            plan.push_back(p);
+            // the class's next bin: its planes follow this one's, its counts follow this one's
+            p.ax += (size_t)rows_a * strides[j] * 4; p.ay += (size_t)rows_a * strides[j] * 4;
+            p.bx += (size_t)rows_b * strides[j] * 4; p.by += (size_t)rows_b * strides[j] * 4;
+            p.ka += b.n; p.kb += b.n;
+        }
     }
     const size_t off_out = bytes;
     bytes = align_up(bytes + pairs, 256);
     const size_t off_index = bytes;
     bytes += n * sizeof(uint32_t);
     const size_t n_bins = B->bins.size();
+    if (n_bins > max_bins) return fail(fail_arg(ctx, "c2d_poly_bins_from_padded: internal error: more bins than the move table holds"));
     const size_t off_base = align_up(bytes, 256);
     bytes = off_base + (n_bins + 1) * sizeof(uint32_t);
     const size_t off_c2b = align_up(bytes, 256);
@@ -1114,8 +1181,10 @@ int c2d_poly_bins_from_padded(c2d_ctx* ctx, const float* d_vx, const float* d_vy
         t.ax = d.d_ax; t.ay = d.d_ay; t.bx = d.d_bx; t.by = d.d_by; t.ka = d.d_ka; t.kb = d.d_kb; t.out = d.d_out;
         t.n = (uint32_t)d.n; t.stride = (uint32_t)d.stride; t.tile0 = 0; t.rows_a = (uint16_t)d.rows_a; t.rows_b = (uint16_t)d.rows_b;
     }
-    BinDesc* d_plain = reinterpret_cast<BinDesc*>(static_cast<char*>(ctx->d_scratch) + off_plain);  // (at most 256 bins: one per class)
+    BinDesc* d_plain = reinterpret_cast<BinDesc*>(static_cast<char*>(ctx->d_scratch) + off_plain);  // (n_bins <= max_bins: see scratch_need)
     if (n_bins) C2D_BIN_HIP(hipMemcpyAsync(d_plain, plain.data(), n_bins * sizeof(BinDesc), hipMemcpyHostToDevice, s));
+    uint8_t* d_class_lg = static_cast<uint8_t*>(ctx->d_scratch) + off_lg;
+    if (split) C2D_BIN_HIP(hipMemcpyAsync(d_class_lg, class_lg.data(), 256, hipMemcpyHostToDevice, s));
     // ---- 3. move the vertices
     C2D_BIN_HIP(hipMemsetAsync(B->d_out_all, 0, pairs, s));
     if (n_bins) C2D_BIN_HIP(hipMemcpyAsync(base + off_base, pair_base.data(), n_bins * sizeof(uint32_t), hipMemcpyHostToDevice, s));
@@ -1130,6 +1199,7 @@ int c2d_poly_bins_from_padded(c2d_ctx* ctx, const float* d_vx, const float* d_vy
     A.n_tiles = (uint32_t)n_tiles;
     A.tiles_per_xcd = (uint32_t)((n_tiles + 7) / 8);
     A.index = B->d_index;
+    A.class_lg = d_class_lg;
     lap("small copies + memset");
     A.base = reinterpret_cast<float*>(base);
 #ifdef C2D_MOVE_CHECK
@@ -1139,8 +1209,14 @@ int c2d_poly_bins_from_padded(c2d_ctx* ctx, const float* d_vx, const float* d_vy
     C2D_BIN_HIP(hipMemset(d_chk, 0, 32));
     A.chk = d_chk;
 #endif
-    if (bytes < (16ull << 30)) hipLaunchKernelGGL(poly_bin_move_kernel<uint32_t>, dim3(A.tiles_per_xcd * 8u), dim3(kBinBlock), 0, s, A);  // (n < 2^32)
-    else hipLaunchKernelGGL(poly_bin_move_kernel<uint64_t>, dim3(A.tiles_per_xcd * 8u), dim3(kBinBlock), 0, s, A);
+    const dim3 move_grid(A.tiles_per_xcd * 8u);
+    if (bytes < (16ull << 30)) {  // (n < 2^32)
+        if (split) hipLaunchKernelGGL((poly_bin_move_kernel<uint32_t, true>), move_grid, dim3(kBinBlock), 0, s, A);
+        else hipLaunchKernelGGL((poly_bin_move_kernel<uint32_t, false>), move_grid, dim3(kBinBlock), 0, s, A);
+    } else {
+        if (split) hipLaunchKernelGGL((poly_bin_move_kernel<uint64_t, true>), move_grid, dim3(kBinBlock), 0, s, A);
+        else hipLaunchKernelGGL((poly_bin_move_kernel<uint64_t, false>), move_grid, dim3(kBinBlock), 0, s, A);
+    }
     C2D_BIN_HIP(hipStreamSynchronize(s));  // (the host vectors above must outlive their copies)
     workspace_stream_drained(ctx, s);
 #ifdef C2D_MOVE_CHECK

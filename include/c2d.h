@@ -279,6 +279,10 @@ int c2d_sat_poly_pairs_rows(c2d_ctx* ctx, const float* d_vx, const float* d_vy, 
  *                          batch is tested more than once or as a converter for stored datasets;
  *                          a producer that can write bins directly should.  Synchronous; a vertex
  *                          count outside 1..rows is refused (C2D_ERR_INVALID_ARG, no handle).
+ *                          Every n up to 2^32 - 65 is accepted: a size class whose vertex plane would
+ *                          reach 4 GiB becomes several bins of 2^k pairs (the last one the rest), so
+ *                          c2d_poly_bins_size / _get show it as consecutive bins with planes below
+ *                          4 GiB.  (The 4 GiB rule of c2d_poly_bins_create is the caller's.)
  *   c2d_poly_bins_results  for a handle made by c2d_poly_bins_from_padded: the results in the
  *                          ORDER OF THE PADDED INPUT, u8[n] (asynchronous on `stream`);
  *   c2d_poly_bins_get      descriptor i of the handle (device pointers), for inspection: bin i of

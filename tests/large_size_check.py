@@ -4,7 +4,9 @@ build multi-GB device inputs and has to be imported before libc2d.so).
   1. 1.2e9 rectangle pairs: every plane is 4.8 GB, so element offsets pass 2^32 bytes and the
      launch has 4.7e6 blocks.  The input is a 2e6-pair block repeated 600 times; the output must
      be 600 copies of the oracle's booleans for that block and the count 600 x the block's count.
-  2. Monte-Carlo sample indices beyond 2^32: hits over [2^32 - 1e6, 2^32 + 1e6) must equal the
+     The same planes through c2d_sat_rect_pairs_verts_mask: the 150 MB bit mask must be 600 copies of the block's bits.
+  2. c2d_sat_rect_pairs_aos over 1.4e8 + 1 pairs: each f32[n][8] rectangle array is 4.5 GB, so rectangle offsets pass 2^32 bytes.
+  3. Monte-Carlo sample indices beyond 2^32: hits over [2^32 - 1e6, 2^32 + 1e6) must equal the
      oracle's, and a 6e9-sample range must equal the sum of its two halves.
 TEST INFRASTRUCTURE: uses the oracle as the checker."""
 import os
@@ -45,7 +47,41 @@ def main():
     refd = torch.from_numpy(ref).to(dev)
     assert bool((out.view(R, B) == refd[None, :]).all()), "booleans differ somewhere in the 1.2e9-pair batch"
     print(f"large SAT ok: {n} pairs, plane size {4 * n / 1e9:.1f} GB, count {int(cnt.item())}")
-    del planes, out
+    del out
+    words = n // 64
+    assert words * 64 == n and B % 64 == 0
+    mask = torch.full((words + 1,), -1, dtype=torch.int64, device=dev)   # poisoned, one word past the end that must stay so
+    cnt.zero_()
+    eng.sat_rect_pairs_verts_mask([row(planes, k) for k in range(16)], n, mask.data_ptr(), cnt.data_ptr())
+    torch.cuda.synchronize()
+    assert int(cnt.item()) == R * ref_cnt, (int(cnt.item()), R * ref_cnt)
+    ref_bits = torch.from_numpy(np.packbits(ref, bitorder="little")).to(dev)   # (little-endian bits in little-endian words)
+    assert bool((mask[:words].view(torch.uint8).view(R, B // 8) == ref_bits[None, :]).all()), "mask bits differ somewhere in the 1.2e9-pair batch"
+    assert int(mask[words].item()) == -1, "the mask was written past its last word"
+    print(f"large SAT mask ok: {n} pairs, {8 * words / 1e6:.0f} MB of mask")
+    del planes, mask
+    torch.cuda.empty_cache()
+
+    n_aos = 140_000_001
+    R_aos, tail = divmod(n_aos, B)
+    assert 32 * n_aos > 2**32
+    out = torch.full((n_aos,), 7, dtype=torch.uint8, device=dev)
+    rects = []
+    for half in (blk[:8], blk[8:]):   # rectangle i of a side = its 8 vertex coordinates, f32[n][8]
+        aos = torch.empty((n_aos, 8), dtype=torch.float32, device=dev)
+        aos[:R_aos * B].view(R_aos, B, 8).copy_(half.t()[None].expand(R_aos, B, 8))
+        aos[R_aos * B:] = half.t()[:tail]
+        rects.append(aos)
+    cnt.zero_()
+    torch.cuda.synchronize()
+    eng.sat_rect_pairs_aos(rects[0].data_ptr(), rects[1].data_ptr(), n_aos, out.data_ptr(), cnt.data_ptr())
+    torch.cuda.synchronize()
+    assert bool((out[:R_aos * B].view(R_aos, B) == refd[None, :]).all()) and bool((out[R_aos * B:] == refd[:tail]).all()), "AoS booleans differ"
+    want = R_aos * ref_cnt + int(ref[:tail].sum())
+    assert int(cnt.item()) == want, (int(cnt.item()), want)
+    print(f"large AoS ok: {n_aos} pairs, rectangle arrays of {32 * n_aos / 1e9:.1f} GB")
+    del rects, out
+    torch.cuda.empty_cache()
 
     sc = wl.MC_PAIR_SCENE
     args = (sc["robot_w"], sc["robot_h"], sc["pos"], sc["pose"], sc["std_dev"], 99, 7)

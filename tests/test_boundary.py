@@ -141,7 +141,8 @@ def test_no_kernel_selects_on_a_stale_scalar_condition():
     # the same with the reader at the branch's TARGET (the scanner follows the control-flow graph, not the text order)
     across = bad.replace("s_cbranch_vccz .LBB5_289\n; %bb.29:\n", "s_cbranch_vccnz .LBB5_30\n\ts_endpgm\n.LBB5_30:\n")
     assert len(scc.scan_lines(across.splitlines(), "across")) == 1
-    libs = [os.path.join(PKG_DIR, "lib", n) for n in ("libc2d.so", "libc2d_fmad1.so", "libc2d_fmad2.so", "libc2d_nopretest.so", "libc2d_movecheck.so")]
+    libs = [os.path.join(PKG_DIR, "lib", n) for n in ("libc2d.so", "libc2d_fmad1.so", "libc2d_fmad2.so", "libc2d_nopretest.so", "libc2d_movecheck.so",
+                                                 "libc2d_splitcheck.so")]
     libs.append(os.path.join(PKG_DIR, "lib-rehearsal", "libc2d.so"))
     for lib in libs:
         assert scc.scan_library(lib) == [], lib

@@ -270,3 +270,78 @@ def test_move_kernel_stays_inside_its_arrays(pkg, oracle, wl, capfd, n, rows, g,
         e.close()
     assert "[c2d move check]" not in err, err
     assert np.array_equal(out, ref) and cnt == ref_cnt
+
+
+def _bin_layout():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bin_layout", os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "bin_layout.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+# (n, rows, g, kmin, kmax, bins the split build must make or None).  Under the 32 KiB plane limit of make lib-splitcheck a class
+# whose larger polygon has 16 rows holds 512 pairs per bin, 4 rows 2048, 2 rows 4096.
+SPLIT_SHAPES = [
+    (512, 16, 1, 16, 16, 1),            # one class of exactly one bin: the largest plane the limit allows
+    (513, 16, 1, 16, 16, 2),            # one pair more: a second bin of one pair
+    (3 * 512 + 100, 16, 1, 16, 16, 4),  # three whole bins and a partial one
+    (8192 + 512 * 5 + 1, 16, 1, 16, 16, 22),  # bins that straddle the move kernel's 8192-pair tiles
+    (2048, 4, 1, 4, 4, 1),
+    (2049, 4, 1, 4, 4, 2),
+    (3 * 8192 + 5, 2, 2, 1, 2, 7),      # points and segments in one class of two rows: 4096-pair bins, two per move tile
+    (20_000, 16, 16, 3, 16, None),      # one counted class of 16 rows: 40 bins, counts of all sizes
+    (100_003, 16, 1, 3, 16, None),      # 196 classes around the limit: some split, some not
+    (70_001, 12, 3, 2, 12, None),       # 16 counted classes, A and B of different rows
+    (9000, 8, 8, 1, 8, None),           # one counted 8-row class of 1-gons to octagons
+    (50_000, 13, 5, 4, 13, None),       # rows above every class's rounded size: clamped to 13
+]
+
+
+@pytest.mark.parametrize("n,rows,g,kmin,kmax,want_bins", SPLIT_SHAPES)
+def test_from_padded_splits_large_classes(pkg, oracle, wl, capfd, n, rows, g, kmin, kmax, want_bins):
+    """c2d_poly_bins_from_padded splits a class whose vertex plane would exceed the limit of a buffer resource (4 GiB) into
+    several bins.  make lib-splitcheck builds the pass with a limit of 32 KiB and every index of the move kernel checked, so
+    that classes of a few hundred pairs split: the bins must be the ones the layout mirror (tests/tools/bin_layout.py) predicts,
+    no index may leave its array, and the results in input order must be the oracle's."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lib = os.path.join(root, "convex-2d-gpu-collision-detection_amd", "lib", "libc2d_splitcheck.so")
+    if not os.path.exists(lib):
+        import subprocess
+
+        subprocess.run(["make", "-C", root, "lib-splitcheck"], check=True, stdout=subprocess.DEVNULL)
+    layout = _bin_layout()
+    vx, vy, k = wl.random_convex_polygons(n, seed=700_001 + n + rows, kmin=kmin, kmax=kmax, extent=1.5, rows=rows)
+    ref, ref_cnt = oracle.sat_poly_pairs(vx, vy, k)
+    want, _ = layout.from_padded_layout(layout.class_histogram(k, rows, g), n, rows, g, layout.SPLITCHECK_PLANE_MAX)
+    if want_bins is not None:
+        assert len(want) == want_bins
+    else:
+        assert len(want) > len(layout.class_histogram(k, rows, g))  # some class is split
+    e = pkg.Engine(0, lib_path=lib)
+    try:
+        capfd.readouterr()
+        out, cnt, bins = run_from_padded(e, vx, vy, k, rows, g)
+        err = capfd.readouterr().err
+        layout.assert_handle_matches(bins, want)
+        bins.close()
+    finally:
+        e.close()
+    assert "[c2d move check]" not in err, err
+    assert np.array_equal(out, ref) and cnt == ref_cnt
+    assert 0.0 < ref.mean() < 1.0
+
+
+@pytest.mark.parametrize("n,rows,g,kmin", [(100_003, 16, 1, 3), (30_000, 12, 4, 1), (4096, 16, 16, 16)])
+def test_from_padded_layout_mirror(eng, wl, n, rows, g, kmin):
+    """The product build makes one bin per class at these sizes, laid out as the mirror says (the large-size check relies on the
+    mirror to place a batch on either side of 16 GiB)."""
+    layout = _bin_layout()
+    vx, vy, k = wl.random_convex_polygons(n, seed=n + g, kmin=kmin, kmax=rows, rows=rows)
+    hist = layout.class_histogram(k, rows, g)
+    want, _ = layout.from_padded_layout(hist, n, rows, g)
+    assert len(want) == len(hist)
+    out, cnt, bins = run_from_padded(eng, vx, vy, k, rows, g)
+    layout.assert_handle_matches(bins, want)
+    bins.close()
