@@ -16,6 +16,7 @@ from .binding import (  # noqa: F401
     PolyBins,
     DeviceArray,
     KMAX,
+    CROSS_UPPER,
     POSE_DT,
     STD_DT,
     SCENE_DT,

@@ -15,6 +15,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 KMAX = 16
+CROSS_UPPER = 1   # C2D_CROSS_UPPER: N x M calls test only pairs with (col_base + j) > (row_base + i)
 
 POSE_DT = np.dtype([("width", "<f4"), ("height", "<f4"), ("theta", "<f4")])
 STD_DT = np.dtype([("x", "<f4"), ("y", "<f4"), ("theta", "<f4"), ("width", "<f4"), ("height", "<f4")])
@@ -136,6 +137,10 @@ _SIGNATURES = {
     "c2d_sat_rect_pairs_pose": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "c2d_sat_rect_pairs_verts_host": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "c2d_sat_rect_pairs_pose_host": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.POINTER(C.c_ulonglong)]),
+    "c2d_sat_rect_cross_mask": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t, C.c_size_t,
+                                          C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "c2d_sat_rect_cross_pairs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t, C.c_size_t,
+                                           C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_sat_poly_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "c2d_sat_poly_pairs_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "c2d_poly_bins_create": (C.c_int, [C.c_void_p, C.POINTER(_PolyBin), C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -458,6 +463,64 @@ class Engine:
         arr = (C.c_void_p * 16)(*[_ptr_of(p) for p in planes])
         self._check(self.lib.c2d_sat_rect_pairs_verts_mask(self.h, arr, n, _ptr_of(mask), _ptr_of(count), C.c_void_p(stream)),
                     "c2d_sat_rect_pairs_verts_mask")
+
+    # -- all pairs of two rectangle sets (include/c2d.h "all pairs of two rectangle sets") ------------------
+    @staticmethod
+    def _cross_planes(a_planes: Sequence, b_planes: Sequence):
+        if len(a_planes) != 8 or len(b_planes) != 8:
+            raise ValueError("need 8 vertex planes per set")
+        return (C.c_void_p * 8)(*[_ptr_of(p) for p in a_planes]), (C.c_void_p * 8)(*[_ptr_of(p) for p in b_planes])
+
+    def sat_rect_cross_mask(self, a_planes: Sequence, n_a: int, b_planes: Sequence, n_b: int, mask, ld_words: Optional[int] = None,
+                            row_base: int = 0, col_base: int = 0, upper: bool = False, count=None, stream: int = 0):
+        """c2d_sat_rect_cross_mask: bit (j & 63) of mask[i * ld_words + (j >> 6)] = rectangle A_i collides with B_j
+        (ld_words defaults to ceil(n_b / 64))"""
+        a, b = self._cross_planes(a_planes, b_planes)
+        ld = (n_b + 63) // 64 if ld_words is None else ld_words
+        self._check(self.lib.c2d_sat_rect_cross_mask(self.h, a, n_a, b, n_b, row_base, col_base, CROSS_UPPER if upper else 0, _ptr_of(mask), ld,
+                                                     _ptr_of(count), C.c_void_p(stream)), "c2d_sat_rect_cross_mask")
+
+    def sat_rect_cross_pairs(self, a_planes: Sequence, n_a: int, b_planes: Sequence, n_b: int, pairs, capacity: int, count,
+                             row_base: int = 0, col_base: int = 0, upper: bool = False, stream: int = 0):
+        """c2d_sat_rect_cross_pairs: the first `capacity` colliding pairs (row_base + i, col_base + j) in row-major order into
+        pairs = u32[capacity][2]; count (required) is incremented by the total"""
+        a, b = self._cross_planes(a_planes, b_planes)
+        self._check(self.lib.c2d_sat_rect_cross_pairs(self.h, a, n_a, b, n_b, row_base, col_base, CROSS_UPPER if upper else 0, _ptr_of(pairs),
+                                                      capacity, _ptr_of(count), C.c_void_p(stream)), "c2d_sat_rect_cross_pairs")
+
+    def rect_cross_pairs_host(self, a_planes: np.ndarray, b_planes: np.ndarray, upper: bool = False) -> np.ndarray:
+        """Host convenience: a_planes f32[8][n_a], b_planes f32[8][n_b] -> the colliding pairs as an int array [k, 2] in row-major
+        order.  Counts with the mask form first, then sizes the list exactly."""
+        a_planes, b_planes = np.asarray(a_planes, np.float32), np.asarray(b_planes, np.float32)
+        if a_planes.ndim != 2 or b_planes.ndim != 2 or a_planes.shape[0] != 8 or b_planes.shape[0] != 8:
+            raise ValueError("need float32 planes [8][n]")
+        n_a, n_b = a_planes.shape[1], b_planes.shape[1]
+        if n_a == 0 or n_b == 0:
+            return np.zeros((0, 2), np.uint32)
+        d_a, d_b = self.to_device(a_planes), self.to_device(b_planes)
+        arrays = [d_a, d_b]
+        try:
+            pa, pb = [d_a.row(k) for k in range(8)], [d_b.row(k) for k in range(8)]
+            d_cnt = self.zeros(1, np.uint64)
+            arrays.append(d_cnt)
+            d_mask = self.empty((n_a, (n_b + 63) // 64), np.uint64)
+            arrays.append(d_mask)
+            self.sat_rect_cross_mask(pa, n_a, pb, n_b, d_mask, upper=upper, count=d_cnt)
+            total = int(d_cnt.get()[0])
+            d_mask.free()
+            if total == 0:
+                return np.zeros((0, 2), np.uint32)
+            d_pairs = self.empty((total, 2), np.uint32)
+            arrays.append(d_pairs)
+            self.memset(d_cnt, 0, 8)
+            self.sat_rect_cross_pairs(pa, n_a, pb, n_b, d_pairs, total, d_cnt, upper=upper)
+            out = d_pairs.get()
+            if int(d_cnt.get()[0]) != total:
+                raise C2DError(-2, "rect_cross_pairs_host", "the list form counted a different total than the mask form")
+            return out
+        finally:
+            for x in arrays:
+                x.free()
 
     def sat_rect_pairs_pose(self, planes: Sequence, n: int, out, count=None, stream: int = 0):
         if len(planes) != 10:

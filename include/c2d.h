@@ -213,6 +213,53 @@ int c2d_sat_rect_pairs_verts_host(c2d_ctx* ctx, const float* const h_planes[16],
 int c2d_sat_rect_pairs_pose_host(c2d_ctx* ctx, const float* const h_pose_planes[10], size_t n, uint8_t* h_out,
                                  unsigned long long* h_count);
 
+/* ---- all pairs of two rectangle sets (N x M) ---------------------------------
+ * Additions to 0.6 (c2d_version() stays 6): a caller can detect them by symbol lookup (dlsym).
+ *
+ * Which of the n_a rectangles of set A overlap which of the n_b rectangles of set B: result (i, j) is
+ * convex_collide(A_i, B_j) (utils.cu:159-184), exactly the boolean c2d_sat_rect_pairs_verts gives for the pair with
+ * A_i as rectangle 1 and B_j as rectangle 2 — for every input bit pattern, the non-finite rule above included.  The
+ * test is symmetric in its two rectangles (the eight axes are both rectangles' edges, and every comparison is made both
+ * ways), so A and B may be the same planes: with C2D_CROSS_UPPER that is the self-collision test of one set.
+ *   d_a[0..7]  : set A, planes x0,y0,x1,y1,x2,y2,x3,y3, each f32[n_a]   (any alignment)
+ *   d_b[0..7]  : set B, same order, f32[n_b]
+ *   row_base, col_base : global indices of A_0 and B_0.  They change only the C2D_CROSS_UPPER predicate and the indices
+ *                the pair list emits, so that a caller can shard A by rows (one GPU per shard) or tile B by
+ *                columns and still get the right triangle; mask bit positions stay local to the call.
+ *   flags      : 0, or C2D_CROSS_UPPER: only the pairs with (col_base + j) > (row_base + i) are tested; every other
+ *                result is 0 and is not counted.
+ *   d_count    : device uint64 *incremented* (atomically) by the number of colliding tested pairs.
+ *
+ * c2d_sat_rect_cross_mask: bit (j & 63) of d_mask[i * ld_words + (j >> 6)] is result (i, j) (the bit order of
+ * c2d_sat_rect_pairs_verts_mask).  ld_words >= ceil(n_b / 64); d_mask 8-byte aligned.  Every bit of each row's first
+ * ceil(n_b / 64) words is written (bits j >= n_b as 0); words beyond them, up to ld_words, are not touched.  d_count is
+ * optional (may be NULL).  Asynchronous on `stream` and graph-capturable.
+ *
+ * c2d_sat_rect_cross_pairs: the colliding tested pairs as a list, d_pairs = u32[capacity][2] holding
+ * (row_base + i, col_base + j) in row-major order (by i, then by j) — the order of np.argwhere on the mask.  Only the
+ * first `capacity` pairs are written, nothing beyond; d_count is required and receives the TOTAL, those beyond the
+ * capacity included: a caller that finds total > capacity calls again with a larger buffer (d_pairs may be NULL when
+ * capacity is 0: a count-only call).  Global indices are u32: a call with row_base + n_a or col_base + n_b above 2^32 is
+ * refused (C2D_ERR_INVALID_ARG).  Asynchronous on `stream`, with no host synchronisation; the order of the output is
+ * deterministic.  It works through the ctx scratch (mask rows of up to 256 MiB per pass), which it grows on first use
+ * and keeps: that allocation cannot happen while the stream is being captured into a graph, so a capture of this call
+ * is refused (C2D_ERR_INVALID_ARG) unless an earlier call of the same or a larger size already grew the scratch. */
+#define C2D_CROSS_UPPER 1   /* test only pairs with (col_base + j) > (row_base + i) */
+
+int c2d_sat_rect_cross_mask(c2d_ctx* ctx,
+                            const float* const d_a[8], size_t n_a,     /* set A: x0,y0,...,x3,y3 planes, f32[n_a] */
+                            const float* const d_b[8], size_t n_b,     /* set B: same order, f32[n_b] */
+                            size_t row_base, size_t col_base, int flags,
+                            unsigned long long* d_mask, size_t ld_words,
+                            unsigned long long* d_count, c2d_stream stream);
+
+int c2d_sat_rect_cross_pairs(c2d_ctx* ctx,
+                             const float* const d_a[8], size_t n_a,
+                             const float* const d_b[8], size_t n_b,
+                             size_t row_base, size_t col_base, int flags,
+                             uint32_t* d_pairs, size_t capacity,        /* u32[capacity][2] */
+                             unsigned long long* d_count, c2d_stream stream);
+
 /* c2d_sat_poly_pairs: SAT for arbitrary convex polygons with up to
  * C2D_POLY_KMAX vertices.  Same projection / strict-< interval test as
  * utils.cu:172-180, but the axis of edge e is its true normal (-e.y, e.x):
