@@ -141,6 +141,8 @@ _SIGNATURES = {
                                           C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_sat_rect_cross_pairs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t, C.c_size_t,
                                            C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "c2d_sat_rect_broad_pairs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_int,
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_sat_poly_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "c2d_sat_poly_pairs_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "c2d_poly_bins_create": (C.c_int, [C.c_void_p, C.POINTER(_PolyBin), C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -517,6 +519,53 @@ class Engine:
             out = d_pairs.get()
             if int(d_cnt.get()[0]) != total:
                 raise C2DError(-2, "rect_cross_pairs_host", "the list form counted a different total than the mask form")
+            return out
+        finally:
+            for x in arrays:
+                x.free()
+
+    def sat_rect_broad_pairs(self, a_planes: Sequence, n_a: int, b_planes: Sequence, n_b: int, pairs, capacity: int, count,
+                             upper: bool = False, stream: int = 0):
+        """c2d_sat_rect_broad_pairs: the list of sat_rect_cross_pairs (row_base = col_base = 0) through a broad phase: the first
+        `capacity` colliding pairs (i, j) in row-major order into pairs = u32[capacity][2]; count (required) is incremented by
+        the total"""
+        a, b = self._cross_planes(a_planes, b_planes)
+        self._check(self.lib.c2d_sat_rect_broad_pairs(self.h, a, n_a, b, n_b, CROSS_UPPER if upper else 0, _ptr_of(pairs), capacity,
+                                                      _ptr_of(count), C.c_void_p(stream)), "c2d_sat_rect_broad_pairs")
+
+    def rect_broad_pairs_host(self, a_planes: np.ndarray, b_planes: Optional[np.ndarray] = None, upper: bool = False) -> np.ndarray:
+        """Host convenience: a_planes f32[8][n_a], b_planes f32[8][n_b] (None: the same set, uploaded once) -> the colliding pairs
+        as an int array [k, 2] in row-major order.  A count-only call first, then the list sized exactly."""
+        a_planes = np.asarray(a_planes, np.float32)
+        b_planes = None if b_planes is None else np.asarray(b_planes, np.float32)
+        for p in (a_planes, a_planes if b_planes is None else b_planes):
+            if p.ndim != 2 or p.shape[0] != 8:
+                raise ValueError("need float32 planes [8][n]")
+        n_a = a_planes.shape[1]
+        n_b = n_a if b_planes is None else b_planes.shape[1]
+        if n_a == 0 or n_b == 0:
+            return np.zeros((0, 2), np.uint32)
+        d_a = self.to_device(a_planes)
+        arrays = [d_a]
+        try:
+            d_b = d_a
+            if b_planes is not None:
+                d_b = self.to_device(b_planes)
+                arrays.append(d_b)
+            pa, pb = [d_a.row(k) for k in range(8)], [d_b.row(k) for k in range(8)]
+            d_cnt = self.zeros(1, np.uint64)
+            arrays.append(d_cnt)
+            self.sat_rect_broad_pairs(pa, n_a, pb, n_b, None, 0, d_cnt, upper=upper)
+            total = int(d_cnt.get()[0])
+            if total == 0:
+                return np.zeros((0, 2), np.uint32)
+            d_pairs = self.empty((total, 2), np.uint32)
+            arrays.append(d_pairs)
+            self.memset(d_cnt, 0, 8)
+            self.sat_rect_broad_pairs(pa, n_a, pb, n_b, d_pairs, total, d_cnt, upper=upper)
+            out = d_pairs.get()
+            if int(d_cnt.get()[0]) != total:
+                raise C2DError(-2, "rect_broad_pairs_host", "the list call counted a different total than the count-only call")
             return out
         finally:
             for x in arrays:

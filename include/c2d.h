@@ -260,6 +260,34 @@ int c2d_sat_rect_cross_pairs(c2d_ctx* ctx,
                              uint32_t* d_pairs, size_t capacity,        /* u32[capacity][2] */
                              unsigned long long* d_count, c2d_stream stream);
 
+/* ---- broad-phase pair search of two rectangle sets ---------------------------
+ * An addition to 0.6 (c2d_version() stays 6), found by symbol lookup like the two above.
+ *
+ * c2d_sat_rect_broad_pairs: the list of c2d_sat_rect_cross_pairs with row_base = col_base = 0, bit for bit and with the
+ * same count, for every input (non-rectangular quads, degenerate shapes, NaN / inf and huge coordinates included), but
+ * found through a broad phase: each rectangle gets a conservative box, B's boxes are sorted into a uniform grid, and the
+ * exact test (rect_collide, utils.cu:159-184) runs only on the pairs whose boxes overlap.  Objects the box argument does not
+ * cover ("wild": non-finite or |coordinate| >= 2^60, degenerate, or a box far wider than the scene's typical one) are tested
+ * against everything.  DESIGN.md §5.8 proves that no pair is lost.  Use it for sparse scenes: its cost is about
+ * O((n_a + n_b) log n_b + candidates) where the cross form's is n_a x n_b tests; dense scenes, small sets and scenes with
+ * many wild objects are the cross form's.
+ *   d_a, d_b, flags : as c2d_sat_rect_cross_pairs (C2D_CROSS_UPPER: only j > i).  B may be the same planes as A: then the
+ *                boxes are made and sorted once.
+ *   d_pairs, capacity, d_count : as c2d_sat_rect_cross_pairs: (i, j) in row-major order, only the first `capacity` written,
+ *                d_count (required) incremented by the TOTAL; d_pairs may be NULL when capacity is 0 (a count-only call,
+ *                which skips the emit pass).
+ * A call with n_a or n_b above 2^32 is refused (C2D_ERR_INVALID_ARG).  Asynchronous on `stream`, with no host
+ * synchronisation; the output is deterministic.  It works through the ctx scratch, which it grows on first use and keeps:
+ * 36 bytes per object of A plus 48.5 per object of B (68.5 per object when B is A: the boxes are shared) and a 4 KiB header.
+ * Graph capture follows the cross list: a capture is refused (C2D_ERR_INVALID_ARG) unless an earlier call of the same or a
+ * larger size already grew the scratch. */
+int c2d_sat_rect_broad_pairs(c2d_ctx* ctx,
+                             const float* const d_a[8], size_t n_a,     /* set A: x0,y0,...,x3,y3 planes, f32[n_a] */
+                             const float* const d_b[8], size_t n_b,     /* set B: same order; may be the same planes as d_a */
+                             int flags,                                 /* 0 or C2D_CROSS_UPPER (j > i only) */
+                             uint32_t* d_pairs, size_t capacity,        /* u32[capacity][2] */
+                             unsigned long long* d_count, c2d_stream stream);
+
 /* c2d_sat_poly_pairs: SAT for arbitrary convex polygons with up to
  * C2D_POLY_KMAX vertices.  Same projection / strict-< interval test as
  * utils.cu:172-180, but the axis of edge e is its true normal (-e.y, e.x):
