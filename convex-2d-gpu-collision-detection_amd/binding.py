@@ -57,6 +57,11 @@ class _PolyBin(C.Structure):
                 ("d_ka", C.c_void_p), ("d_kb", C.c_void_p), ("d_out", C.c_void_p)]
 
 
+class _PolySet(C.Structure):
+    """c2d_poly_set: one set of convex polygons (one half of the padded pair layout)"""
+    _fields_ = [("rows", C.c_uint32), ("n", C.c_size_t), ("stride", C.c_size_t), ("d_vx", C.c_void_p), ("d_vy", C.c_void_p), ("d_k", C.c_void_p)]
+
+
 class _McScenesArgs(C.Structure):
     _fields_ = [
         ("d_poses", C.c_void_p), ("num_poses", C.c_uint32),
@@ -145,6 +150,10 @@ _SIGNATURES = {
                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_sat_poly_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "c2d_sat_poly_pairs_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "c2d_sat_poly_cross_mask": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_void_p]),
+    "c2d_sat_poly_cross_pairs": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_void_p]),
     "c2d_poly_bins_create": (C.c_int, [C.c_void_p, C.POINTER(_PolyBin), C.c_size_t, C.POINTER(C.c_void_p)]),
     "c2d_poly_bins_from_padded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "c2d_poly_bins_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -616,6 +625,77 @@ class Engine:
     def sat_poly_pairs(self, vx, vy, k, n: int, out, count=None, stream: int = 0):
         self._check(self.lib.c2d_sat_poly_pairs(self.h, _ptr_of(vx), _ptr_of(vy), _ptr_of(k), n, _ptr_of(out), _ptr_of(count),
                                                 C.c_void_p(stream)), "c2d_sat_poly_pairs")
+
+    # -- all pairs of two convex polygon sets (include/c2d.h "all pairs of two convex polygon sets") ----------
+    @staticmethod
+    def poly_set(vx, vy, k, n: int, rows: int = KMAX, stride: int = 0) -> _PolySet:
+        """A c2d_poly_set from device pointers (or DeviceArrays): vx, vy f32[rows][stride], k u8[n] or None (every polygon has
+        `rows` vertices); stride 0 = n"""
+        return _PolySet(rows, n, stride, _ptr_of(vx), _ptr_of(vy), _ptr_of(k))
+
+    def sat_poly_cross_mask(self, a: _PolySet, b: _PolySet, mask, ld_words: Optional[int] = None, row_base: int = 0, col_base: int = 0,
+                            upper: bool = False, count=None, stream: int = 0):
+        """c2d_sat_poly_cross_mask: bit (j & 63) of mask[i * ld_words + (j >> 6)] = polygon A_i collides with B_j
+        (ld_words defaults to ceil(n_b / 64)); a, b from poly_set()"""
+        ld = (b.n + 63) // 64 if ld_words is None else ld_words
+        self._check(self.lib.c2d_sat_poly_cross_mask(self.h, C.byref(a), C.byref(b), row_base, col_base, CROSS_UPPER if upper else 0, _ptr_of(mask), ld,
+                                                     _ptr_of(count), C.c_void_p(stream)), "c2d_sat_poly_cross_mask")
+
+    def sat_poly_cross_pairs(self, a: _PolySet, b: _PolySet, pairs, capacity: int, count, row_base: int = 0, col_base: int = 0,
+                             upper: bool = False, stream: int = 0):
+        """c2d_sat_poly_cross_pairs: the first `capacity` colliding pairs (row_base + i, col_base + j) in row-major order into
+        pairs = u32[capacity][2]; count (required) is incremented by the total"""
+        self._check(self.lib.c2d_sat_poly_cross_pairs(self.h, C.byref(a), C.byref(b), row_base, col_base, CROSS_UPPER if upper else 0, _ptr_of(pairs),
+                                                      capacity, _ptr_of(count), C.c_void_p(stream)), "c2d_sat_poly_cross_pairs")
+
+    @staticmethod
+    def _host_poly_set(vx, vy, k):
+        vx, vy = np.asarray(vx, np.float32), np.asarray(vy, np.float32)
+        if vx.ndim != 2 or vx.shape != vy.shape or not 1 <= vx.shape[0] <= KMAX:
+            raise ValueError("need float32 vertex planes vx, vy [rows][n] of one shape, 1 <= rows <= %d" % KMAX)
+        if k is not None:
+            k = np.asarray(k)
+            if k.shape != (vx.shape[1],):
+                raise ValueError("need vertex counts k [n] for planes [rows][n]")
+            k = k.astype(np.uint8)
+        return vx, vy, k
+
+    def poly_cross_pairs_host(self, vx_a, vy_a, k_a, vx_b, vy_b, k_b, upper: bool = False) -> np.ndarray:
+        """Host convenience: vx, vy f32[rows][n] and k u8[n] (or None) per set -> the colliding pairs as u32 [total][2] in row-major
+        order.  A count-only call first, then the list sized exactly."""
+        vx_a, vy_a, k_a = self._host_poly_set(vx_a, vy_a, k_a)
+        vx_b, vy_b, k_b = self._host_poly_set(vx_b, vy_b, k_b)
+        n_a, n_b = vx_a.shape[1], vx_b.shape[1]
+        if n_a == 0 or n_b == 0:
+            return np.zeros((0, 2), np.uint32)
+        arrays = []
+        try:
+            def up(x):
+                if x is None:
+                    return None
+                arrays.append(self.to_device(x))
+                return arrays[-1]
+
+            a = self.poly_set(up(vx_a), up(vy_a), up(k_a), n_a, vx_a.shape[0])
+            b = self.poly_set(up(vx_b), up(vy_b), up(k_b), n_b, vx_b.shape[0])
+            d_cnt = self.zeros(1, np.uint64)
+            arrays.append(d_cnt)
+            self.sat_poly_cross_pairs(a, b, None, 0, d_cnt, upper=upper)
+            total = int(d_cnt.get()[0])
+            self.check_async()
+            if total == 0:
+                return np.zeros((0, 2), np.uint32)
+            d_pairs = self.empty((total, 2), np.uint32)
+            arrays.append(d_pairs)
+            self.memset(d_cnt, 0, 8)
+            self.sat_poly_cross_pairs(a, b, d_pairs, total, d_cnt, upper=upper)
+            out = d_pairs.get()
+            if int(d_cnt.get()[0]) != total:
+                raise C2DError(-2, "poly_cross_pairs_host", "the list call counted a different total than the count-only call")
+            return out
+        finally:
+            for x in arrays:
+                x.free()
 
     # -- binned polygon batches (include/c2d.h "binned polygon batches") ---------------
     def poly_bins_create(self, bins) -> "PolyBins":

@@ -388,6 +388,64 @@ static int cross_mask_launch(c2d_ctx* ctx, hipStream_t s, const CrossPlanes& A, 
     return C2D_OK;
 }
 
+// The pair list of any N x M mask producer (declared in c2d_internal.hpp; the polygon form, c2d_poly_cross.hip, is the second
+// caller): `pass` queues the counting mask kernel(s) of rows [r0, r0 + rows) of A into `mask` (row stride `words`); the row
+// counts, the chunk scan with the running base on the device and the emit follow each pass.
+int cross_list_run(c2d_ctx* ctx, hipStream_t s, const char* what, size_t n_a, size_t n_b, size_t row_base, size_t col_base, uint32_t* d_pairs,
+                   size_t capacity, unsigned long long* d_count, const CrossMaskPass& pass)
+{
+    char msg[256];
+    auto fail = [&](const char* why) {
+        std::snprintf(msg, sizeof msg, "%s: %s", what, why);
+        return fail_arg(ctx, msg);
+    };
+    if (!d_count) return fail("d_count is required");
+    if (!d_pairs && capacity) return fail("NULL pair buffer");
+    if (row_base + n_a > kIndexLimit || col_base + n_b > kIndexLimit) return fail("global indices must stay below 2^32 (the list is u32)");
+    // scratch: [rows_pass][words] mask | [rows_pass] row offsets | [chunks] chunk sums | running base
+    const size_t words = (n_b + 63) / 64;
+    size_t rows_pass = kPairScratchMaskBytes / (words * 8);
+    rows_pass = rows_pass >= (size_t)kListBlock ? rows_pass / kListBlock * kListBlock : (rows_pass ? rows_pass : 1);
+    if (rows_pass > n_a) rows_pass = n_a;
+    const size_t chunks = (rows_pass + kListBlock - 1) / kListBlock;
+    const size_t off_rows = (rows_pass * words * 8 + 255) / 256 * 256;
+    const size_t off_chunks = off_rows + (rows_pass * 8 + 255) / 256 * 256;
+    const size_t off_base = off_chunks + (chunks * 8 + 255) / 256 * 256;
+    const size_t need = off_base + 256;
+    if (int rc = workspace_acquire(ctx, s, true)) return rc;
+    if (ctx->scratch_bytes < need) {
+        if (stream_is_capturing(s))
+            return fail("the ctx scratch must grow, which cannot happen during graph capture (make the call once outside the capture first)");
+        if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
+        ctx->d_scratch = nullptr;
+        ctx->scratch_bytes = 0;
+        C2D_HIP(ctx, hipMalloc(&ctx->d_scratch, need));
+        ctx->scratch_bytes = need;
+    }
+    char* scratch = static_cast<char*>(ctx->d_scratch);
+    unsigned long long* d_mask = reinterpret_cast<unsigned long long*>(scratch);
+    unsigned long long* d_row_off = reinterpret_cast<unsigned long long*>(scratch + off_rows);
+    unsigned long long* d_chunk = reinterpret_cast<unsigned long long*>(scratch + off_chunks);
+    unsigned long long* d_base = reinterpret_cast<unsigned long long*>(scratch + off_base);
+    WorkspaceUse use(ctx, s);   // the list kernels read the scratch behind the counting mask kernel: stamp behind the last one
+    C2D_HIP(ctx, hipMemsetAsync(d_base, 0, 8, s));
+    use.arm();
+    for (size_t r0 = 0; r0 < n_a; r0 += rows_pass) {
+        const size_t rows = n_a - r0 < rows_pass ? n_a - r0 : rows_pass;
+        const size_t n_chunks = (rows + kListBlock - 1) / kListBlock;
+        if (int rc = pass(r0, rows, d_mask, words)) return rc;
+        hipLaunchKernelGGL(cross_row_counts_kernel, dim3((unsigned)n_chunks), dim3(kListBlock), 0, s, d_mask, rows, words, d_row_off, d_chunk);
+        C2D_LAUNCH_CHECK(ctx);
+        hipLaunchKernelGGL(cross_scan_chunks_kernel, dim3(1), dim3(kListBlock), 0, s, d_chunk, n_chunks, d_base);
+        C2D_LAUNCH_CHECK(ctx);
+        hipLaunchKernelGGL(cross_emit_kernel, dim3((unsigned)n_chunks), dim3(kListBlock), 0, s, d_mask, rows, words, d_row_off, d_chunk,
+                           (uint32_t)(row_base + r0), (uint32_t)col_base, d_pairs, capacity);
+        C2D_LAUNCH_CHECK(ctx);
+    }
+    use.done();
+    return C2D_OK;
+}
+
 }  // namespace c2d
 
 using namespace c2d;
@@ -419,58 +477,15 @@ int c2d_sat_rect_cross_pairs(c2d_ctx* ctx, const float* const d_a[8], size_t n_a
     if (n_a == 0 || n_b == 0) return C2D_OK;
     CrossPlanes A, B;
     if (int rc = cross_check(ctx, "c2d_sat_rect_cross_pairs", d_a, n_a, d_b, n_b, row_base, col_base, flags, A, B)) return rc;
-    if (!d_count) return fail_arg(ctx, "c2d_sat_rect_cross_pairs: d_count is required");
-    if (!d_pairs && capacity) return fail_arg(ctx, "c2d_sat_rect_cross_pairs: NULL pair buffer");
-    if (row_base + n_a > kIndexLimit || col_base + n_b > kIndexLimit)
-        return fail_arg(ctx, "c2d_sat_rect_cross_pairs: global indices must stay below 2^32 (the list is u32)");
     DeviceGuard g(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    // scratch: [rows_pass][words] mask | [rows_pass] row offsets | [chunks] chunk sums | running base
-    const size_t words = (n_b + 63) / 64;
-    size_t rows_pass = kPairScratchMaskBytes / (words * 8);
-    rows_pass = rows_pass >= (size_t)kListBlock ? rows_pass / kListBlock * kListBlock : (rows_pass ? rows_pass : 1);
-    if (rows_pass > n_a) rows_pass = n_a;
-    const size_t chunks = (rows_pass + kListBlock - 1) / kListBlock;
-    const size_t off_rows = (rows_pass * words * 8 + 255) / 256 * 256;
-    const size_t off_chunks = off_rows + (rows_pass * 8 + 255) / 256 * 256;
-    const size_t off_base = off_chunks + (chunks * 8 + 255) / 256 * 256;
-    const size_t need = off_base + 256;
-    if (int rc = workspace_acquire(ctx, s, true)) return rc;
-    if (ctx->scratch_bytes < need) {
-        if (stream_is_capturing(s))
-            return fail_arg(ctx, "c2d_sat_rect_cross_pairs: the ctx scratch must grow, which cannot happen during graph capture "
-                                 "(make the call once outside the capture first)");
-        if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-        ctx->d_scratch = nullptr;
-        ctx->scratch_bytes = 0;
-        C2D_HIP(ctx, hipMalloc(&ctx->d_scratch, need));
-        ctx->scratch_bytes = need;
-    }
-    char* scratch = static_cast<char*>(ctx->d_scratch);
-    unsigned long long* d_mask = reinterpret_cast<unsigned long long*>(scratch);
-    unsigned long long* d_row_off = reinterpret_cast<unsigned long long*>(scratch + off_rows);
-    unsigned long long* d_chunk = reinterpret_cast<unsigned long long*>(scratch + off_chunks);
-    unsigned long long* d_base = reinterpret_cast<unsigned long long*>(scratch + off_base);
-    WorkspaceUse use(ctx, s);   // the list kernels read the scratch behind the counting mask kernel: stamp behind the last one
-    C2D_HIP(ctx, hipMemsetAsync(d_base, 0, 8, s));
-    use.arm();
     const bool upper = (flags & C2D_CROSS_UPPER) != 0;
-    for (size_t r0 = 0; r0 < n_a; r0 += rows_pass) {
-        const size_t rows = n_a - r0 < rows_pass ? n_a - r0 : rows_pass;
-        const size_t n_chunks = (rows + kListBlock - 1) / kListBlock;
-        CrossPlanes Ar;
-        for (int k = 0; k < 8; k++) Ar.p[k] = A.p[k] + r0;
-        if (int rc = cross_mask_launch(ctx, s, Ar, rows, B, n_b, row_base + r0, col_base, upper, d_mask, words, d_count)) return rc;
-        hipLaunchKernelGGL(cross_row_counts_kernel, dim3((unsigned)n_chunks), dim3(kListBlock), 0, s, d_mask, rows, words, d_row_off, d_chunk);
-        C2D_LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL(cross_scan_chunks_kernel, dim3(1), dim3(kListBlock), 0, s, d_chunk, n_chunks, d_base);
-        C2D_LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL(cross_emit_kernel, dim3((unsigned)n_chunks), dim3(kListBlock), 0, s, d_mask, rows, words, d_row_off, d_chunk,
-                           (uint32_t)(row_base + r0), (uint32_t)col_base, d_pairs, capacity);
-        C2D_LAUNCH_CHECK(ctx);
-    }
-    use.done();
-    return C2D_OK;
+    return cross_list_run(ctx, s, "c2d_sat_rect_cross_pairs", n_a, n_b, row_base, col_base, d_pairs, capacity, d_count,
+                          [&](size_t r0, size_t rows, unsigned long long* d_mask, size_t words) {
+                              CrossPlanes Ar;
+                              for (int k = 0; k < 8; k++) Ar.p[k] = A.p[k] + r0;
+                              return cross_mask_launch(ctx, s, Ar, rows, B, n_b, row_base + r0, col_base, upper, d_mask, words, d_count);
+                          });
 }
 
 }  // extern "C"

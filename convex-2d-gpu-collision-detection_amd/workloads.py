@@ -66,6 +66,13 @@ def random_convex_polygons(n: int, seed: int = 0xC0FFEE, kmin: int = 3, kmax: in
     return vx, vy, k
 
 
+def random_convex_polygon_set(n: int, seed: int = 0xC0FFEE, kmin: int = 3, kmax: int = KMAX, extent: float = 8.0, rows: int = KMAX):
+    """One set of convex polygons for the N x M entry points: vx, vy float32 [rows][n], k uint8 [n].  It is polygon 1 of
+    random_convex_polygons with the same arguments (the same floats)."""
+    vx, vy, k = random_convex_polygons(n, seed=seed, kmin=kmin, kmax=kmax, extent=extent, rows=rows)
+    return vx[0], vy[0], k[0]
+
+
 def random_tables(num_poses: int, num_variances: int, seed: int = 7, shape_variance: bool = False):
     """Pose and StdDev tables as generate_dataset builds them (generate_dataset.cu:282-332):
     variances ~ U(0, 0.3) per dimension (width/height forced to 0 unless

@@ -315,6 +315,52 @@ int c2d_sat_poly_pairs_rows(c2d_ctx* ctx, const float* d_vx, const float* d_vy, 
                             size_t n, int rows, uint8_t* d_out, unsigned long long* d_count,
                             c2d_stream stream);
 
+/* ---- all pairs of two convex polygon sets (N x M) ------------------------------
+ * Additions to 0.6 (c2d_version() stays 6): a caller can detect them by symbol lookup (dlsym).
+ *
+ * Which of the n polygons of set A overlap which of those of set B: result (i, j) is exactly the boolean
+ * c2d_sat_poly_pairs_rows gives for the pair with A_i as polygon 1 and B_j as polygon 2 — the projection and strict-<
+ * interval test of utils.cu:172-180 on the true normals (-e.y, e.x) of all ka + kb edges, for every input bit pattern,
+ * the non-finite rule above included; padded vertex slots are never interpreted.  Only a polygon's own edge normals are
+ * axes, so degenerate polygons read as c2d_sat_poly_pairs reads them (two far-apart points "collide": a point's only axis is
+ * the zero vector).  The test is symmetric in its two polygons, so a and b may describe the same memory: with
+ * C2D_CROSS_UPPER that is the self-collision test of one set.  The two sets may have different `rows`.
+ *
+ * c2d_poly_set is one half of the padded pair layout of c2d_sat_poly_pairs_rows.  `stride` lets a caller shard A by rows or
+ * tile B by columns with a pointer offset (d_vx + r0, d_vy + r0, d_k + r0, n = r1 - r0, the same stride), and makes the two
+ * halves of a padded pair batch f32[2][rows][n] two sets without a copy.  A vertex count outside 1..rows gives result 0 for
+ * every pair the polygon is in (those pairs are not counted), and the error is reported by the next
+ * c2d_stream_synchronize / c2d_ctx_check_async, as for c2d_sat_poly_pairs.
+ *
+ * Everything else is c2d_sat_rect_cross_mask / c2d_sat_rect_cross_pairs word for word: row_base / col_base change only the
+ * C2D_CROSS_UPPER predicate ((col_base + j) > (row_base + i)) and the indices the list emits; bit (j & 63) of
+ * d_mask[i * ld_words + (j >> 6)] is result (i, j), ld_words >= ceil(n_b / 64), d_mask 8-byte aligned, every bit of each
+ * row's first ceil(n_b / 64) words written (bits j >= n_b as 0), words beyond untouched; d_count is *incremented*
+ * atomically (optional for the mask, required for the list).  The list is u32[capacity][2] of (row_base + i, col_base + j)
+ * in row-major order (np.argwhere of the mask), only the first `capacity` pairs written, the TOTAL in d_count, d_pairs may
+ * be NULL when capacity is 0; a call with row_base + n_a or col_base + n_b above 2^32 is refused.  n_a == 0 or n_b == 0 is
+ * a no-op.  Both forms are asynchronous on `stream` with no host synchronisation and deterministic.  The mask form is
+ * graph-capturable; the list form works through the ctx scratch like the rectangle list (a capture that would have to grow
+ * the scratch is refused, C2D_ERR_INVALID_ARG). */
+typedef struct c2d_poly_set {
+    uint32_t rows;          /* vertex rows in memory, 1..C2D_POLY_KMAX */
+    size_t n;               /* polygons */
+    size_t stride;          /* elements between consecutive vertex rows, >= n; 0 = n */
+    const float* d_vx;      /* f32[rows][stride], polygon index fastest; any 4-byte alignment */
+    const float* d_vy;
+    const uint8_t* d_k;     /* u8[n] vertex counts 1..rows, or NULL = every polygon has exactly `rows` vertices */
+} c2d_poly_set;             /* a host struct, read before the call returns */
+
+int c2d_sat_poly_cross_mask(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b,
+                            size_t row_base, size_t col_base, int flags,
+                            unsigned long long* d_mask, size_t ld_words,
+                            unsigned long long* d_count, c2d_stream stream);
+
+int c2d_sat_poly_cross_pairs(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b,
+                             size_t row_base, size_t col_base, int flags,
+                             uint32_t* d_pairs, size_t capacity,        /* u32[capacity][2] */
+                             unsigned long long* d_count, c2d_stream stream);
+
 /* ---- binned polygon batches ---------------------------------------------------
  * The padded layout above moves 16 vertex rows per polygon whatever the polygons are: with
  * K ~ U{3..16} that is 259 bytes per pair for 155 bytes of real vertices, and no kernel can
