@@ -154,6 +154,8 @@ _SIGNATURES = {
                                           C.c_void_p, C.c_void_p]),
     "c2d_sat_poly_cross_pairs": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.c_void_p]),
+    "c2d_sat_poly_broad_pairs": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                           C.c_void_p]),
     "c2d_poly_bins_create": (C.c_int, [C.c_void_p, C.POINTER(_PolyBin), C.c_size_t, C.POINTER(C.c_void_p)]),
     "c2d_poly_bins_from_padded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "c2d_poly_bins_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -692,6 +694,60 @@ class Engine:
             out = d_pairs.get()
             if int(d_cnt.get()[0]) != total:
                 raise C2DError(-2, "poly_cross_pairs_host", "the list call counted a different total than the count-only call")
+            return out
+        finally:
+            for x in arrays:
+                x.free()
+
+    def sat_poly_broad_pairs(self, a: _PolySet, b: _PolySet, pairs, capacity: int, count, upper: bool = False, stream: int = 0):
+        """c2d_sat_poly_broad_pairs: the list of sat_poly_cross_pairs (row_base = col_base = 0) through a broad phase: the first
+        `capacity` colliding pairs (i, j) in row-major order into pairs = u32[capacity][2]; count (required) is incremented by
+        the total; a, b from poly_set() (the same set twice: boxes and sort are made once)"""
+        if not isinstance(a, _PolySet) or not isinstance(b, _PolySet):
+            raise ValueError("need two poly_set() descriptions")
+        self._check(self.lib.c2d_sat_poly_broad_pairs(self.h, C.byref(a), C.byref(b), CROSS_UPPER if upper else 0, _ptr_of(pairs), capacity,
+                                                      _ptr_of(count), C.c_void_p(stream)), "c2d_sat_poly_broad_pairs")
+
+    def poly_broad_pairs_host(self, vx_a, vy_a, k_a, vx_b=None, vy_b=None, k_b=None, upper: bool = False) -> np.ndarray:
+        """Host convenience: vx, vy f32[rows][n] and k u8[n] (or None) per set (vx_b None: the same set, uploaded once) -> the
+        colliding pairs as u32 [total][2] in row-major order.  A count-only call first, then the list sized exactly."""
+        vx_a, vy_a, k_a = self._host_poly_set(vx_a, vy_a, k_a)
+        same = vx_b is None
+        if same:
+            if vy_b is not None or k_b is not None:
+                raise ValueError("set B needs vx_b and vy_b (or none of vx_b, vy_b, k_b: the same set)")
+        else:
+            if vy_b is None:
+                raise ValueError("set B needs vx_b and vy_b")
+            vx_b, vy_b, k_b = self._host_poly_set(vx_b, vy_b, k_b)
+        n_a = vx_a.shape[1]
+        n_b = n_a if same else vx_b.shape[1]
+        if n_a == 0 or n_b == 0:
+            return np.zeros((0, 2), np.uint32)
+        arrays = []
+        try:
+            def up(x):
+                if x is None:
+                    return None
+                arrays.append(self.to_device(x))
+                return arrays[-1]
+
+            a = self.poly_set(up(vx_a), up(vy_a), up(k_a), n_a, vx_a.shape[0])
+            b = a if same else self.poly_set(up(vx_b), up(vy_b), up(k_b), n_b, vx_b.shape[0])
+            d_cnt = self.zeros(1, np.uint64)
+            arrays.append(d_cnt)
+            self.sat_poly_broad_pairs(a, b, None, 0, d_cnt, upper=upper)
+            total = int(d_cnt.get()[0])
+            self.check_async()
+            if total == 0:
+                return np.zeros((0, 2), np.uint32)
+            d_pairs = self.empty((total, 2), np.uint32)
+            arrays.append(d_pairs)
+            self.memset(d_cnt, 0, 8)
+            self.sat_poly_broad_pairs(a, b, d_pairs, total, d_cnt, upper=upper)
+            out = d_pairs.get()
+            if int(d_cnt.get()[0]) != total:
+                raise C2DError(-2, "poly_broad_pairs_host", "the list call counted a different total than the count-only call")
             return out
         finally:
             for x in arrays:

@@ -33,6 +33,7 @@
 #include "c2d_internal.hpp"
 #include "c2d_math.hpp"
 #include "c2d_count.hpp"
+#include "c2d_poly_pair.hpp"   // PolySetDev, poly_set_check
 
 namespace c2d {
 
@@ -53,14 +54,6 @@ constexpr int kParkLo = 32, kParkHi = 48, kParkFloats = 64;
 constexpr int kPcSerialMin = 16;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct PolySetDev {
-    const float* vx;
-    const float* vy;
-    const uint8_t* k;   // nullptr: every polygon has `rows` vertices
-    size_t n, stride;
-    int rows;
-};
 
 C2D_DEV void pc_minmax(float nx, float ny, float x, float y, float& mn, float& mx)
 {
@@ -382,22 +375,6 @@ __global__ __launch_bounds__(kPcBlock) void poly_cross_mask_kernel(PolySetDev A,
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
 constexpr size_t kPcBaseLimit = (size_t)1 << 62;   // row_base + n_a, col_base + n_b stay far from signed overflow
-
-static int poly_set_check(c2d_ctx* ctx, const char* what, const char* which, const c2d_poly_set* set, PolySetDev& out)
-{
-    char msg[192];
-    auto fail = [&](const char* why) {
-        std::snprintf(msg, sizeof msg, "%s: set %s: %s", what, which, why);
-        return fail_arg(ctx, msg);
-    };
-    if (set->rows < 1 || set->rows > (uint32_t)C2D_POLY_KMAX) return fail("rows must be 1..C2D_POLY_KMAX");
-    if (!set->d_vx || !set->d_vy) return fail("NULL plane");
-    if ((reinterpret_cast<uintptr_t>(set->d_vx) | reinterpret_cast<uintptr_t>(set->d_vy)) & 3u) return fail("planes must be 4-byte aligned");
-    const size_t stride = set->stride ? set->stride : set->n;
-    if (stride < set->n) return fail("stride < n");
-    out = PolySetDev{set->d_vx, set->d_vy, set->d_k, set->n, stride, (int)set->rows};
-    return C2D_OK;
-}
 
 // Shared argument checks of both forms; C2D_OK or the status to return.
 static int poly_cross_check(c2d_ctx* ctx, const char* what, const c2d_poly_set* a, const c2d_poly_set* b, size_t row_base, size_t col_base, int flags,

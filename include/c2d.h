@@ -361,6 +361,40 @@ int c2d_sat_poly_cross_pairs(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly
                              uint32_t* d_pairs, size_t capacity,        /* u32[capacity][2] */
                              unsigned long long* d_count, c2d_stream stream);
 
+/* ---- broad-phase pair search of two convex polygon sets -------------------------
+ * An addition to 0.6 (c2d_version() stays 6), found by symbol lookup like the ones above.
+ *
+ * c2d_sat_poly_broad_pairs: the list and the total of c2d_sat_poly_cross_pairs(a, b, 0, 0, flags, ...) — the same pairs in the
+ * same row-major order with the same count, for every input bit pattern: degenerate polygons (points and far-apart collinear
+ * segments "collide", as above), NaN / inf and huge or subnormal coordinates, clockwise polygons and repeated vertices, sets
+ * with different `rows`, any `stride`, d_k == NULL — but found through the broad phase of c2d_sat_rect_broad_pairs (the same
+ * grid, sort, scan, count and emit pipeline).  A polygon's conservative box is the box of a parallelogram whose edge normals
+ * are two of the polygon's own test axes, each interval widened by the test's rounding bound; polygons the argument does not
+ * cover ("wild": a non-finite real vertex or a |coordinate| >= 2^60, fewer than three vertices, no two usable non-parallel
+ * edges, or a box far wider than the scene's typical one) are tested against everything.  DESIGN.md §5.10 proves that no pair
+ * is lost.  Use it for sparse scenes of many polygons; dense scenes, small sets and scenes with many wild polygons are the
+ * cross form's.
+ *   a, b       : as c2d_sat_poly_cross_pairs.  Padded vertex slots (index >= the polygon's count) are never interpreted.  A
+ *                polygon with a vertex count outside 1..rows is in no pair and is not counted; the error is reported by the
+ *                next c2d_stream_synchronize / c2d_ctx_check_async, exactly as for the cross form.  a and b may describe the
+ *                same memory (same pointers, n, stride, rows, d_k): the boxes and the sort are then made once, and with
+ *                C2D_CROSS_UPPER that is the self-collision test of one set.
+ *   flags      : 0, or C2D_CROSS_UPPER: only the pairs with j > i.
+ *   d_pairs, capacity, d_count : u32[capacity][2] of (i, j) in row-major order, only the first `capacity` pairs written;
+ *                d_count (required) is incremented by the TOTAL; d_pairs may be NULL when capacity is 0 (a count-only call,
+ *                which skips the emit pass).
+ * n_a == 0 or n_b == 0 is a no-op.  A call with n_a or n_b above 2^32 is refused; an unknown flag, a NULL argument or `rows`
+ * outside 1..C2D_POLY_KMAX is refused (C2D_ERR_INVALID_ARG) before a device is touched.  Asynchronous on `stream`, with no host
+ * synchronisation; the output is deterministic.  It works through the ctx scratch under the workspace guard, which it grows
+ * on first use and keeps; the size depends only on (n_a, n_b, same memory): 36 bytes per polygon of A plus 48.5 per polygon
+ * of B (68.5 per polygon when B is A: the boxes are shared) and a 4 KiB header.  Graph capture follows the rectangle broad
+ * phase: allowed after an eager call of the same or a larger size, refused (C2D_ERR_INVALID_ARG) before anything is enqueued
+ * if the scratch would have to grow. */
+int c2d_sat_poly_broad_pairs(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b,
+                             int flags,                                 /* 0 or C2D_CROSS_UPPER (j > i only) */
+                             uint32_t* d_pairs, size_t capacity,        /* u32[capacity][2] */
+                             unsigned long long* d_count, c2d_stream stream);
+
 /* ---- binned polygon batches ---------------------------------------------------
  * The padded layout above moves 16 vertex rows per polygon whatever the polygons are: with
  * K ~ U{3..16} that is 259 bytes per pair for 155 bytes of real vertices, and no kernel can

@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""Differential fuzz of c2d_sat_poly_broad_pairs against c2d_sat_poly_cross_pairs (itself pinned to the oracle by
+tests/test_gpu_sat_poly_cross.py): random set sizes, row layouts, vertex-count ranges, densities, strides and pointer offsets, self
+and two-set mode, clockwise polygons, points and segments, outliers, NaN / inf in real slots, junk in the padded slots.  Prints its
+seed; a mismatch names its configuration.
+usage: poly_broad_fuzz.py [configs] [seed]"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+from __graft_entry__ import load_package  # noqa: E402
+import importlib  # noqa: E402
+
+pkg = load_package()
+wl = importlib.import_module("c2d_amd.workloads")
+
+
+def random_set(rng, n, rows):
+    kmax = int(rng.integers(1, rows + 1))
+    kmin = int(rng.integers(1, kmax + 1))
+    density = float(rng.choice([0.5, 1.0, 2.0, 4.0, 16.0]))
+    if n > 3000:
+        density = min(density, 4.0)   # (large and dense at once is the cross form's scene: millions of pairs per configuration)
+    extent = 200.0 * np.sqrt(max(n, 16) / 32768) / density
+    vx, vy, k = wl.random_convex_polygon_set(n, seed=int(rng.integers(1 << 30)), kmin=kmin, kmax=kmax, extent=extent, rows=rows)
+    vx, vy = vx.copy(), vy.copy()
+    for q in np.flatnonzero(rng.random(n) < 0.2):          # clockwise
+        kk = int(k[q])
+        vx[:kk, q], vy[:kk, q] = vx[:kk, q][::-1].copy(), vy[:kk, q][::-1].copy()
+    odd = np.flatnonzero(rng.random(n) < 0.02)             # outliers, huge coordinates, non-finite real vertices
+    for q in odd:
+        what = int(rng.integers(0, 4))
+        r = int(rng.integers(0, k[q]))
+        if what == 0:
+            vx[:, q] *= np.float32(10.0 ** rng.integers(2, 7))
+        elif what == 1:
+            vy[:, q] += np.float32(rng.choice([1e30, 2.0 ** 60, -2.0 ** 61, 1e-30]))
+        else:
+            (vx if what == 2 else vy)[r, q] = rng.choice(np.array([np.nan, np.inf, -np.inf, 3e38], np.float32))
+    junk = np.array([np.nan, np.inf, -np.inf, 3e38, -1e-40, 0.0], np.float32)
+    pad = np.arange(rows)[:, None] >= k[None, :]
+    vx[pad], vy[pad] = rng.choice(junk, int(pad.sum())), rng.choice(junk, int(pad.sum()))
+    return (vx, vy, k), f"rows {rows} k {kmin}..{kmax} density {density}"
+
+
+def upload(eng, s, offset, stride):
+    vx, vy, k = s
+    rows, n = vx.shape
+    host = np.full((2, rows * stride + 4), np.nan, np.float32)
+    for p, v in enumerate((vx, vy)):
+        for r in range(rows):
+            host[p, offset + r * stride: offset + r * stride + n] = v[r]
+    d, dk = eng.to_device(host), eng.to_device(k)
+    return eng.poly_set(d.row(0) + 4 * offset, d.row(1) + 4 * offset, dk, n, rows, stride), (d, dk)
+
+
+def one(eng, rng, idx, announce=None):
+    """One configuration; `announce(text)` is called with its description BEFORE any GPU work, so that a fault names its input.
+    Returns (ok, (description, hits))."""
+    sizes = [1, 2, 63, 64, 65, 257, 2049, int(rng.integers(1, 3000)), int(rng.integers(3000, 12_000))]
+    n_a, n_b = int(rng.choice(sizes)), int(rng.choice(sizes))
+    self_mode, upper = bool(rng.random() < 0.4), bool(rng.random() < 0.5)
+    a, da = random_set(rng, n_a, int(rng.integers(1, 17)))
+    sa, keep = upload(eng, a, int(rng.integers(0, 4)), n_a + int(rng.integers(0, 9)))
+    if self_mode:
+        sb, desc = sa, f"config {idx}: self n {n_a} {da} upper {upper}"
+    else:
+        b, db = random_set(rng, n_b, int(rng.integers(1, 17)))
+        sb, keep_b = upload(eng, b, int(rng.integers(0, 4)), n_b + int(rng.integers(0, 9)))
+        keep += keep_b
+        desc = f"config {idx}: {n_a} x {n_b}, A {da}, B {db}, upper {upper}"
+    if announce is not None:
+        announce(desc)
+    d_cnt = eng.zeros(2, np.uint64)
+    eng.sat_poly_cross_pairs(sa, sb, None, 0, d_cnt.ptr, upper=upper)
+    eng.sat_poly_broad_pairs(sa, sb, None, 0, d_cnt.ptr + 8, upper=upper)
+    want_n, got_n = (int(x) for x in d_cnt.get())
+    d_want, d_got = eng.zeros((want_n + 1, 2), np.uint32), eng.zeros((want_n + 1, 2), np.uint32)
+    eng.sat_poly_cross_pairs(sa, sb, d_want, want_n, d_cnt.ptr, upper=upper)
+    eng.sat_poly_broad_pairs(sa, sb, d_got, want_n, d_cnt.ptr + 8, upper=upper)
+    want, got = d_want.get(), d_got.get()
+    for x in list(keep) + [d_cnt, d_want, d_got]:
+        x.free()
+    ok = want_n == got_n and np.array_equal(want, got)
+    if not ok:
+        print(f"MISMATCH {desc}: cross counts {want_n}, broad {got_n}; {int((want != got).any(1).sum())} list entries differ")
+    return ok, (desc, want_n)
+
+
+def main():
+    configs = int(sys.argv[1]) if len(sys.argv) > 1 else 200
+    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 2026
+    print(f"poly_broad_fuzz: {configs} configurations, seed {seed}", flush=True)
+    rng = np.random.default_rng(seed)
+    eng = pkg.Engine(0)
+    fails = hits = 0
+    for i in range(configs):
+        ok, info = one(eng, rng, i)
+        fails += not ok
+        hits += info[-1]
+        if (i + 1) % 50 == 0:  # a sign of life for long runs
+            print(f"  {i + 1} / {configs} configurations, {fails} failures so far", flush=True)
+    print(f"{configs} configurations, {fails} failures; {hits} colliding pairs compared")
+    eng.check_async()
+    eng.close()
+    sys.exit(1 if fails else 0)
+
+
+if __name__ == "__main__":
+    main()
