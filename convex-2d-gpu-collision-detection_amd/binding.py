@@ -477,6 +477,50 @@ class Engine:
         self._check(self.lib.c2d_sat_rect_pairs_verts_mask(self.h, arr, n, _ptr_of(mask), _ptr_of(count), C.c_void_p(stream)),
                     "c2d_sat_rect_pairs_verts_mask")
 
+    # -- the host conveniences of the N x M pair lists ------------------------------------------------------
+    def _to_device_all(self, hosts: Sequence) -> list:
+        """to_device of every array (None stays None); what was uploaded is freed again if a later upload fails"""
+        out = []
+        try:
+            for x in hosts:
+                out.append(None if x is None else self.to_device(x))
+        except BaseException:
+            for d in out:
+                if d is not None:
+                    d.free()
+            raise
+        return out
+
+    def _pairs_sized_exactly(self, name: str, arrays: Sequence, list_call, count_call=None, check_async: bool = False) -> np.ndarray:
+        """The one shape of the *_pairs_host functions: count, size the list exactly, list, compare the two totals.
+        list_call(pairs, capacity, count) makes the list call; count_call(count) counts another way (default: the list call
+        without a buffer).  Frees `arrays` (the caller's uploads; None entries are skipped) and its own on every way out."""
+        arrays = [x for x in arrays if x is not None]
+        try:
+            d_cnt = self.zeros(1, np.uint64)
+            arrays.append(d_cnt)
+            if count_call is None:
+                list_call(None, 0, d_cnt)
+            else:
+                count_call(d_cnt)
+            total = int(d_cnt.get()[0])
+            if check_async:
+                self.check_async()
+            if total == 0:
+                return np.zeros((0, 2), np.uint32)
+            d_pairs = self.empty((total, 2), np.uint32)
+            arrays.append(d_pairs)
+            self.memset(d_cnt, 0, 8)
+            list_call(d_pairs, total, d_cnt)
+            out = d_pairs.get()
+            if int(d_cnt.get()[0]) != total:
+                raise C2DError(-2, name, "the list call counted a different total than the count-only call" if count_call is None
+                               else "the list form counted a different total than the mask form")
+            return out
+        finally:
+            for x in arrays:
+                x.free()
+
     # -- all pairs of two rectangle sets (include/c2d.h "all pairs of two rectangle sets") ------------------
     @staticmethod
     def _cross_planes(a_planes: Sequence, b_planes: Sequence):
@@ -510,30 +554,19 @@ class Engine:
         n_a, n_b = a_planes.shape[1], b_planes.shape[1]
         if n_a == 0 or n_b == 0:
             return np.zeros((0, 2), np.uint32)
-        d_a, d_b = self.to_device(a_planes), self.to_device(b_planes)
-        arrays = [d_a, d_b]
-        try:
-            pa, pb = [d_a.row(k) for k in range(8)], [d_b.row(k) for k in range(8)]
-            d_cnt = self.zeros(1, np.uint64)
-            arrays.append(d_cnt)
+        d_a, d_b = self._to_device_all([a_planes, b_planes])
+        pa, pb = [d_a.row(k) for k in range(8)], [d_b.row(k) for k in range(8)]
+
+        def count_with_mask(d_cnt):
             d_mask = self.empty((n_a, (n_b + 63) // 64), np.uint64)
-            arrays.append(d_mask)
-            self.sat_rect_cross_mask(pa, n_a, pb, n_b, d_mask, upper=upper, count=d_cnt)
-            total = int(d_cnt.get()[0])
-            d_mask.free()
-            if total == 0:
-                return np.zeros((0, 2), np.uint32)
-            d_pairs = self.empty((total, 2), np.uint32)
-            arrays.append(d_pairs)
-            self.memset(d_cnt, 0, 8)
-            self.sat_rect_cross_pairs(pa, n_a, pb, n_b, d_pairs, total, d_cnt, upper=upper)
-            out = d_pairs.get()
-            if int(d_cnt.get()[0]) != total:
-                raise C2DError(-2, "rect_cross_pairs_host", "the list form counted a different total than the mask form")
-            return out
-        finally:
-            for x in arrays:
-                x.free()
+            try:
+                self.sat_rect_cross_mask(pa, n_a, pb, n_b, d_mask, upper=upper, count=d_cnt)
+            finally:
+                d_mask.free()
+
+        return self._pairs_sized_exactly("rect_cross_pairs_host", [d_a, d_b],
+                                         lambda pairs, cap, cnt: self.sat_rect_cross_pairs(pa, n_a, pb, n_b, pairs, cap, cnt, upper=upper),
+                                         count_call=count_with_mask)
 
     def sat_rect_broad_pairs(self, a_planes: Sequence, n_a: int, b_planes: Sequence, n_b: int, pairs, capacity: int, count,
                              upper: bool = False, stream: int = 0):
@@ -556,31 +589,11 @@ class Engine:
         n_b = n_a if b_planes is None else b_planes.shape[1]
         if n_a == 0 or n_b == 0:
             return np.zeros((0, 2), np.uint32)
-        d_a = self.to_device(a_planes)
-        arrays = [d_a]
-        try:
-            d_b = d_a
-            if b_planes is not None:
-                d_b = self.to_device(b_planes)
-                arrays.append(d_b)
-            pa, pb = [d_a.row(k) for k in range(8)], [d_b.row(k) for k in range(8)]
-            d_cnt = self.zeros(1, np.uint64)
-            arrays.append(d_cnt)
-            self.sat_rect_broad_pairs(pa, n_a, pb, n_b, None, 0, d_cnt, upper=upper)
-            total = int(d_cnt.get()[0])
-            if total == 0:
-                return np.zeros((0, 2), np.uint32)
-            d_pairs = self.empty((total, 2), np.uint32)
-            arrays.append(d_pairs)
-            self.memset(d_cnt, 0, 8)
-            self.sat_rect_broad_pairs(pa, n_a, pb, n_b, d_pairs, total, d_cnt, upper=upper)
-            out = d_pairs.get()
-            if int(d_cnt.get()[0]) != total:
-                raise C2DError(-2, "rect_broad_pairs_host", "the list call counted a different total than the count-only call")
-            return out
-        finally:
-            for x in arrays:
-                x.free()
+        d_a, d_b = self._to_device_all([a_planes, b_planes])
+        pa = [d_a.row(k) for k in range(8)]
+        pb = pa if d_b is None else [d_b.row(k) for k in range(8)]
+        return self._pairs_sized_exactly("rect_broad_pairs_host", [d_a, d_b],
+                                         lambda pairs, cap, cnt: self.sat_rect_broad_pairs(pa, n_a, pb, n_b, pairs, cap, cnt, upper=upper))
 
     def sat_rect_pairs_pose(self, planes: Sequence, n: int, out, count=None, stream: int = 0):
         if len(planes) != 10:
@@ -670,34 +683,11 @@ class Engine:
         n_a, n_b = vx_a.shape[1], vx_b.shape[1]
         if n_a == 0 or n_b == 0:
             return np.zeros((0, 2), np.uint32)
-        arrays = []
-        try:
-            def up(x):
-                if x is None:
-                    return None
-                arrays.append(self.to_device(x))
-                return arrays[-1]
-
-            a = self.poly_set(up(vx_a), up(vy_a), up(k_a), n_a, vx_a.shape[0])
-            b = self.poly_set(up(vx_b), up(vy_b), up(k_b), n_b, vx_b.shape[0])
-            d_cnt = self.zeros(1, np.uint64)
-            arrays.append(d_cnt)
-            self.sat_poly_cross_pairs(a, b, None, 0, d_cnt, upper=upper)
-            total = int(d_cnt.get()[0])
-            self.check_async()
-            if total == 0:
-                return np.zeros((0, 2), np.uint32)
-            d_pairs = self.empty((total, 2), np.uint32)
-            arrays.append(d_pairs)
-            self.memset(d_cnt, 0, 8)
-            self.sat_poly_cross_pairs(a, b, d_pairs, total, d_cnt, upper=upper)
-            out = d_pairs.get()
-            if int(d_cnt.get()[0]) != total:
-                raise C2DError(-2, "poly_cross_pairs_host", "the list call counted a different total than the count-only call")
-            return out
-        finally:
-            for x in arrays:
-                x.free()
+        arrays = self._to_device_all([vx_a, vy_a, k_a, vx_b, vy_b, k_b])
+        a = self.poly_set(*arrays[:3], n_a, vx_a.shape[0])
+        b = self.poly_set(*arrays[3:], n_b, vx_b.shape[0])
+        return self._pairs_sized_exactly("poly_cross_pairs_host", arrays,
+                                         lambda pairs, cap, cnt: self.sat_poly_cross_pairs(a, b, pairs, cap, cnt, upper=upper), check_async=True)
 
     def sat_poly_broad_pairs(self, a: _PolySet, b: _PolySet, pairs, capacity: int, count, upper: bool = False, stream: int = 0):
         """c2d_sat_poly_broad_pairs: the list of sat_poly_cross_pairs (row_base = col_base = 0) through a broad phase: the first
@@ -724,34 +714,11 @@ class Engine:
         n_b = n_a if same else vx_b.shape[1]
         if n_a == 0 or n_b == 0:
             return np.zeros((0, 2), np.uint32)
-        arrays = []
-        try:
-            def up(x):
-                if x is None:
-                    return None
-                arrays.append(self.to_device(x))
-                return arrays[-1]
-
-            a = self.poly_set(up(vx_a), up(vy_a), up(k_a), n_a, vx_a.shape[0])
-            b = a if same else self.poly_set(up(vx_b), up(vy_b), up(k_b), n_b, vx_b.shape[0])
-            d_cnt = self.zeros(1, np.uint64)
-            arrays.append(d_cnt)
-            self.sat_poly_broad_pairs(a, b, None, 0, d_cnt, upper=upper)
-            total = int(d_cnt.get()[0])
-            self.check_async()
-            if total == 0:
-                return np.zeros((0, 2), np.uint32)
-            d_pairs = self.empty((total, 2), np.uint32)
-            arrays.append(d_pairs)
-            self.memset(d_cnt, 0, 8)
-            self.sat_poly_broad_pairs(a, b, d_pairs, total, d_cnt, upper=upper)
-            out = d_pairs.get()
-            if int(d_cnt.get()[0]) != total:
-                raise C2DError(-2, "poly_broad_pairs_host", "the list call counted a different total than the count-only call")
-            return out
-        finally:
-            for x in arrays:
-                x.free()
+        arrays = self._to_device_all([vx_a, vy_a, k_a] + ([] if same else [vx_b, vy_b, k_b]))
+        a = self.poly_set(*arrays[:3], n_a, vx_a.shape[0])
+        b = a if same else self.poly_set(*arrays[3:], n_b, vx_b.shape[0])
+        return self._pairs_sized_exactly("poly_broad_pairs_host", arrays,
+                                         lambda pairs, cap, cnt: self.sat_poly_broad_pairs(a, b, pairs, cap, cnt, upper=upper), check_async=True)
 
     # -- binned polygon batches (include/c2d.h "binned polygon batches") ---------------
     def poly_bins_create(self, bins) -> "PolyBins":
@@ -793,9 +760,11 @@ class Engine:
                                          C.byref(_StdDev(*std_dev)), seed, scene_id, sample_begin, n_samples,
                                          _ptr_of(hits), C.c_void_p(stream)), "c2d_mc_pair")
 
-    def mc_scenes(self, poses, num_poses, std_devs, num_std_devs, scenes, n_scenes, robot_w, robot_h, accuracy_bins,
-                  bin_accuracy, max_samples, seed, scene_id_base, hits, n_used, rows=None, stream: int = 0,
-                  schedule=(0, 0, 0)):
+    @staticmethod
+    def _mc_scenes_args(poses, num_poses, std_devs, num_std_devs, scenes, n_scenes, robot_w, robot_h, accuracy_bins, bin_accuracy,
+                        max_samples, seed, scene_id_base, schedule, hits, n_used, rows, host_outputs: bool):
+        """-> (c2d_mc_scenes_args, total, iters): the argument block of the adaptive entry points, with the two host outputs
+        behind it when host_outputs (NULL otherwise: the loop is only enqueued).  The block keeps what it points to alive."""
         bins = np.ascontiguousarray(accuracy_bins, dtype=np.float32)
         acc = np.ascontiguousarray(bin_accuracy, dtype=np.float32)
         if len(acc) != len(bins) - 1:
@@ -805,7 +774,15 @@ class Engine:
                           robot_h, bins.ctypes.data_as(C.POINTER(C.c_float)), acc.ctypes.data_as(C.POINTER(C.c_float)),
                           len(bins), max_samples, seed, scene_id_base, schedule[0], schedule[1], schedule[2],
                           _ptr_of(hits), _ptr_of(n_used), _ptr_of(rows),
-                          C.pointer(total), C.pointer(iters))
+                          C.pointer(total) if host_outputs else None, C.pointer(iters) if host_outputs else None)
+        a.keep_alive = (bins, acc)
+        return a, total, iters
+
+    def mc_scenes(self, poses, num_poses, std_devs, num_std_devs, scenes, n_scenes, robot_w, robot_h, accuracy_bins,
+                  bin_accuracy, max_samples, seed, scene_id_base, hits, n_used, rows=None, stream: int = 0,
+                  schedule=(0, 0, 0)):
+        a, total, iters = self._mc_scenes_args(poses, num_poses, std_devs, num_std_devs, scenes, n_scenes, robot_w, robot_h, accuracy_bins,
+                                               bin_accuracy, max_samples, seed, scene_id_base, schedule, hits, n_used, rows, True)
         self._check(self.lib.c2d_mc_scenes(self.h, C.byref(a), C.c_void_p(stream)), "c2d_mc_scenes")
         return int(total.value), int(iters.value)
 
@@ -813,14 +790,8 @@ class Engine:
                         bin_accuracy, max_samples, seed, scene_id_base, hits, n_used, rows=None, stream: int = 0,
                         schedule=(0, 0, 0)):
         """c2d_mc_scenes without host outputs: the whole adaptive loop is only enqueued (no synchronisation)."""
-        bins = np.ascontiguousarray(accuracy_bins, dtype=np.float32)
-        acc = np.ascontiguousarray(bin_accuracy, dtype=np.float32)
-        if len(acc) != len(bins) - 1:
-            raise ValueError("bin_accuracy must have len(accuracy_bins) - 1 entries")
-        a = _McScenesArgs(_ptr_of(poses), num_poses, _ptr_of(std_devs), num_std_devs, _ptr_of(scenes), n_scenes, robot_w,
-                          robot_h, bins.ctypes.data_as(C.POINTER(C.c_float)), acc.ctypes.data_as(C.POINTER(C.c_float)),
-                          len(bins), max_samples, seed, scene_id_base, schedule[0], schedule[1], schedule[2],
-                          _ptr_of(hits), _ptr_of(n_used), _ptr_of(rows), None, None)
+        a, _, _ = self._mc_scenes_args(poses, num_poses, std_devs, num_std_devs, scenes, n_scenes, robot_w, robot_h, accuracy_bins,
+                                       bin_accuracy, max_samples, seed, scene_id_base, schedule, hits, n_used, rows, False)
         self._check(self.lib.c2d_mc_scenes(self.h, C.byref(a), C.c_void_p(stream)), "c2d_mc_scenes")
 
     def mc_poly_pair(self, robot, pos, robot_theta, obstacle, std_dev, seed, scene_id, sample_begin, n_samples, hits, stream: int = 0):
@@ -833,16 +804,8 @@ class Engine:
     def mc_poly_scenes(self, robot, poly_poses, num_poly_poses, std_devs, num_std_devs, scenes, n_scenes, accuracy_bins, bin_accuracy, max_samples,
                        seed, scene_id_base, hits, n_used, rows=None, stream: int = 0, schedule=(0, 0, 0), host_outputs: bool = True):
         """c2d_mc_poly_scenes; with host_outputs=False the loop is only enqueued (no synchronisation) and None is returned"""
-        bins = np.ascontiguousarray(accuracy_bins, dtype=np.float32)
-        acc = np.ascontiguousarray(bin_accuracy, dtype=np.float32)
-        if len(acc) != len(bins) - 1:
-            raise ValueError("bin_accuracy must have len(accuracy_bins) - 1 entries")
-        total, iters = C.c_uint64(0), C.c_uint32(0)
-        base = _McScenesArgs(None, 0, _ptr_of(std_devs), num_std_devs, _ptr_of(scenes), n_scenes, 0.0, 0.0,
-                             bins.ctypes.data_as(C.POINTER(C.c_float)), acc.ctypes.data_as(C.POINTER(C.c_float)),
-                             len(bins), max_samples, seed, scene_id_base, schedule[0], schedule[1], schedule[2],
-                             _ptr_of(hits), _ptr_of(n_used), _ptr_of(rows),
-                             C.pointer(total) if host_outputs else None, C.pointer(iters) if host_outputs else None)
+        base, total, iters = self._mc_scenes_args(None, 0, std_devs, num_std_devs, scenes, n_scenes, 0.0, 0.0, accuracy_bins, bin_accuracy,
+                                                  max_samples, seed, scene_id_base, schedule, hits, n_used, rows, host_outputs)
         r = None if robot is None else (make_polygon(*robot) if isinstance(robot, tuple) else make_polygon(robot))
         a = _McPolyScenesArgs(base, C.pointer(r) if r is not None else None, _ptr_of(poly_poses), num_poly_poses)
         self._check(self.lib.c2d_mc_poly_scenes(self.h, C.byref(a), C.c_void_p(stream)), "c2d_mc_poly_scenes")

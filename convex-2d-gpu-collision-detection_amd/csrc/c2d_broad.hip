@@ -539,11 +539,7 @@ int c2d_sat_rect_broad_pairs(c2d_ctx* ctx, const float* const d_a[8], size_t n_a
         B.p[k] = d_b[k];
         same = same && d_a[k] == d_b[k];
     }
-    if (flags & ~C2D_CROSS_UPPER) return fail_arg(ctx, "c2d_sat_rect_broad_pairs: unknown flag");
-    if (!d_count) return fail_arg(ctx, "c2d_sat_rect_broad_pairs: d_count is required");
-    if (!d_pairs && capacity) return fail_arg(ctx, "c2d_sat_rect_broad_pairs: NULL pair buffer");
-    if (n_a > kBroadIndexLimit || n_b > kBroadIndexLimit)
-        return fail_arg(ctx, "c2d_sat_rect_broad_pairs: n_a and n_b must stay at or below 2^32 (the list is u32)");
+    if (int rc = broad_check_list(ctx, "c2d_sat_rect_broad_pairs", flags, d_pairs, capacity, d_count, n_a, n_b)) return rc;
     DeviceGuard dg(ctx->device);
     return broad_run<RectShape>(ctx, (hipStream_t)stream, "c2d_sat_rect_broad_pairs", A, n_a, B, n_b, same, flags, d_pairs, capacity, d_count);
 }

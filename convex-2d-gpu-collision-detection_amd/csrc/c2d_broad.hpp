@@ -13,8 +13,9 @@
 // c2d_poly_broad.hip for convex polygons.
 #pragma once
 
-#include "c2d_internal.hpp"
+#include "c2d_cross.hpp"
 #include "c2d_math.hpp"
+#include "c2d_wave.hpp"
 
 namespace c2d {
 
@@ -379,9 +380,7 @@ __global__ __launch_bounds__(kBroadBlock) void broad_long_emit_kernel(BroadQuery
                     if (hit && at < (uint32_t)kMidHits) hits[wave][at] = j;
                     m += (uint32_t)__popcll(bal);
                 }
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
                 if ((unsigned long long)m == cnt) {   // always (the count pass ran the same query); the guard keeps writes in the row's range
                     for (uint32_t e = lane; e < m; e += 64) {
                         const uint32_t v = hits[wave][e];
@@ -416,6 +415,14 @@ __global__ __launch_bounds__(kBroadBlock) void broad_long_emit_kernel(BroadQuery
 // ---- host side: the shape-independent stages live in c2d_broad.hip ------------------------------------------------------
 
 constexpr size_t kBroadIndexLimit = (size_t)1 << 32;   // the list's indices are u32
+
+// the flags and the list arguments of a broad entry point (row_base = col_base = 0: the indices end at n_a, n_b)
+inline int broad_check_list(c2d_ctx* ctx, const char* what, int flags, const uint32_t* d_pairs, size_t capacity, const unsigned long long* d_count,
+                            size_t n_a, size_t n_b)
+{
+    if (int rc = cross_check_flags(ctx, what, flags)) return rc;
+    return cross_check_list(ctx, what, d_pairs, capacity, d_count, n_a, n_b, kBroadIndexLimit, "n_a and n_b must stay at or below 2^32 (the list is u32)");
+}
 
 // the scratch of one call, carved (broad_layout: every size depends on n_a, n_b and whether B is A, never on the input's values)
 struct BroadScratch {

@@ -17,9 +17,10 @@
 //
 // The pair list runs the mask kernel over row passes of A into ctx scratch, counts each row's bits, scans the counts on the
 // device (the running base of earlier passes stays on the device) and emits the pairs whose position is below the capacity.
-#include "c2d_internal.hpp"
+#include "c2d_cross.hpp"
 #include "c2d_math.hpp"
 #include "c2d_count.hpp"
+#include "c2d_wave.hpp"
 
 namespace c2d {
 
@@ -28,7 +29,6 @@ struct CrossPlanes { const float* p[8]; };
 constexpr int kCrossBlock = 256;      // rows of A per block: one per lane
 constexpr int kCrossCols = 256;       // columns of B per block: four mask words
 constexpr int kSideVecs = 6;          // one rectangle's hoisted quantities: 24 floats, six 16-byte LDS reads
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // The quantities of convex_collide that depend on one rectangle only.  Every field is computed by the same IEEE operations,
 // in the same order, as rect_collide_certified (c2d_math.hpp) computes it inside a pair, so the pair test below sees the
@@ -136,14 +136,6 @@ C2D_DEV bool cross_collide_certified(const RectSide& A, const RectSide& B, bool&
     return !sep;
 }
 
-// the fall-back's inputs go through an empty asm, so that the compiler does not keep the fast path's projections alive for
-// reuse there (the same device as collide_pairs in c2d_sat.hip)
-C2D_DEV float cross_launder(float x)
-{
-    asm volatile("" : "+v"(x));
-    return x;
-}
-
 // Result (i, j) for the lane's row i and the wave-uniform column held in `col`, fast path and wave-wide fall-back.
 C2D_DEV uint32_t cross_pair(const RectSide& a, const f32x4 (&col)[kSideVecs])
 {
@@ -155,8 +147,8 @@ C2D_DEV uint32_t cross_pair(const RectSide& a, const f32x4 (&col)[kSideVecs])
         float r1[8], r2[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-            r1[k] = cross_launder(a.v[k]);
-            r2[k] = cross_launder(b.v[k]);
+            r1[k] = launder(a.v[k], Laundered{});   // (as collide_pairs of c2d_sat.hip: nothing of the fast path is kept alive)
+            r2[k] = launder(b.v[k], Laundered{});
         }
         const bool full = rect_collide(r1, r2);
         hit = thin ? full : hit;
@@ -337,8 +329,6 @@ __global__ __launch_bounds__(kListBlock) void cross_emit_kernel(const unsigned l
 // ---- host side ----------------------------------------------------------------------------------------------------------
 
 constexpr size_t kPairScratchMaskBytes = (size_t)256 << 20;   // mask rows of one pass of the pair list
-constexpr size_t kIndexLimit = (size_t)1 << 32;               // the pair list's indices are u32
-constexpr size_t kBaseLimit = (size_t)1 << 62;                // row_base + n_a, col_base + n_b stay far from signed overflow
 
 static bool cross_planes(const float* const d[8], CrossPlanes& P)
 {
@@ -353,17 +343,9 @@ static bool cross_planes(const float* const d[8], CrossPlanes& P)
 static int cross_check(c2d_ctx* ctx, const char* what, const float* const d_a[8], size_t n_a, const float* const d_b[8], size_t n_b,
                 size_t row_base, size_t col_base, int flags, CrossPlanes& A, CrossPlanes& B)
 {
-    char msg[160];
-    auto fail = [&](const char* why) {
-        std::snprintf(msg, sizeof msg, "%s: %s", what, why);
-        return fail_arg(ctx, msg);
-    };
-    if (!d_a || !d_b) return fail("NULL argument");
-    if (!cross_planes(d_a, A) || !cross_planes(d_b, B)) return fail("NULL plane");
-    if (flags & ~C2D_CROSS_UPPER) return fail("unknown flag");
-    if (n_a > kBaseLimit || n_b > kBaseLimit || row_base > kBaseLimit - n_a || col_base > kBaseLimit - n_b)
-        return fail("row_base + n_a and col_base + n_b must stay below 2^62");
-    return C2D_OK;
+    if (!d_a || !d_b) return cross_fail(ctx, what, "NULL argument");
+    if (!cross_planes(d_a, A) || !cross_planes(d_b, B)) return cross_fail(ctx, what, "NULL plane");
+    return cross_check_flags_bases(ctx, what, n_a, n_b, row_base, col_base, flags);
 }
 
 // The mask of rows [0, n_a) x columns [0, n_b) into `mask` (row stride ld_words), in launches of at most kMaxGrid blocks.
@@ -371,37 +353,25 @@ static int cross_mask_launch(c2d_ctx* ctx, hipStream_t s, const CrossPlanes& A, 
                       size_t col_base, bool upper, unsigned long long* mask, size_t ld_words, unsigned long long* d_count)
 {
     const size_t row_tiles = (n_a + kCrossBlock - 1) / kCrossBlock, col_tiles = (n_b + kCrossCols - 1) / kCrossCols;
-    const size_t col_step = col_tiles < (size_t)kMaxGrid ? col_tiles : (size_t)kMaxGrid;
     const long long diag = (long long)row_base - (long long)col_base;
-    for (size_t c0 = 0; c0 < col_tiles; c0 += col_step) {
-        const size_t cols = col_tiles - c0 < col_step ? col_tiles - c0 : col_step;
-        const size_t row_step = (size_t)kMaxGrid / cols;
-        for (size_t r0 = 0; r0 < row_tiles; r0 += row_step) {
-            const size_t rows = row_tiles - r0 < row_step ? row_tiles - r0 : row_step;
-            const size_t grid = rows * cols;
-            hipLaunchKernelGGL(cross_mask_kernel, dim3((unsigned)grid), dim3(kCrossBlock), 0, s, A, n_a, B, n_b, r0, c0, (uint32_t)cols, diag,
-                               upper ? 1 : 0, mask, ld_words, d_count,
-                               workspace_count_ticket(ctx, s, grid * (kCrossBlock / 64), d_count != nullptr));
-            C2D_LAUNCH_CHECK(ctx);
-        }
-    }
-    return C2D_OK;
+    return for_each_tile_launch(row_tiles, col_tiles, (size_t)kMaxGrid, [&](size_t r0, size_t c0, size_t rows, size_t cols) {
+        const size_t grid = rows * cols;
+        hipLaunchKernelGGL(cross_mask_kernel, dim3((unsigned)grid), dim3(kCrossBlock), 0, s, A, n_a, B, n_b, r0, c0, (uint32_t)cols, diag,
+                           upper ? 1 : 0, mask, ld_words, d_count, workspace_count_ticket(ctx, s, grid * (kCrossBlock / 64), d_count != nullptr));
+        C2D_LAUNCH_CHECK(ctx);
+        return (int)C2D_OK;
+    });
 }
 
-// The pair list of any N x M mask producer (declared in c2d_internal.hpp; the polygon form, c2d_poly_cross.hip, is the second
+// The pair list of any N x M mask producer (declared in c2d_cross.hpp; the polygon form, c2d_poly_cross.hip, is the second
 // caller): `pass` queues the counting mask kernel(s) of rows [r0, r0 + rows) of A into `mask` (row stride `words`); the row
 // counts, the chunk scan with the running base on the device and the emit follow each pass.
 int cross_list_run(c2d_ctx* ctx, hipStream_t s, const char* what, size_t n_a, size_t n_b, size_t row_base, size_t col_base, uint32_t* d_pairs,
                    size_t capacity, unsigned long long* d_count, const CrossMaskPass& pass)
 {
-    char msg[256];
-    auto fail = [&](const char* why) {
-        std::snprintf(msg, sizeof msg, "%s: %s", what, why);
-        return fail_arg(ctx, msg);
-    };
-    if (!d_count) return fail("d_count is required");
-    if (!d_pairs && capacity) return fail("NULL pair buffer");
-    if (row_base + n_a > kIndexLimit || col_base + n_b > kIndexLimit) return fail("global indices must stay below 2^32 (the list is u32)");
+    if (int rc = cross_check_list(ctx, what, d_pairs, capacity, d_count, row_base + n_a, col_base + n_b, kIndexLimit,
+                                  "global indices must stay below 2^32 (the list is u32)"))
+        return rc;
     // scratch: [rows_pass][words] mask | [rows_pass] row offsets | [chunks] chunk sums | running base
     const size_t words = (n_b + 63) / 64;
     size_t rows_pass = kPairScratchMaskBytes / (words * 8);
@@ -415,7 +385,7 @@ int cross_list_run(c2d_ctx* ctx, hipStream_t s, const char* what, size_t n_a, si
     if (int rc = workspace_acquire(ctx, s, true)) return rc;
     if (ctx->scratch_bytes < need) {
         if (stream_is_capturing(s))
-            return fail("the ctx scratch must grow, which cannot happen during graph capture (make the call once outside the capture first)");
+            return cross_fail(ctx, what, "the ctx scratch must grow, which cannot happen during graph capture (make the call once outside the capture first)");
         if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
         ctx->d_scratch = nullptr;
         ctx->scratch_bytes = 0;
@@ -460,9 +430,7 @@ int c2d_sat_rect_cross_mask(c2d_ctx* ctx, const float* const d_a[8], size_t n_a,
     if (n_a == 0 || n_b == 0) return C2D_OK;
     CrossPlanes A, B;
     if (int rc = cross_check(ctx, "c2d_sat_rect_cross_mask", d_a, n_a, d_b, n_b, row_base, col_base, flags, A, B)) return rc;
-    if (!d_mask) return fail_arg(ctx, "c2d_sat_rect_cross_mask: NULL mask");
-    if (reinterpret_cast<uintptr_t>(d_mask) & 7u) return fail_arg(ctx, "c2d_sat_rect_cross_mask: the mask must be 8-byte aligned");
-    if (ld_words < (n_b + 63) / 64) return fail_arg(ctx, "c2d_sat_rect_cross_mask: ld_words < ceil(n_b / 64)");
+    if (int rc = cross_check_mask(ctx, "c2d_sat_rect_cross_mask", d_mask, ld_words, n_b)) return rc;
     DeviceGuard g(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = workspace_acquire(ctx, s, d_count != nullptr)) return rc;

@@ -6,7 +6,6 @@
 
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <string>
 
 #include "../../include/c2d.h"
@@ -307,14 +306,6 @@ inline void workspace_launch_failed(c2d_ctx* ctx)
 }
 inline void workspace_launch_ok(const c2d_ctx*) {}       // (entry points that hold the ctx const take no tickets)
 inline void workspace_launch_failed(const c2d_ctx*) {}
-
-// The pair list behind an N x M bit mask (c2d_cross.hip): row passes of A through the ctx scratch, per pass the mask rows
-// (`pass` queues the counting mask kernel of rows [r0, r0 + rows) into d_mask, row stride `words`), the row counts, the chunk scan
-// with the running base on the device, and the emit.  Checks d_count / d_pairs / the u32 index limit, grows the scratch (refused
-// during graph capture).  The caller holds the DeviceGuard.  Shared by the rectangle and the polygon forms.
-using CrossMaskPass = std::function<int(size_t r0, size_t rows, unsigned long long* d_mask, size_t words)>;
-int cross_list_run(c2d_ctx* ctx, hipStream_t s, const char* what, size_t n_a, size_t n_b, size_t row_base, size_t col_base, uint32_t* d_pairs,
-                   size_t capacity, unsigned long long* d_count, const CrossMaskPass& pass);
 
 inline int grid_for(size_t work_items, int block, int max_blocks)
 {

@@ -229,6 +229,17 @@ C2D_DEV void rect_from_half_extents(float hx, float hy, float c, float s, float 
     r[7] = dy - t4;  // (-p) +   q  + dy
 }
 
+// One step of a convex polygon's projection interval (reference utils.cu:173, then minmax_element): the projection of vertex
+// (x, y) onto the axis (nx, ny) and the running min / max.  The one definition for every polygon kernel, pairwise, binned, N x M
+// and broad phase, whose results are promised bit-equal to each other.  The product sum is unfused in EVERY build, independent
+// of C2D_FMAD (the translation units are -ffp-contract=off): the validation builds contract the rectangle paths only.
+C2D_DEV void poly_minmax(float nx, float ny, float x, float y, float& mn, float& mx)
+{
+    const float p = nx * x + ny * y;
+    mn = __builtin_fminf(mn, p);
+    mx = __builtin_fmaxf(mx, p);
+}
+
 C2D_DEV float min4(float a, float b, float c, float d) { return __builtin_fminf(__builtin_fminf(a, b), __builtin_fminf(c, d)); }
 C2D_DEV float max4(float a, float b, float c, float d) { return __builtin_fmaxf(__builtin_fmaxf(a, b), __builtin_fmaxf(c, d)); }
 

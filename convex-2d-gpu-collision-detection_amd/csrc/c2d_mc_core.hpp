@@ -19,6 +19,7 @@
 
 #include "c2d_internal.hpp"
 #include "c2d_math.hpp"
+#include "c2d_wave.hpp"
 
 #ifndef C2D_MC_STAT
 #define C2D_MC_STAT(i, v) do { } while (0)
@@ -142,13 +143,6 @@ union SampleQueues {
         uint32_t und_idx[kQueueSlots];
     } far;
 };
-
-C2D_DEV void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // ---- evaluation of queued undecided samples (centre, offset): the last `take` (<= 64) of `n` entries.  Each lane draws the
 // block of ITS sample's second Box-Muller pair (block 2 or 3 of the sample's group).  Lanes read slots that other lanes of this wave
@@ -314,16 +308,12 @@ C2D_DEV uint32_t wave_count_hits_far(const typename P::Scene& sc, uint64_t seed,
         // ---- stage 2: up to 64 candidates (fewer only when the input has ended).  Lanes read slots other lanes of this
         // wave wrote; the fences only constrain the compiler (see wave_count_hits_near)
         if (cn) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             const uint32_t take = cn < 64 ? cn : 64;
             const bool live = lane < take;
             const unsigned long long live_m = take >= 64 ? ~0ull : (1ull << take) - 1;
             const uint2 e = q.cand[cn - take + (live ? lane : 0)];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             cn -= take;
             const uint64_t s = begin + e.y;
             const U4 a = philox_draw_block(seed, scene_id, s >> 2, 1);

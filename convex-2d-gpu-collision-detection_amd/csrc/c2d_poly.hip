@@ -28,27 +28,11 @@
 #include "c2d_internal.hpp"
 #include "c2d_math.hpp"
 #include "c2d_count.hpp"
+#include "c2d_wave.hpp"
 
 namespace c2d {
 
 constexpr int kSlots = 8;          // undecided pairs parked in LDS per group (16 KM bytes each)
-
-C2D_DEV void minmax_update(float nx, float ny, float x, float y, float& mn, float& mx)
-{
-    const float p = nx * x + ny * y;  // unfused (translation unit is -ffp-contract=off), utils.cu:173
-    mn = __builtin_fminf(mn, p);
-    mx = __builtin_fmaxf(mx, p);
-}
-
-C2D_DEV uint32_t wave_max_u32(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64);
-        v = o > v ? o : v;
-    }
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
 
 // One wave = one tile of 64 pairs.  KM (4, 8 or 16) is the number of vertex slots a lane holds per polygon: the
 // smallest that covers the layout's `rows` (vertex rows per polygon in memory, f32[2][rows][n]).  Small polygons
@@ -168,10 +152,10 @@ __global__ __launch_bounds__(64, MIN_WAVES) void sat_poly_kernel(const float* __
         float mnA = __builtin_inff(), mxA = -__builtin_inff(), mnB = __builtin_inff(), mxB = -__builtin_inff();
 #pragma unroll
         for (int r = 0; r < KM; r++)
-            if (r < kmaxA) minmax_update(nx1, ny1, ax[r], ay[r], mnA, mxA);
+            if (r < kmaxA) poly_minmax(nx1, ny1, ax[r], ay[r], mnA, mxA);
 #pragma unroll
         for (int r = 0; r < KM; r++)
-            if (r < kmaxB) minmax_update(nx1, ny1, bx[r], by[r], mnB, mxB);
+            if (r < kmaxB) poly_minmax(nx1, ny1, bx[r], by[r], mnB, mxB);
         // (a NaN first projection keeps an axis from separating, as the comparison-based extremes of utils.cu:176-178
         // would: see first_projections_ordered in c2d_math.hpp)
         bool sep = ((mxA < mnB) || (mxB < mnA)) && first_projections_ordered(nx1 * ax[0] + ny1 * ay[0], nx1 * bx[0] + ny1 * by[0]);
@@ -229,15 +213,15 @@ __global__ __launch_bounds__(64, MIN_WAVES) void sat_poly_kernel(const float* __
                 float4 q4 = S4[0];
                 for (int r2 = 0; 2 * r2 < kA; r2++) {
                     const float4 qn = S4[r2 + 1];  // r2 + 1 <= KM / 2: at worst B's first pair, always inside the slot
-                    minmax_update(nx, ny, q4.x, q4.y, mn1, mx1);
-                    minmax_update(nx, ny, q4.z, q4.w, mn1, mx1);
+                    poly_minmax(nx, ny, q4.x, q4.y, mn1, mx1);
+                    poly_minmax(nx, ny, q4.z, q4.w, mn1, mx1);
                     q4 = qn;
                 }
                 q4 = S4[KM / 2];
                 for (int r2 = 0; 2 * r2 < kB; r2++) {
                     const float4 qn = S4[KM / 2 + ((r2 + 1) & (KM / 2 - 1))];
-                    minmax_update(nx, ny, q4.x, q4.y, mn2, mx2);
-                    minmax_update(nx, ny, q4.z, q4.w, mn2, mx2);
+                    poly_minmax(nx, ny, q4.x, q4.y, mn2, mx2);
+                    poly_minmax(nx, ny, q4.z, q4.w, mn2, mx2);
                     q4 = qn;
                 }
                 const float pa0 = nx * S[0].x + ny * S[0].y, pb0 = nx * S[KM].x + ny * S[KM].y;  // first projections (vertex 0 of A, of B)
@@ -262,7 +246,6 @@ __global__ __launch_bounds__(64, MIN_WAVES) void sat_poly_kernel(const float* __
 // costs, so there is nothing to gain from a cheap first axis: a lane takes 4 consecutive pairs with 16-byte loads (16
 // loads in flight, as sat_rect_verts_kernel), pads each polygon by repeating vertex 0 (exactly neutral, see above) and
 // evaluates everything in registers.  No LDS, no second phase: dense and sparse scenes run at the same, HBM-bound rate.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(64) void sat_poly4_kernel(const float* __restrict__ vx, const float* __restrict__ vy,
                                                        const uint8_t* __restrict__ kcnt, size_t n, size_t n_groups,
@@ -305,8 +288,8 @@ __global__ __launch_bounds__(64) void sat_poly4_kernel(const float* __restrict__
                 float mn1 = __builtin_inff(), mx1 = -__builtin_inff(), mn2 = __builtin_inff(), mx2 = -__builtin_inff();
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
-                    minmax_update(nx, ny, px[r], py[r], mn1, mx1);
-                    minmax_update(nx, ny, px[4 + r], py[4 + r], mn2, mx2);
+                    poly_minmax(nx, ny, px[r], py[r], mn1, mx1);
+                    poly_minmax(nx, ny, px[4 + r], py[4 + r], mn2, mx2);
                 }
                 sep |= ((mx1 < mn2) || (mx2 < mn1)) && first_projections_ordered(nx * px[0] + ny * py[0], nx * px[4] + ny * py[4]);
             }

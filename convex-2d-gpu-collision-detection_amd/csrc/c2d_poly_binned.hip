@@ -47,13 +47,6 @@ struct alignas(8) BinDesc {
 };
 static_assert(sizeof(BinDesc) == 72, "BinDesc layout");
 
-C2D_DEV void binned_minmax(float nx, float ny, float x, float y, float& mn, float& mx)
-{
-    const float p = nx * x + ny * y;  // unfused (translation unit is -ffp-contract=off), utils.cu:173
-    mn = __builtin_fminf(mn, p);
-    mx = __builtin_fmaxf(mx, p);
-}
-
 // One plane of a bin as a raw buffer: a row is addressed as (lane offset in a VGPR) + (row offset in ONE SGPR), so stepping to
 // the next row costs one scalar add for both coordinates (a flat 64-bit row pointer costs two per plane).  Planes are below
 // 4 GiB (checked when the table is built).
@@ -166,9 +159,9 @@ C2D_DEV bool binned_phase1(const BinDesc& D, uint32_t p0, uint32_t cl, bool& bad
     }
     float mnA = __builtin_inff(), mxA = -__builtin_inff(), mnB = __builtin_inff(), mxB = -__builtin_inff();
 #pragma unroll
-    for (int r = 0; r < CA; r++) binned_minmax(nx1, ny1, ax[r], ay[r], mnA, mxA);
+    for (int r = 0; r < CA; r++) poly_minmax(nx1, ny1, ax[r], ay[r], mnA, mxA);
 #pragma unroll
-    for (int r = 0; r < CB; r++) binned_minmax(nx1, ny1, bx[r], by[r], mnB, mxB);
+    for (int r = 0; r < CB; r++) poly_minmax(nx1, ny1, bx[r], by[r], mnB, mxB);
     // (a NaN first projection keeps an axis from separating: first_projections_ordered, c2d_math.hpp)
     return ((mxA < mnB) || (mxB < mnA)) && first_projections_ordered(nx1 * ax[0] + ny1 * ay[0], nx1 * bx[0] + ny1 * by[0]);
 }
@@ -285,28 +278,28 @@ C2D_DEV uint32_t binned_tile(const BinDesc& D, uint32_t tile_in_bin, uint32_t* _
                     int r2 = 0;
                     for (; r2 + 1 < na2; r2 += 2) {
                         const float4 qa = SA[r2], qb = SA[r2 + 1];
-                        binned_minmax(nx, ny, qa.x, qa.y, mn1, mx1);
-                        binned_minmax(nx, ny, qa.z, qa.w, mn1, mx1);
-                        binned_minmax(nx, ny, qb.x, qb.y, mn1, mx1);
-                        binned_minmax(nx, ny, qb.z, qb.w, mn1, mx1);
+                        poly_minmax(nx, ny, qa.x, qa.y, mn1, mx1);
+                        poly_minmax(nx, ny, qa.z, qa.w, mn1, mx1);
+                        poly_minmax(nx, ny, qb.x, qb.y, mn1, mx1);
+                        poly_minmax(nx, ny, qb.z, qb.w, mn1, mx1);
                     }
                     if (r2 < na2) {
                         const float4 q4 = SA[r2];
-                        binned_minmax(nx, ny, q4.x, q4.y, mn1, mx1);
-                        binned_minmax(nx, ny, q4.z, q4.w, mn1, mx1);
+                        poly_minmax(nx, ny, q4.x, q4.y, mn1, mx1);
+                        poly_minmax(nx, ny, q4.z, q4.w, mn1, mx1);
                     }
                     r2 = 0;
                     for (; r2 + 1 < nb2; r2 += 2) {
                         const float4 qa = SB[r2], qb = SB[r2 + 1];
-                        binned_minmax(nx, ny, qa.x, qa.y, mn2, mx2);
-                        binned_minmax(nx, ny, qa.z, qa.w, mn2, mx2);
-                        binned_minmax(nx, ny, qb.x, qb.y, mn2, mx2);
-                        binned_minmax(nx, ny, qb.z, qb.w, mn2, mx2);
+                        poly_minmax(nx, ny, qa.x, qa.y, mn2, mx2);
+                        poly_minmax(nx, ny, qa.z, qa.w, mn2, mx2);
+                        poly_minmax(nx, ny, qb.x, qb.y, mn2, mx2);
+                        poly_minmax(nx, ny, qb.z, qb.w, mn2, mx2);
                     }
                     if (r2 < nb2) {
                         const float4 q4 = SB[r2];
-                        binned_minmax(nx, ny, q4.x, q4.y, mn2, mx2);
-                        binned_minmax(nx, ny, q4.z, q4.w, mn2, mx2);
+                        poly_minmax(nx, ny, q4.x, q4.y, mn2, mx2);
+                        poly_minmax(nx, ny, q4.z, q4.w, mn2, mx2);
                     }
                 }
                 const float pa0 = nx * S[0].x + ny * S[0].y, pb0 = nx * S[ca].x + ny * S[ca].y;  // first projections

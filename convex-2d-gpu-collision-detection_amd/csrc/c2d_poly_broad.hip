@@ -114,11 +114,7 @@ int c2d_sat_poly_broad_pairs(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly
     PolyBroadSet A, B;
     if (int rc = poly_set_check(ctx, what, "a", a, A.set)) return rc;
     if (int rc = poly_set_check(ctx, what, "b", b, B.set)) return rc;
-    if (flags & ~C2D_CROSS_UPPER) return fail_arg(ctx, "c2d_sat_poly_broad_pairs: unknown flag");
-    if (!d_count) return fail_arg(ctx, "c2d_sat_poly_broad_pairs: d_count is required");
-    if (!d_pairs && capacity) return fail_arg(ctx, "c2d_sat_poly_broad_pairs: NULL pair buffer");
-    if (A.set.n > kBroadIndexLimit || B.set.n > kBroadIndexLimit)
-        return fail_arg(ctx, "c2d_sat_poly_broad_pairs: n_a and n_b must stay at or below 2^32 (the list is u32)");
+    if (int rc = broad_check_list(ctx, what, flags, d_pairs, capacity, d_count, A.set.n, B.set.n)) return rc;
     A.async_err = B.async_err = ctx->d_async_err;
     const bool same = A.set.vx == B.set.vx && A.set.vy == B.set.vy && A.set.k == B.set.k && A.set.n == B.set.n && A.set.stride == B.set.stride &&
                       A.set.rows == B.set.rows;

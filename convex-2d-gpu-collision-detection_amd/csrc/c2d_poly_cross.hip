@@ -29,10 +29,11 @@
 // A lane builds one 64-bit mask word per 64 columns and stores it with one 8-byte store.  With C2D_CROSS_UPPER untested pairs are
 // never evaluated, and a block skips every word that lies on or below the diagonal for all of its rows.
 //
-// The pair list is the rectangle list's machinery (cross_list_run, c2d_cross.hip) over this mask kernel.
-#include "c2d_internal.hpp"
+// The pair list is the rectangle list's machinery (cross_list_run, c2d_cross.hpp) over this mask kernel.
+#include "c2d_cross.hpp"
 #include "c2d_math.hpp"
 #include "c2d_count.hpp"
+#include "c2d_wave.hpp"
 #include "c2d_poly_pair.hpp"   // PolySetDev, poly_set_check
 
 namespace c2d {
@@ -52,34 +53,6 @@ constexpr int kParkLo = 32, kParkHi = 48, kParkFloats = 64;
 // phase 2: a column with at least this many undecided rows in a wave is evaluated one pair per lane, below it two pairs per trip
 // with lanes over axes (a full per-lane evaluation costs about what eight trips cost)
 constexpr int kPcSerialMin = 16;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-C2D_DEV void pc_minmax(float nx, float ny, float x, float y, float& mn, float& mx)
-{
-    const float p = nx * x + ny * y;   // unfused in every build, as minmax_update of c2d_poly.hip (utils.cu:173)
-    mn = __builtin_fminf(mn, p);
-    mx = __builtin_fmaxf(mx, p);
-}
-
-C2D_DEV uint32_t pc_wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64);
-        v = o > v ? o : v;
-    }
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-
-// LDS written by some lanes of a wave and read by others of the SAME wave: a wave's LDS instructions execute in order, so only
-// the compiler has to be kept from moving them across this point
-C2D_DEV void pc_wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Direction -> one of 16 sectors: the octant (signs, |dy| > |dx|) and which side of 22.5 degrees inside it.  Heuristic only: any
 // input, NaN included, gives a number in 0..15.
@@ -124,7 +97,7 @@ __global__ __launch_bounds__(kPcBlock) void poly_cross_mask_kernel(PolySetDev A,
     const bool bad_a = ka < 1 || ka > A.rows;   // out of range: clamped (memory safety), reported, every pair of the row reads 0
     ka = ka < 1 ? 1 : (ka > A.rows ? A.rows : ka);
     if (__ballot(bad_a) != 0ull && wl == 0) __hip_atomic_fetch_or(async_err, C2D_ASYNC_ERR_POLY_K, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    const int kmax_a = (int)pc_wave_max((uint32_t)ka);   // wave-uniform loop bound: slots above it repeat vertex 0 in every lane
+    const int kmax_a = (int)wave_max_u32((uint32_t)ka);   // wave-uniform loop bound: slots above it repeat vertex 0 in every lane
     float ax[kPcK], ay[kPcK];
 #pragma unroll
     for (int r = 0; r < kPcK; r++) {
@@ -158,7 +131,7 @@ __global__ __launch_bounds__(kPcBlock) void poly_cross_mask_kernel(PolySetDev A,
             float mn = inf, mx = -inf;
 #pragma unroll
             for (int r = 0; r < kPcK; r++)
-                if (r < kmax_a) pc_minmax(nx, ny, ax[r], ay[r], mn, mx);
+                if (r < kmax_a) poly_minmax(nx, ny, ax[r], ay[r], mn, mx);
             const bool nan0 = __builtin_isnan(nx * ax[0] + ny * ay[0]);
             alo[a] = nan0 ? -inf : mn;
             ahi[a] = nan0 ? inf : mx;
@@ -216,8 +189,8 @@ __global__ __launch_bounds__(kPcBlock) void poly_cross_mask_kernel(PolySetDev A,
 #pragma unroll
                 for (int r2 = 0; r2 < kPcK / 2; r2++) {
                     const f32x4 q = V4[r2];
-                    pc_minmax(nx, ny, q.x, q.y, mn, mx);
-                    pc_minmax(nx, ny, q.z, q.w, mn, mx);
+                    poly_minmax(nx, ny, q.x, q.y, mn, mx);
+                    poly_minmax(nx, ny, q.z, q.w, mn, mx);
                     sx += q.x + q.z;
                     sy += q.y + q.w;
                 }
@@ -279,7 +252,7 @@ __global__ __launch_bounds__(kPcBlock) void poly_cross_mask_kernel(PolySetDev A,
                     float mn = inf, mx = -inf;
 #pragma unroll
                     for (int r = 0; r < kPcK; r++)
-                        if (r < kmax_a) pc_minmax(nx, ny, ax[r], ay[r], mn, mx);
+                        if (r < kmax_a) poly_minmax(nx, ny, ax[r], ay[r], mn, mx);
                     // (B_j's own first projection is folded into lo / hi; A_i's is checked here: first_projections_ordered)
                     const bool sep = ((hi < mn) || (mx < lo)) && !__builtin_isnan(nx * ax[0] + ny * ay[0]);
                     bool coll = row_live && (int)b > t_lane && !sep;
@@ -307,7 +280,7 @@ __global__ __launch_bounds__(kPcBlock) void poly_cross_mask_kernel(PolySetDev A,
                                 float qmn = inf, qmx = -inf;
 #pragma unroll
                                 for (int r = 0; r < kPcK; r++)
-                                    if (r < kb) pc_minmax(qnx, qny, bx[r], by[r], qmn, qmx);
+                                    if (r < kb) poly_minmax(qnx, qny, bx[r], by[r], qmn, qmx);
                                 sep2 |= ((ahi[a] < qmn) || (qmx < alo[a])) && !__builtin_isnan(qnx * bx[0] + qny * by[0]);
                             }
                         }
@@ -317,7 +290,7 @@ __global__ __launch_bounds__(kPcBlock) void poly_cross_mask_kernel(PolySetDev A,
                             float qmn = inf, qmx = -inf;
 #pragma unroll
                             for (int r = 0; r < kPcK; r++)
-                                if (r < kmax_a) pc_minmax(qnx, qny, ax[r], ay[r], qmn, qmx);
+                                if (r < kmax_a) poly_minmax(qnx, qny, ax[r], ay[r], qmn, qmx);
                             sep2 |= ((qhi < qmn) || (qmx < qlo)) && !__builtin_isnan(qnx * ax[0] + qny * ay[0]);
                         }
                         coll = coll && !sep2;
@@ -339,7 +312,7 @@ __global__ __launch_bounds__(kPcBlock) void poly_cross_mask_kernel(PolySetDev A,
                                     S4[kParkHi / 4 + r] = f32x4{ahi[4 * r], ahi[4 * r + 1], ahi[4 * r + 2], ahi[4 * r + 3]};
                                 }
                             }
-                            pc_wave_lds_sync();
+                            wave_lds_sync();
                             const float* P = s_park[wave][(wl >> 5) != 0u && o1 >= 0 ? 1 : 0];   // (without a second pair both halves test the first)
                             const float2* PV = reinterpret_cast<const float2*>(P);
                             const float2 e0 = PV[a], e1 = PV[(a + 1u) & 15u];
@@ -352,13 +325,13 @@ __global__ __launch_bounds__(kPcBlock) void poly_cross_mask_kernel(PolySetDev A,
                             float qmn = inf, qmx = -inf;
                             for (int r2 = 0; 2 * r2 < kq; r2++) {
                                 const f32x4 q = Q4[r2];
-                                pc_minmax(qnx, qny, q.x, q.y, qmn, qmx);
-                                pc_minmax(qnx, qny, q.z, q.w, qmn, qmx);
+                                poly_minmax(qnx, qny, q.x, q.y, qmn, qmx);
+                                poly_minmax(qnx, qny, q.z, q.w, qmn, qmx);
                             }
                             const unsigned long long bal = __ballot(((qhi < qmn) || (qmx < qlo)) && !__builtin_isnan(first));
                             coll = (int)wl == o0 ? (uint32_t)bal == 0u : coll;
                             coll = (int)wl == o1 ? (uint32_t)(bal >> 32) == 0u : coll;
-                            pc_wave_lds_sync();   // the slots are rewritten by the next trip
+                            wave_lds_sync();   // the slots are rewritten by the next trip
                         }
                     }
                     bits |= coll ? (1ull << b) : 0ull;
@@ -374,45 +347,28 @@ __global__ __launch_bounds__(kPcBlock) void poly_cross_mask_kernel(PolySetDev A,
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-constexpr size_t kPcBaseLimit = (size_t)1 << 62;   // row_base + n_a, col_base + n_b stay far from signed overflow
-
 // Shared argument checks of both forms; C2D_OK or the status to return.
 static int poly_cross_check(c2d_ctx* ctx, const char* what, const c2d_poly_set* a, const c2d_poly_set* b, size_t row_base, size_t col_base, int flags,
                             PolySetDev& A, PolySetDev& B)
 {
-    char msg[160];
-    auto fail = [&](const char* why) {
-        std::snprintf(msg, sizeof msg, "%s: %s", what, why);
-        return fail_arg(ctx, msg);
-    };
     if (int rc = poly_set_check(ctx, what, "a", a, A)) return rc;
     if (int rc = poly_set_check(ctx, what, "b", b, B)) return rc;
-    if (flags & ~C2D_CROSS_UPPER) return fail("unknown flag");
-    if (A.n > kPcBaseLimit || B.n > kPcBaseLimit || row_base > kPcBaseLimit - A.n || col_base > kPcBaseLimit - B.n)
-        return fail("row_base + n_a and col_base + n_b must stay below 2^62");
-    return C2D_OK;
+    return cross_check_flags_bases(ctx, what, A.n, B.n, row_base, col_base, flags);
 }
 
 // The mask of rows [0, A.n) x columns [0, B.n) into `mask` (row stride ld_words), in launches of at most kMaxGrid blocks.
-static int poly_cross_mask_launch(c2d_ctx* ctx, hipStream_t s, const PolySetDev& A, const PolySetDev& B, size_t row_base, size_t col_base, bool upper,
-                                  unsigned long long* mask, size_t ld_words, unsigned long long* d_count)
+static int cross_mask_launch(c2d_ctx* ctx, hipStream_t s, const PolySetDev& A, const PolySetDev& B, size_t row_base, size_t col_base, bool upper,
+                             unsigned long long* mask, size_t ld_words, unsigned long long* d_count)
 {
     const size_t row_tiles = (A.n + kPcBlock - 1) / kPcBlock, col_tiles = (B.n + kPcCols - 1) / kPcCols;
-    const size_t col_step = col_tiles < (size_t)kMaxGrid ? col_tiles : (size_t)kMaxGrid;
     const long long diag = (long long)row_base - (long long)col_base;
-    for (size_t c0 = 0; c0 < col_tiles; c0 += col_step) {
-        const size_t cols = col_tiles - c0 < col_step ? col_tiles - c0 : col_step;
-        const size_t row_step = (size_t)kMaxGrid / cols;
-        for (size_t r0 = 0; r0 < row_tiles; r0 += row_step) {
-            const size_t rows = row_tiles - r0 < row_step ? row_tiles - r0 : row_step;
-            const size_t grid = rows * cols;
-            hipLaunchKernelGGL(poly_cross_mask_kernel, dim3((unsigned)grid), dim3(kPcBlock), 0, s, A, B, r0, c0, (uint32_t)cols, diag, upper ? 1 : 0,
-                               mask, ld_words, d_count, workspace_count_ticket(ctx, s, grid * (kPcBlock / 64), d_count != nullptr),
-                               ctx->d_async_err);
-            C2D_LAUNCH_CHECK(ctx);
-        }
-    }
-    return C2D_OK;
+    return for_each_tile_launch(row_tiles, col_tiles, (size_t)kMaxGrid, [&](size_t r0, size_t c0, size_t rows, size_t cols) {
+        const size_t grid = rows * cols;
+        hipLaunchKernelGGL(poly_cross_mask_kernel, dim3((unsigned)grid), dim3(kPcBlock), 0, s, A, B, r0, c0, (uint32_t)cols, diag, upper ? 1 : 0, mask,
+                           ld_words, d_count, workspace_count_ticket(ctx, s, grid * (kPcBlock / 64), d_count != nullptr), ctx->d_async_err);
+        C2D_LAUNCH_CHECK(ctx);
+        return (int)C2D_OK;
+    });
 }
 
 }  // namespace c2d
@@ -429,13 +385,11 @@ int c2d_sat_poly_cross_mask(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_
     if (a->n == 0 || b->n == 0) return C2D_OK;
     PolySetDev A, B;
     if (int rc = poly_cross_check(ctx, "c2d_sat_poly_cross_mask", a, b, row_base, col_base, flags, A, B)) return rc;
-    if (!d_mask) return fail_arg(ctx, "c2d_sat_poly_cross_mask: NULL mask");
-    if (reinterpret_cast<uintptr_t>(d_mask) & 7u) return fail_arg(ctx, "c2d_sat_poly_cross_mask: the mask must be 8-byte aligned");
-    if (ld_words < (B.n + 63) / 64) return fail_arg(ctx, "c2d_sat_poly_cross_mask: ld_words < ceil(n_b / 64)");
+    if (int rc = cross_check_mask(ctx, "c2d_sat_poly_cross_mask", d_mask, ld_words, B.n)) return rc;
     DeviceGuard g(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = workspace_acquire(ctx, s, d_count != nullptr)) return rc;
-    return poly_cross_mask_launch(ctx, s, A, B, row_base, col_base, (flags & C2D_CROSS_UPPER) != 0, d_mask, ld_words, d_count);
+    return cross_mask_launch(ctx, s, A, B, row_base, col_base, (flags & C2D_CROSS_UPPER) != 0, d_mask, ld_words, d_count);
 }
 
 int c2d_sat_poly_cross_pairs(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b, size_t row_base, size_t col_base, int flags,
@@ -456,7 +410,7 @@ int c2d_sat_poly_cross_pairs(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly
                               Ar.vy += r0;
                               if (Ar.k) Ar.k += r0;
                               Ar.n = rows;
-                              return poly_cross_mask_launch(ctx, s, Ar, B, row_base + r0, col_base, upper, d_mask, words, d_count);
+                              return cross_mask_launch(ctx, s, Ar, B, row_base + r0, col_base, upper, d_mask, words, d_count);
                           });
 }
 

@@ -1,7 +1,7 @@
 // c2d_poly_pair.hpp — one convex polygon of a c2d_poly_set in registers, and the exact polygon test of one pair per lane.
 //
 // poly_collide(A, B) is value-equal to what c2d_sat_poly_pairs_rows computes for the pair (c2d_poly.hip): the true normals
-// (-e.y, e.x) of all ka + kb own edges, projections nx * x + ny * y unfused in every build (minmax_update), strict <, and the NaN rule
+// (-e.y, e.x) of all ka + kb own edges, projections nx * x + ny * y unfused in every build (poly_minmax, c2d_math.hpp), strict <, and the NaN rule
 // of first_projections_ordered (c2d_math.hpp).  It is the form for callers whose lanes hold unrelated pairs (the broad phase,
 // c2d_poly_broad.hip): every loop runs over the 16 vertex slots with compile-time indices, so the vertices stay in registers.
 // Slots >= k repeat vertex 0, which is exactly neutral: a repeated vertex adds a zero-length edge, whose axis (0, 0) never
@@ -74,13 +74,6 @@ C2D_DEV void poly_load(const PolySetDev& X, size_t i, PolyObj& p)
             p.y[r] = X.vy[(size_t)r * X.stride + i];
         }
     }
-}
-
-C2D_DEV void poly_minmax(float nx, float ny, float x, float y, float& mn, float& mx)
-{
-    const float p = nx * x + ny * y;   // unfused in every build, as minmax_update of c2d_poly.hip (utils.cu:173)
-    mn = __builtin_fminf(mn, p);
-    mx = __builtin_fmaxf(mx, p);
 }
 
 // "some own edge normal of P separates P and Q".  Axes >= P.k are zero vectors and are skipped (they never separate).

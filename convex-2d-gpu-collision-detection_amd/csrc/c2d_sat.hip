@@ -12,6 +12,7 @@
 #include "c2d_internal.hpp"
 #include "c2d_math.hpp"
 #include "c2d_count.hpp"
+#include "c2d_wave.hpp"
 
 namespace c2d {
 
@@ -22,23 +23,15 @@ struct Planes8 { float* p[8]; };
 constexpr int kBlock = 256;
 constexpr int kWideBlock = 64;          // the 4-pairs-per-lane kernel runs one wave per block
 constexpr int kMaxBlocks = kMaxGrid;     // beyond this a launch falls back to its grid-stride loop
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- the pairs of one lane: certified fast path, wave-wide fall-back ----------------------------------------------------
 // rect_collide_certified (c2d_math.hpp) evaluates four of the eight axes and certifies the other four from the overlaps it
 // saw; a pair whose certificate fails is "thin".  Thin pairs are rare (config 2: a wave in a few thousand), so the wave votes:
 // if any lane holds one, every lane evaluates its pairs again with all eight axes (rect_collide) — straight-line code, no
 // divergence.  `build(e, launder, r1, r2)` fills pair e of the lane; in the fall-back it is asked to launder its inputs through
-// an empty asm, otherwise the compiler keeps every projection of the fast path alive for reuse there (172 spilled dwords).
+// an empty asm (launder, c2d_wave.hpp), otherwise the compiler keeps every projection of the fast path alive for reuse there
+// (172 spilled dwords).
 // Returns bit e = pair e collides.  Headline kernel 104.5 -> 103.3 us, pose format 85.9 -> 74.9 us per 1e7 pairs.
-struct Plain {};
-struct Laundered {};
-C2D_DEV float launder(float x, Plain) { return x; }
-C2D_DEV float launder(float x, Laundered)
-{
-    asm volatile("" : "+v"(x));
-    return x;
-}
 
 template <int PAIRS, class Build>
 C2D_DEV uint32_t collide_pairs(Build build)
@@ -70,9 +63,6 @@ C2D_DEV uint32_t bits_to_bytes4(uint32_t b) { return (b & 1u) | ((b & 2u) << 7) 
 // ---- rectangle pairs, vertex format ------------------------------------------
 // VEC == 4: planes read as float4 (16 B / lane), results written as one dword.
 // VEC == 1: scalar loads; used for the tail and for unaligned buffers.
-#ifndef C2D_SAT_PRIO
-#define C2D_SAT_PRIO 0
-#endif
 template <int VEC, int BLOCK>
 __global__ __launch_bounds__(BLOCK, (VEC == 4 ? 5 : 1)) void sat_rect_verts_kernel(Planes16 P, size_t first, size_t n_groups,
                                                                 uint8_t* __restrict__ out,
@@ -83,17 +73,8 @@ __global__ __launch_bounds__(BLOCK, (VEC == 4 ? 5 : 1)) void sat_rect_verts_kern
     for (size_t g = (size_t)blockIdx.x * BLOCK + threadIdx.x; g < n_groups; g += stride) {
         if constexpr (VEC == 4) {
             f32x4 v[16];
-#if C2D_SAT_PRIO == 1  // (experiment: the wave's address arithmetic and loads ahead of older waves' arithmetic)
-            __builtin_amdgcn_s_setprio(3);
-#endif
 #pragma unroll
             for (int k = 0; k < 16; k++) v[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(P.p[k]) + g);
-#if C2D_SAT_PRIO == 1
-            __builtin_amdgcn_s_setprio(0);
-#elif C2D_SAT_PRIO == 2  // (experiment: a wave whose data has arrived ahead of younger waves, so that it frees its slot sooner)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_setprio(3);
-#endif
             const uint32_t packed = bits_to_bytes4(collide_pairs<4>([&v](int e, auto how, float (&r1)[8], float (&r2)[8]) {
 #pragma unroll
                 for (int k = 0; k < 8; k++) {
@@ -219,11 +200,7 @@ __global__ __launch_bounds__(64) void sat_rect_aos_kernel(const float* __restric
             tile[0][64 * k + lane] = va[k];
             tile[1][64 * k + lane] = vb[k];
         }
-        // same wave wrote and reads: LDS operations of a wave complete in order; the fence pair keeps the
-        // compiler from moving a lane's reads above another lane's writes (it emits no instruction)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();   // the same wave wrote and reads
         f32x4 pa[4], pb[4];  // the lane's two pairs: chunks 4 lane .. 4 lane + 3 of each array
 #pragma unroll
         for (int c = 0; c < 4; c++) {
@@ -251,10 +228,7 @@ __global__ __launch_bounds__(64) void sat_rect_aos_kernel(const float* __restric
             out[i] = (uint8_t)(packed & 1u);
             my_count += packed & 1u;
         }
-        // the next tile's stores must not overtake this tile's loads
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();   // the next tile's stores must not overtake this tile's loads
     }
     if (d_count) wave_count_arrive(my_count, d_count, words);
 }

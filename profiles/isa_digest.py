@@ -9,9 +9,17 @@ by class.  With --scratch every scratch_load / scratch_store is listed with the 
 LLVM's own block annotations in the assembly ("in Loop: Header=BBx_y Depth=N"): depth 0 = straight-line code outside
 every loop, depth 1 = the kernel's outermost loop (for the adaptive Monte-Carlo kernels: the loop over work items).
 Static counts are not dynamic counts: they say what exists in the code, the PMC passes say what runs.
+
+    python profiles/isa_digest.py --sha [-D...] FILE... > digest.txt
+
+With --sha it prints one line per kernel, sorted by name: a SHA-256 of the kernel's instruction stream (comments stripped, the
+function index of .LBB<n>_<m> labels dropped, so that adding or removing a kernel in front of it changes nothing) and its
+resource metadata.  Two such outputs, taken at two commits, are compared with `diff`: an empty diff means every kernel's code
+and resources are the same (a refactor's check).
 """
 from __future__ import annotations
 
+import hashlib
 import os
 import re
 import subprocess
@@ -153,6 +161,33 @@ def digest(src: str, defines: list[str], show_scratch: bool, md_out: bool) -> No
         print()
 
 
+def normalised_body(body: list[str]) -> str:
+    out = []
+    for ln in body:
+        ln = re.sub(r"\.LBB\d+_(\d+)", r".LBB_\1", ln.split(";")[0]).strip()
+        if ln:
+            out.append(" ".join(ln.split()))
+    return "\n".join(out) + "\n"
+
+
+def sha_lines(src: str, defines: list[str]) -> None:
+    text = assemble(src, defines)
+    bodies = kernel_bodies(text)
+    meta = kernel_metadata(text)
+    names = demangle(list(bodies))
+    tag = os.path.basename(src) + "".join(" " + d for d in defines)
+    rows = []
+    for k, body in bodies.items():
+        md = meta.get(k, {})
+        short = re.sub(r"\(.*", "", names[k]).replace("c2d::", "").replace("void ", "")
+        rows.append(f"{tag}: {short}: sha256 {hashlib.sha256(normalised_body(body).encode()).hexdigest()} "
+                    f"vgpr {md.get('vgpr_count', '?')} sgpr {md.get('sgpr_count', '?')} "
+                    f"spills {md.get('vgpr_spill_count', '?')}+{md.get('sgpr_spill_count', '?')} "
+                    f"scratch {md.get('private_segment_fixed_size', '?')} LDS {md.get('group_segment_fixed_size', '?')}")
+    if rows:
+        print("\n".join(sorted(rows)))
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     defs = [a for a in args if a.startswith("-D")]
@@ -160,4 +195,7 @@ if __name__ == "__main__":
     if not files:
         raise SystemExit(__doc__)
     for f in files:
-        digest(f, defs, "--scratch" in args, "--md" in args)
+        if "--sha" in args:
+            sha_lines(f, defs)
+        else:
+            digest(f, defs, "--scratch" in args, "--md" in args)
