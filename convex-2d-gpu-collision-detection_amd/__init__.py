@@ -23,6 +23,7 @@ from .binding import (  # noqa: F401
     ROW_DT,
     POLY_DT,
     POLY_POSE_DT,
+    CONTACT_DT,
     make_polygon,
     library_path,
     load_library,

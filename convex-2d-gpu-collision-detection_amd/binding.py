@@ -27,6 +27,10 @@ ROW_DT = np.dtype([("x", "<f4"), ("y", "<f4"), ("cp", "<f4"), ("var_idx", "<f4")
 POLY_DT = np.dtype([("k", "<u4"), ("x", "<f4", (KMAX,)), ("y", "<f4", (KMAX,))])       # c2d_polygon
 POLY_POSE_DT = np.dtype([("theta", "<f4"), ("obstacle", POLY_DT)])                       # c2d_poly_pose
 
+# contact queries (include/c2d.h, "contact queries: depth and normal for listed pairs")
+CONTACT_DT = np.dtype([("depth", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("axis", "<u2"), ("hit", "u1"), ("flags", "u1")])   # c2d_contact
+CONTACT_NO_AXIS, CONTACT_BAD_PAIR = 1, 2
+
 
 class C2DError(RuntimeError):
     def __init__(self, status: int, what: str, detail: str = ""):
@@ -156,6 +160,10 @@ _SIGNATURES = {
                                            C.c_void_p, C.c_void_p]),
     "c2d_sat_poly_broad_pairs": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                            C.c_void_p]),
+    "c2d_poly_pair_contacts": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                         C.c_void_p, C.c_void_p]),
+    "c2d_rect_pair_contacts": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_bins_create": (C.c_int, [C.c_void_p, C.POINTER(_PolyBin), C.c_size_t, C.POINTER(C.c_void_p)]),
     "c2d_poly_bins_from_padded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "c2d_poly_bins_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -719,6 +727,94 @@ class Engine:
         b = a if same else self.poly_set(*arrays[3:], n_b, vx_b.shape[0])
         return self._pairs_sized_exactly("poly_broad_pairs_host", arrays,
                                          lambda pairs, cap, cnt: self.sat_poly_broad_pairs(a, b, pairs, cap, cnt, upper=upper), check_async=True)
+
+    # -- contact queries (include/c2d.h "contact queries: depth and normal for listed pairs") -----------------
+    def poly_pair_contacts(self, a: _PolySet, b: _PolySet, pairs, n_pairs: int, out, n_pairs_dev=None, row_base: int = 0, col_base: int = 0,
+                           stream: int = 0):
+        """c2d_poly_pair_contacts: out[p] (CONTACT_DT[n_pairs], 16-byte aligned) = the contact of list entry p = (row_base + i,
+        col_base + j) of pairs = u32[n_pairs][2]; with n_pairs_dev (a device u64, the count a list call filled) only the first
+        min(n_pairs, *n_pairs_dev) entries are processed and nothing beyond them is touched; a, b from poly_set()"""
+        if not isinstance(a, _PolySet) or not isinstance(b, _PolySet):
+            raise ValueError("need two poly_set() descriptions")
+        self._check(self.lib.c2d_poly_pair_contacts(self.h, C.byref(a), C.byref(b), _ptr_of(pairs), n_pairs, _ptr_of(n_pairs_dev), row_base, col_base,
+                                                    _ptr_of(out), C.c_void_p(stream)), "c2d_poly_pair_contacts")
+
+    def rect_pair_contacts(self, a_planes: Sequence, n_a: int, b_planes: Sequence, n_b: int, pairs, n_pairs: int, out, n_pairs_dev=None,
+                           row_base: int = 0, col_base: int = 0, stream: int = 0):
+        """c2d_rect_pair_contacts: poly_pair_contacts for two rectangle sets given as 8 vertex planes each"""
+        a, b = self._cross_planes(a_planes, b_planes)
+        self._check(self.lib.c2d_rect_pair_contacts(self.h, a, n_a, b, n_b, _ptr_of(pairs), n_pairs, _ptr_of(n_pairs_dev), row_base, col_base,
+                                                    _ptr_of(out), C.c_void_p(stream)), "c2d_rect_pair_contacts")
+
+    def _contacts_of_list(self, name: str, arrays: Sequence, list_call, contacts_call, check_async: bool = False):
+        """The one shape of the *_contacts_host functions: a count-only list call sizes the buffers, then the list call and the
+        contacts call run back to back on the list's DEVICE count (no read-back between them).  list_call(pairs, capacity, count),
+        contacts_call(pairs, capacity, count, out).  Frees `arrays` and its own on every way out.  -> (pairs, contacts)"""
+        arrays = [x for x in arrays if x is not None]
+        try:
+            d_cnt = self.zeros(1, np.uint64)
+            arrays.append(d_cnt)
+            list_call(None, 0, d_cnt)
+            total = int(d_cnt.get()[0])
+            if check_async:
+                self.check_async()
+            if total == 0:
+                return np.zeros((0, 2), np.uint32), np.zeros(0, CONTACT_DT)
+            d_pairs, d_out = self.empty((total, 2), np.uint32), self.empty(total, CONTACT_DT)
+            arrays += [d_pairs, d_out]
+            self.memset(d_cnt, 0, 8)
+            list_call(d_pairs, total, d_cnt)
+            contacts_call(d_pairs, total, d_cnt, d_out)
+            pairs, contacts = d_pairs.get(), d_out.get()
+            if int(d_cnt.get()[0]) != total:
+                raise C2DError(-2, name, "the list call counted a different total than the count-only call")
+            return pairs, contacts
+        finally:
+            for x in arrays:
+                x.free()
+
+    def poly_contacts_host(self, vx_a, vy_a, k_a, vx_b=None, vy_b=None, k_b=None, upper: bool = False, broad: bool = True):
+        """Host convenience: the sets of poly_broad_pairs_host (vx_b None: the same set) -> (pairs u32 [total][2], contacts
+        CONTACT_DT[total]): the colliding pairs through the broad phase (broad=False: the N x M list) and their contacts, computed
+        on the list's device count."""
+        vx_a, vy_a, k_a = self._host_poly_set(vx_a, vy_a, k_a)
+        same = vx_b is None
+        if same:
+            if vy_b is not None or k_b is not None:
+                raise ValueError("set B needs vx_b and vy_b (or none of vx_b, vy_b, k_b: the same set)")
+        else:
+            if vy_b is None:
+                raise ValueError("set B needs vx_b and vy_b")
+            vx_b, vy_b, k_b = self._host_poly_set(vx_b, vy_b, k_b)
+        n_a = vx_a.shape[1]
+        n_b = n_a if same else vx_b.shape[1]
+        if n_a == 0 or n_b == 0:
+            return np.zeros((0, 2), np.uint32), np.zeros(0, CONTACT_DT)
+        arrays = self._to_device_all([vx_a, vy_a, k_a] + ([] if same else [vx_b, vy_b, k_b]))
+        a = self.poly_set(*arrays[:3], n_a, vx_a.shape[0])
+        b = a if same else self.poly_set(*arrays[3:], n_b, vx_b.shape[0])
+        lister = self.sat_poly_broad_pairs if broad else self.sat_poly_cross_pairs
+        return self._contacts_of_list("poly_contacts_host", arrays, lambda pairs, cap, cnt: lister(a, b, pairs, cap, cnt, upper=upper),
+                                      lambda pairs, cap, cnt, out: self.poly_pair_contacts(a, b, pairs, cap, out, n_pairs_dev=cnt), check_async=True)
+
+    def rect_contacts_host(self, a_planes: np.ndarray, b_planes: Optional[np.ndarray] = None, upper: bool = False, broad: bool = True):
+        """Host convenience: the sets of rect_broad_pairs_host (b_planes None: the same set) -> (pairs u32 [total][2], contacts
+        CONTACT_DT[total]), through the broad phase (broad=False: the N x M list) and the contacts call on the list's device count."""
+        a_planes = np.asarray(a_planes, np.float32)
+        b_planes = None if b_planes is None else np.asarray(b_planes, np.float32)
+        for p in (a_planes, a_planes if b_planes is None else b_planes):
+            if p.ndim != 2 or p.shape[0] != 8:
+                raise ValueError("need float32 planes [8][n]")
+        n_a = a_planes.shape[1]
+        n_b = n_a if b_planes is None else b_planes.shape[1]
+        if n_a == 0 or n_b == 0:
+            return np.zeros((0, 2), np.uint32), np.zeros(0, CONTACT_DT)
+        d_a, d_b = self._to_device_all([a_planes, b_planes])
+        pa = [d_a.row(k) for k in range(8)]
+        pb = pa if d_b is None else [d_b.row(k) for k in range(8)]
+        lister = self.sat_rect_broad_pairs if broad else self.sat_rect_cross_pairs
+        return self._contacts_of_list("rect_contacts_host", [d_a, d_b], lambda pairs, cap, cnt: lister(pa, n_a, pb, n_b, pairs, cap, cnt, upper=upper),
+                                      lambda pairs, cap, cnt, out: self.rect_pair_contacts(pa, n_a, pb, n_b, pairs, cap, out, n_pairs_dev=cnt))
 
     # -- binned polygon batches (include/c2d.h "binned polygon batches") ---------------
     def poly_bins_create(self, bins) -> "PolyBins":

@@ -237,6 +237,8 @@ int c2d_ctx_check_async(c2d_ctx* ctx)
     if (e == 0) return C2D_OK;
     if (e & C2D_ASYNC_ERR_POLY_K)
         ctx->last_error = "c2d_sat_poly_pairs: vertex count outside 1..C2D_POLY_KMAX (reported asynchronously; those pairs were written as 0)";
+    else if (e & C2D_ASYNC_ERR_PAIR_INDEX)
+        ctx->last_error = "c2d_*_pair_contacts: a listed pair has an index outside its set (reported asynchronously; those contacts carry C2D_CONTACT_BAD_PAIR)";
     else
         ctx->last_error = "asynchronous argument error reported by a kernel";
     return C2D_ERR_INVALID_ARG;

@@ -1,0 +1,324 @@
+// c2d_contact.hip — contact queries for gfx950 (MI355X): for each listed pair (A_i, B_j) the minimum-translation contact over the
+// pairwise test's own axes — a signed depth, a unit normal from A to B, the axis it came from — and the boolean of the pairwise
+// test itself (c2d_poly_pair_contacts, c2d_rect_pair_contacts; include/c2d.h).
+//
+// The rule (the contract of include/c2d.h), per axis n in axis order, with [minA, maxA] and [minB, maxB] the projection intervals
+// the pairwise test computes on n:
+//     o1 = maxA - minB,  o2 = maxB - minA,  o = o1 <= o2 ? o1 : o2,  len2 = n.x * n.x + n.y * n.y  (unfused)
+//     unusable: len2 == 0, or d = o / sqrt(len2) is NaN;   otherwise the first axis with the smallest d (strict <) wins:
+//     depth = d, normal = +-n / sqrt(len2) with + when o1 <= o2.
+// One pair per lane; the lanes of a wave hold unrelated pairs, so every loop runs over all vertex slots with compile-time indices
+// (c2d_poly_pair.hpp).  The pair list is row-major: the lanes of a wave mostly share their row, so A is loaded through one
+// wave-uniform index when they all do; B is a gather.  Each contact leaves as one 16-byte store.
+//
+// One square root and one division per PAIR instead of one per axis (DESIGN.md §5.11 has the proof).  A first pass estimates every
+// axis's d as q = o * v_rsq_f32(len2) and keeps the smallest and the second smallest estimate.  With len2 in [2^-100, 2^100] and
+// |o| < 2^60, q and the contract's d each lie within 2^-22 |t| + 2^-149 of the real quotient t, hence d in
+// [q - 2^-20 |q| - 2^-147, q + 2^-20 |q| + 2^-147].  When the lower end of the runner-up's range is above the upper end of the
+// best one's (evaluated with margins of 2^-19 |q| + 1e-36, which also cover their own rounding), every other axis's d is strictly
+// larger than the best axis's, so the sequential rule picks that axis whatever the rounded values are, and its d and normal are
+// computed once with the correctly rounded sqrt and divisions.  A pair with an axis outside those ranges, a NaN anywhere, or two
+// estimates too close to call (ties: parallel edges, touching or equal shapes) runs the sequential rule itself in a second pass.
+#include "c2d_cross.hpp"
+#include "c2d_math.hpp"
+#include "c2d_poly_pair.hpp"
+
+namespace c2d {
+
+static_assert(sizeof(c2d_contact) == 16 && offsetof(c2d_contact, axis) == 12 && offsetof(c2d_contact, hit) == 14 && offsetof(c2d_contact, flags) == 15,
+              "the kernel stores a contact as four dwords");
+
+constexpr int kContactBlock = 256;
+constexpr int kContactMaxGrid = 1 << 16;   // blocks per launch; the kernel grid-strides beyond it
+constexpr uint32_t kContactNoAxis = 0xFFFFu;
+
+// what a pick leaves behind: the contact without its `hit`
+struct ContactValue {
+    float depth, nx, ny;
+    uint32_t axis, flags;
+};
+
+// The sequential rule itself: every axis pays the correctly rounded sqrt and division.
+struct ExactPick {
+    float d = __builtin_inff(), nx = 0.0f, ny = 0.0f, len = 1.0f;
+    uint32_t axis = kContactNoAxis;
+    bool pos = true;
+    C2D_DEV void add(uint32_t axis_, float nx_, float ny_, float o1, float o2)
+    {
+        const bool p = o1 <= o2;
+        const float o = p ? o1 : o2;
+        const float len2 = nx_ * nx_ + ny_ * ny_;
+        const float l = __builtin_sqrtf(len2);
+        const float dd = o / l;
+        if (len2 != 0.0f && !__builtin_isnan(dd) && (axis == kContactNoAxis || dd < d)) {
+            d = dd; nx = nx_; ny = ny_; len = l; axis = axis_; pos = p;
+        }
+    }
+    C2D_DEV ContactValue value() const
+    {
+        if (axis == kContactNoAxis) return ContactValue{__builtin_inff(), 0.0f, 0.0f, kContactNoAxis, (uint32_t)C2D_CONTACT_NO_AXIS};
+        const float ux = nx / len, uy = ny / len;
+        return ContactValue{d, pos ? ux : -ux, pos ? uy : -uy, axis, 0u};
+    }
+};
+
+// The first pass: estimates only.  decided() says whether the estimates already name the axis the sequential rule picks.
+struct FastPick {
+    float q1 = __builtin_inff(), q2 = __builtin_inff();   // the smallest estimate and the smallest of all others
+    float o = 0.0f, nx = 0.0f, ny = 0.0f, len2 = 1.0f;    // the axis of q1
+    uint32_t axis = kContactNoAxis;
+    bool pos = true, hard = false;
+    C2D_DEV void add(uint32_t axis_, float nx_, float ny_, float o1, float o2)
+    {
+        const bool p = o1 <= o2;
+        const float o_ = p ? o1 : o2;
+        const float l2 = nx_ * nx_ + ny_ * ny_;
+        const bool live = l2 != 0.0f;   // (a NaN is live, and hard)
+        hard |= live && !(l2 >= 0x1p-100f && l2 <= 0x1p100f && __builtin_fabsf(o_) < 0x1p60f);
+        const float q = live ? o_ * __builtin_amdgcn_rsqf(l2) : __builtin_inff();
+        if (q < q1) {
+            q2 = q1;
+            q1 = q; o = o_; nx = nx_; ny = ny_; len2 = l2; axis = axis_; pos = p;
+        } else {
+            q2 = __builtin_fminf(q2, q);
+        }
+    }
+    C2D_DEV bool decided() const
+    {
+        if (hard) return false;
+        if (axis == kContactNoAxis || q2 == __builtin_inff()) return true;   // no live axis at all, or exactly one
+        const float lo2 = q2 - __builtin_fabsf(q2) * 0x1p-19f - 1e-36f, hi1 = q1 + __builtin_fabsf(q1) * 0x1p-19f + 1e-36f;
+        return lo2 > hi1;
+    }
+    C2D_DEV ContactValue value() const   // (decided() holds)
+    {
+        if (axis == kContactNoAxis) return ContactValue{__builtin_inff(), 0.0f, 0.0f, kContactNoAxis, (uint32_t)C2D_CONTACT_NO_AXIS};
+        const float l = __builtin_sqrtf(len2);
+        const float ux = nx / l, uy = ny / l;
+        return ContactValue{o / l, pos ? ux : -ux, pos ? uy : -uy, axis, 0u};
+    }
+};
+
+// ---- the shapes: every axis of the pairwise test, with its two intervals, to a pick; returns the pairwise boolean ------------
+
+// poly_collide (c2d_poly_pair.hpp) with the intervals kept: axes 0 .. ka - 1 are A's edges, ka .. ka + kb - 1 are B's.
+template <class Pick>
+C2D_DEV bool poly_contact_axes(const PolyObj& A, const PolyObj& B, Pick& pick)
+{
+    const float inf = __builtin_inff();
+    PolyObj P = A, Q = B;
+    bool sep = false;
+#pragma unroll 1
+    for (int side = 0; side < 2; side++) {
+        const uint32_t base = side ? (uint32_t)A.k : 0u;
+#pragma unroll
+        for (int a = 0; a < C2D_POLY_KMAX; a++) {
+            if (a < P.k) {   // axes >= P.k are zero vectors: they never separate and are never usable
+                const int a1 = (a + 1) & (C2D_POLY_KMAX - 1);
+                const float nx = -(P.y[a1] - P.y[a]), ny = P.x[a1] - P.x[a];
+                float mnp = inf, mxp = -inf, mnq = inf, mxq = -inf;
+#pragma unroll
+                for (int r = 0; r < C2D_POLY_KMAX; r++) {
+                    poly_minmax(nx, ny, P.x[r], P.y[r], mnp, mxp);
+                    poly_minmax(nx, ny, Q.x[r], Q.y[r], mnq, mxq);
+                }
+                sep |= ((mxp < mnq) || (mxq < mnp)) && first_projections_ordered(nx * P.x[0] + ny * P.y[0], nx * Q.x[0] + ny * Q.y[0]);
+                const float u = mxp - mnq, v = mxq - mnp;   // side 0: P is A, so u = maxA - minB; side 1: P is B, so v is
+                pick.add(base + (uint32_t)a, nx, ny, side ? v : u, side ? u : v);
+            }
+        }
+        const PolyObj t = P;
+        P = Q;
+        Q = t;
+    }
+    return !sep;
+}
+
+// rect_collide (c2d_math.hpp) with the intervals kept: axes 0 .. 3 are the edge vectors of rectangle 1, 4 .. 7 those of rectangle 2.
+template <class Pick>
+C2D_DEV bool rect_contact_axes(const float (&r1)[8], const float (&r2)[8], Pick& pick)
+{
+    bool sep = false;
+#pragma unroll
+    for (int which = 0; which < 2; which++) {
+        const float (&r)[8] = which == 0 ? r1 : r2;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const float ax = r[(2 * i + 2) & 7] - r[2 * i], ay = r[(2 * i + 3) & 7] - r[2 * i + 1];
+            const float p10 = dot2(ax, r1[0], ay, r1[1]), p11 = dot2(ax, r1[2], ay, r1[3]);
+            const float p12 = dot2(ax, r1[4], ay, r1[5]), p13 = dot2(ax, r1[6], ay, r1[7]);
+            const float p20 = dot2(ax, r2[0], ay, r2[1]), p21 = dot2(ax, r2[2], ay, r2[3]);
+            const float p22 = dot2(ax, r2[4], ay, r2[5]), p23 = dot2(ax, r2[6], ay, r2[7]);
+            const float min1 = min4(p10, p11, p12, p13), max1 = max4(p10, p11, p12, p13);
+            const float min2 = min4(p20, p21, p22, p23), max2 = max4(p20, p21, p22, p23);
+            sep |= ((max1 < min2) || (max2 < min1)) && first_projections_ordered(p10, p20);
+            pick.add((uint32_t)(4 * which + i), ax, ay, max1 - min2, max2 - min1);
+        }
+    }
+    return !sep;
+}
+
+// The shape policies of the contact kernel:
+//   S::Set                 the device-side description of one set (a kernel argument);  S::size(set): its objects
+//   S::present(set, i)     false: object i is in no pair (a polygon with a vertex count outside 1..rows)
+//   S::load(set, i, obj)   object i in registers
+//   S::axes(a, b, pick)    the axes of the pairwise test of (a, b) to `pick`; returns the pairwise boolean
+struct PolyContactShape {
+    using Set = PolySetDev;
+    using Obj = PolyObj;
+    static constexpr uint32_t kAbsentErr = C2D_ASYNC_ERR_POLY_K;
+    static __host__ __device__ size_t size(const Set& X) { return X.n; }
+    static C2D_DEV bool present(const Set& X, size_t i)
+    {
+        int k;
+        return poly_count(X, i, k);
+    }
+    static C2D_DEV void load(const Set& X, size_t i, Obj& o) { poly_load(X, i, o); }
+    template <class Pick>
+    static C2D_DEV bool axes(const Obj& a, const Obj& b, Pick& pick) { return poly_contact_axes(a, b, pick); }
+};
+
+struct RectContactSet {
+    const float* p[8];
+    size_t n;
+};
+
+struct RectContactShape {
+    using Set = RectContactSet;
+    struct Obj { float r[8]; };
+    static constexpr uint32_t kAbsentErr = 0u;
+    static __host__ __device__ size_t size(const Set& X) { return X.n; }
+    static C2D_DEV bool present(const Set&, size_t) { return true; }
+    static C2D_DEV void load(const Set& X, size_t i, Obj& o)
+    {
+#pragma unroll
+        for (int k = 0; k < 8; k++) o.r[k] = X.p[k][i];
+    }
+    template <class Pick>
+    static C2D_DEV bool axes(const Obj& a, const Obj& b, Pick& pick) { return rect_contact_axes(a.r, b.r, pick); }
+};
+
+// One pair per lane.  Entry p of the list is processed when p < min(n_pairs, *d_n); nothing else of `out` is touched.  A pair with
+// an index outside its set, or with an absent object, reads no vertex and gets the BAD_PAIR contact.
+template <class S>
+__global__ __launch_bounds__(kContactBlock) void contact_kernel(typename S::Set A, typename S::Set B, const uint32_t* __restrict__ pairs, size_t n_pairs,
+                                                                const unsigned long long* __restrict__ d_n, size_t row_base, size_t col_base,
+                                                                c2d_contact* __restrict__ out, uint32_t* __restrict__ async_err)
+{
+    size_t bound = n_pairs;
+    if (d_n) {
+        const unsigned long long listed = *d_n;
+        if (listed < (unsigned long long)bound) bound = (size_t)listed;
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const size_t n_a = S::size(A), n_b = S::size(B);
+    const size_t step = (size_t)gridDim.x * kContactBlock;
+    // every lane of a wave makes the same trips (the loop variable is the wave's first entry): the ballots below see whole waves
+    for (size_t p0 = (size_t)blockIdx.x * kContactBlock + (threadIdx.x & ~63u); p0 < bound; p0 += step) {
+        const size_t p = p0 + lane;
+        const bool in = p < bound;
+        uint32_t gi = 0, gj = 0;
+        if (in) {
+            gi = pairs[2 * p];
+            gj = pairs[2 * p + 1];
+        }
+        // local indices; one below its base wraps to far above any n (n and the bases stay below 2^62)
+        const size_t i = (size_t)gi - row_base, j = (size_t)gj - col_base;
+        const bool ranged = in && i < n_a && j < n_b;
+        bool valid = false;
+        if (ranged) valid = S::present(A, i) && S::present(B, j);   // (the count planes are read inside the sets only)
+        const unsigned long long bad_index = __ballot(in && !ranged), absent = __ballot(ranged && !valid);
+        if (lane == 0) {
+            const uint32_t e = (bad_index ? C2D_ASYNC_ERR_PAIR_INDEX : 0u) | (absent ? S::kAbsentErr : 0u);
+            if (e) __hip_atomic_fetch_or(async_err, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        uint4 word = make_uint4(0u, 0u, 0u, kContactNoAxis | ((uint32_t)C2D_CONTACT_BAD_PAIR << 24));   // depth 0, normal (0, 0), hit 0
+        const unsigned long long vm = __ballot(valid);
+        if (vm != 0ull) {   // (wave-uniform)
+            // Lanes without a valid pair compute the first valid lane's pair and drop the result: every index used below is inside
+            // its set, and no branch of the pair routine depends on who is valid.  i, j < 2^32 for a valid pair (gi, gj are u32).
+            const int first = (int)__builtin_ctzll(vm);
+            const uint32_t i0 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)i, first);
+            const uint32_t j0 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)j, first);
+            const uint32_t ia = valid ? (uint32_t)i : i0, jb = valid ? (uint32_t)j : j0;
+            typename S::Obj a, b;
+            if (__ballot(ia != i0) == 0ull)
+                S::load(A, (size_t)i0, a);   // the whole wave is in one row: one wave-uniform index
+            else
+                S::load(A, (size_t)ia, a);
+            S::load(B, (size_t)jb, b);
+            FastPick fast;
+            const bool hit = S::axes(a, b, fast);
+            ContactValue c;
+            if (fast.decided()) {
+                c = fast.value();
+            } else {
+                ExactPick exact;
+                (void)S::axes(a, b, exact);
+                c = exact.value();
+            }
+            if (valid)
+                word = make_uint4(__float_as_uint(c.depth), __float_as_uint(c.nx), __float_as_uint(c.ny), c.axis | (hit ? 1u << 16 : 0u) | (c.flags << 24));
+        }
+        if (in) reinterpret_cast<uint4*>(out)[p] = word;   // d_out is 16-byte aligned (checked on the host)
+    }
+}
+
+// the arguments both entry points share, then the launch
+template <class S>
+int contact_run(c2d_ctx* ctx, const char* what, const typename S::Set& A, const typename S::Set& B, const uint32_t* d_pairs, size_t n_pairs,
+                const unsigned long long* d_n_pairs, size_t row_base, size_t col_base, c2d_contact* d_out, c2d_stream stream)
+{
+    if (int rc = cross_check_flags_bases(ctx, what, S::size(A), S::size(B), row_base, col_base, 0)) return rc;
+    if (!d_pairs) return cross_fail(ctx, what, "NULL pair list");
+    if (!d_out) return cross_fail(ctx, what, "NULL output");
+    if (reinterpret_cast<uintptr_t>(d_pairs) & 3u) return cross_fail(ctx, what, "the pair list must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return cross_fail(ctx, what, "the output must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_n_pairs) & 7u) return cross_fail(ctx, what, "d_n_pairs must be 8-byte aligned");
+    if (n_pairs > kBaseLimit) return cross_fail(ctx, what, "n_pairs must stay below 2^62");
+    DeviceGuard dg(ctx->device);
+    hipLaunchKernelGGL(contact_kernel<S>, dim3(grid_for(n_pairs, kContactBlock, kContactMaxGrid)), dim3(kContactBlock), 0, (hipStream_t)stream, A, B, d_pairs,
+                       n_pairs, d_n_pairs, row_base, col_base, d_out, ctx->d_async_err);
+    C2D_LAUNCH_CHECK(ctx);
+    return C2D_OK;
+}
+
+}  // namespace c2d
+
+using namespace c2d;
+
+extern "C" {
+
+int c2d_poly_pair_contacts(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b, const uint32_t* d_pairs, size_t n_pairs,
+                           const unsigned long long* d_n_pairs, size_t row_base, size_t col_base, c2d_contact* d_out, c2d_stream stream)
+{
+    const char* what = "c2d_poly_pair_contacts";
+    if (!ctx) return C2D_ERR_INVALID_ARG;
+    if (!a || !b) return cross_fail(ctx, what, "NULL set");
+    if (n_pairs == 0) return C2D_OK;
+    PolySetDev A, B;
+    if (int rc = poly_set_check(ctx, what, "a", a, A)) return rc;
+    if (int rc = poly_set_check(ctx, what, "b", b, B)) return rc;
+    return contact_run<PolyContactShape>(ctx, what, A, B, d_pairs, n_pairs, d_n_pairs, row_base, col_base, d_out, stream);
+}
+
+int c2d_rect_pair_contacts(c2d_ctx* ctx, const float* const d_a[8], size_t n_a, const float* const d_b[8], size_t n_b, const uint32_t* d_pairs,
+                           size_t n_pairs, const unsigned long long* d_n_pairs, size_t row_base, size_t col_base, c2d_contact* d_out, c2d_stream stream)
+{
+    const char* what = "c2d_rect_pair_contacts";
+    if (!ctx) return C2D_ERR_INVALID_ARG;
+    if (!d_a || !d_b) return cross_fail(ctx, what, "NULL argument");
+    if (n_pairs == 0) return C2D_OK;
+    RectContactSet A, B;
+    A.n = n_a;
+    B.n = n_b;
+    for (int k = 0; k < 8; k++) {
+        if (!d_a[k] || !d_b[k]) return cross_fail(ctx, what, "NULL plane");
+        if ((reinterpret_cast<uintptr_t>(d_a[k]) | reinterpret_cast<uintptr_t>(d_b[k])) & 3u) return cross_fail(ctx, what, "planes must be 4-byte aligned");
+        A.p[k] = d_a[k];
+        B.p[k] = d_b[k];
+    }
+    return contact_run<RectContactShape>(ctx, what, A, B, d_pairs, n_pairs, d_n_pairs, row_base, col_base, d_out, stream);
+}
+
+}  // extern "C"

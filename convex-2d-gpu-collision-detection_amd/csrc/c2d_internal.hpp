@@ -53,6 +53,7 @@ struct c2d_ctx {
 };
 
 #define C2D_ASYNC_ERR_POLY_K 1u   /* polygon vertex count outside 1..C2D_POLY_KMAX */
+#define C2D_ASYNC_ERR_PAIR_INDEX 2u   /* a listed pair with an index outside its set (c2d_*_pair_contacts) */
 
 
 namespace c2d {

@@ -294,6 +294,10 @@ C2D_DEV bool rect_collide(const float (&r1)[8], const float (&r2)[8])
 // certificate (or not a number: the comparisons are written so that a NaN anywhere reads "thin") — the caller then evaluates
 // the pair in full (rect_collide).  The thresholds carry 2^-8 relative and 1e-36 absolute slack for their own rounding and
 // for underflow.  The Monte-Carlo kernels use the same certificates with scene-level constants (c2d_mc.hip).
+// The bound is a rounding bound and holds while no product or difference overflows: with a coordinate of 3e38 or inf an infinite
+// overlap passes an infinite `need` and the pair was certified "collide" while an axis of edge 2 or 3 separates it.  So the
+// certificate is kept to its domain, as rect_side (c2d_cross.hip) keeps it: with every |coordinate| below 2^61, |axis| <= 2^62,
+// |projection| <= 2^124 and every overlap stays below 2^126; a pair beyond that (or all NaN) reads thin.  One compare per pair.
 C2D_DEV bool rect_collide_certified(const float (&r1)[8], const float (&r2)[8], bool& thin)
 {
     float cmax = __builtin_fabsf(r1[0]);
@@ -302,7 +306,7 @@ C2D_DEV bool rect_collide_certified(const float (&r1)[8], const float (&r2)[8], 
 #pragma unroll
     for (int k = 0; k < 8; k++) cmax = __builtin_fmaxf(cmax, __builtin_fabsf(r2[k]));
     const float c2 = (2.0f + 0x1p-7f) * cmax, c3 = (8.0f + 0x1p-5f) * 0x1p-24f * cmax;
-    bool sep = false, uneasy = false;
+    bool sep = false, uneasy = !(cmax < 0x1p61f);
 #pragma unroll
     for (int which = 0; which < 2; which++) {
         const float (&r)[8] = which == 0 ? r1 : r2;

@@ -1,0 +1,148 @@
+#!/usr/bin/env python3
+"""Developer tool: the contact queries (c2d_poly_pair_contacts / c2d_rect_pair_contacts) next to the list calls that feed them, one
+JSON line per configuration.  GPU only, no oracle (tests/test_gpu_contacts.py checks the values).
+
+Scenes: the sparse self-collision scenes of poly_broad_bench.py (K ~ U{3..16}, extent 200 * sqrt(N / 32768)) and broad_bench.py
+(rectangles of random_obb_pose_planes at the same density), C2D_CROSS_UPPER with B = A; and one dense polygon list of about 1e7
+pairs (every pair of two sets of --dense-n polygons, enumerated on the device).  Per configuration, HIP events on one stream,
+median of --reps (>= 7) after a warm-up:
+  list_ms         the broad-phase list call alone (exact capacity)
+  contacts_ms     the contacts call alone on that list, bounded by the list's device count
+  both_ms         the two back to back on the stream, no host synchronisation between them
+  contacts_per_s  listed pairs / contacts_ms;   hits: the list's length
+The kernels' own times come from a separate run under `rocprofv3 --kernel-trace --stats -- python3 contact_bench.py --once`.
+usage: contact_bench.py [--n 131072] [--dense-n 3163] [--reps 7] [--once]"""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+import torch  # before libc2d.so
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, ROOT)
+from __graft_entry__ import load_package  # noqa: E402
+
+pkg = load_package()
+wl = importlib.import_module("c2d_amd.workloads")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=131072)
+    ap.add_argument("--dense-n", type=int, default=3163)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--once", action="store_true")
+    args = ap.parse_args()
+    reps = max(7, args.reps)
+    dev = torch.device("cuda", 0)
+    eng = pkg.Engine(0)
+    stream = torch.cuda.Stream(device=dev)
+    sh = stream.cuda_stream
+    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def timed(fn):
+        fn()
+        stream.synchronize()
+        ms = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            stream.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return float(np.median(ms))
+
+    def report(config, n, list_call, contacts_call, total, extra=None):
+        def both():
+            if list_call is not None:
+                list_call()
+            contacts_call()
+
+        if args.once:
+            both()
+            stream.synchronize()
+            return
+        out = {"config": config, "n": n, "hits": total, "reps": reps}
+        if list_call is not None:
+            out["list_ms"] = round(timed(list_call), 4)
+        out["contacts_ms"] = round(timed(contacts_call), 4)
+        if list_call is not None:
+            out["both_ms"] = round(timed(both), 4)
+        out["contacts_per_s"] = round(total / (out["contacts_ms"] * 1e-3), 0)
+        out.update(extra or {})
+        print(json.dumps(out), flush=True)
+
+    n = args.n
+    extent = 200.0 * np.sqrt(n / 32768)
+    # -- sparse polygons, self-collision ---------------------------------------------------------------------------------
+    host = wl.random_convex_polygon_set(n, seed=0xC505, extent=extent)
+    t = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in host]
+    s = eng.poly_set(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), n, wl.KMAX)
+    cnt.zero_()
+    eng.sat_poly_broad_pairs(s, s, None, 0, cnt.data_ptr(), upper=True, stream=sh)
+    stream.synchronize()
+    total = int(cnt.item())
+    pairs = torch.empty((max(total, 1), 2), dtype=torch.int32, device=dev)
+    out = torch.empty((max(total, 1), 16), dtype=torch.uint8, device=dev)
+
+    def poly_list():
+        cnt.zero_()
+        eng.sat_poly_broad_pairs(s, s, pairs.data_ptr(), total, cnt.data_ptr(), upper=True, stream=sh)
+
+    def poly_contacts():
+        eng.poly_pair_contacts(s, s, pairs.data_ptr(), total, out.data_ptr(), n_pairs_dev=cnt.data_ptr(), stream=sh)
+
+    poly_list()
+    report("sparse_polygons_self_upper", n, poly_list, poly_contacts, total, {"extent": round(float(extent), 2)})
+    hit_share = float((out.view(torch.int32)[:total, 3] >> 16 & 1).float().mean().item()) if total and not args.once else None
+    assert hit_share in (None, 1.0), "a listed pair without `hit`"
+    del pairs, out
+
+    # -- sparse rectangles, self-collision -------------------------------------------------------------------------------
+    poses = wl.random_obb_pose_planes(n, seed=0xB0AD, extent=extent)
+    d_pose = torch.from_numpy(np.ascontiguousarray(poses[:5])).to(dev)
+    planes = torch.empty((8, n), dtype=torch.float32, device=dev)
+    eng.rects_from_poses(*[d_pose[k].data_ptr() for k in range(5)], n, [planes[k].data_ptr() for k in range(8)], stream=sh)
+    pp = [planes[k].data_ptr() for k in range(8)]
+    cnt.zero_()
+    eng.sat_rect_broad_pairs(pp, n, pp, n, None, 0, cnt.data_ptr(), upper=True, stream=sh)
+    stream.synchronize()
+    rtotal = int(cnt.item())
+    rpairs = torch.empty((max(rtotal, 1), 2), dtype=torch.int32, device=dev)
+    rout = torch.empty((max(rtotal, 1), 16), dtype=torch.uint8, device=dev)
+
+    def rect_list():
+        cnt.zero_()
+        eng.sat_rect_broad_pairs(pp, n, pp, n, rpairs.data_ptr(), rtotal, cnt.data_ptr(), upper=True, stream=sh)
+
+    def rect_contacts():
+        eng.rect_pair_contacts(pp, n, pp, n, rpairs.data_ptr(), rtotal, rout.data_ptr(), n_pairs_dev=cnt.data_ptr(), stream=sh)
+
+    rect_list()
+    report("sparse_rectangles_self_upper", n, rect_list, rect_contacts, rtotal, {"extent": round(float(extent), 2)})
+    del rpairs, rout
+
+    # -- one dense polygon list: every pair of two sets ------------------------------------------------------------------
+    m = args.dense_n
+    da = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in wl.random_convex_polygon_set(m, seed=0xC507, extent=8.0)]
+    db = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in wl.random_convex_polygon_set(m, seed=0xC508, extent=8.0)]
+    sa = eng.poly_set(da[0].data_ptr(), da[1].data_ptr(), da[2].data_ptr(), m, wl.KMAX)
+    sb = eng.poly_set(db[0].data_ptr(), db[1].data_ptr(), db[2].data_ptr(), m, wl.KMAX)
+    idx = torch.arange(m, dtype=torch.int32, device=dev)
+    dense = torch.stack([idx.repeat_interleave(m), idx.repeat(m)], dim=1).contiguous()
+    dout = torch.empty((m * m, 16), dtype=torch.uint8, device=dev)
+
+    def dense_contacts():
+        eng.poly_pair_contacts(sa, sb, dense.data_ptr(), m * m, dout.data_ptr(), stream=sh)
+
+    report("dense_polygon_list", m, None, dense_contacts, m * m)
+    eng.check_async()
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -395,6 +395,67 @@ int c2d_sat_poly_broad_pairs(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly
                              uint32_t* d_pairs, size_t capacity,        /* u32[capacity][2] */
                              unsigned long long* d_count, c2d_stream stream);
 
+/* ---- contact queries: depth and normal for listed pairs -------------------------
+ * Additions to 0.6 (c2d_version() stays 6), found by symbol lookup like the ones above.
+ *
+ * c2d_poly_pair_contacts / c2d_rect_pair_contacts: for each pair of a list — the list a cross or broad call emitted, or any
+ * other — the minimum-translation contact over the pairwise test's OWN axes: a signed depth, a unit normal from A towards B,
+ * the axis the contact came from, and the boolean of the pairwise test for that pair.  The list and its length stay on the
+ * device, so broad phase -> pair list -> contacts runs on one stream with no host synchronisation.
+ *
+ * Arithmetic contract.  Everything is IEEE binary32, round to nearest, subnormals kept, nothing contracted;
+ * division and square root are correctly rounded.
+ *   axes     polygons: axis e is the true normal (-(y[e+1] - y[e]), x[e+1] - x[e]) of edge e, A's ka edges first (0..ka-1), then
+ *            B's kb (ka..ka+kb-1), the vertex index wrapping at k; projections are nx * x + ny * y, unfused, as in
+ *            c2d_sat_poly_pairs.  Rectangles: the eight edge-vector axes of convex_collide (utils.cu:170-171; 0..3 rectangle A,
+ *            4..7 rectangle B), projected exactly as c2d_sat_rect_pairs_verts of the same build projects them.
+ *   per axis with [minA, maxA], [minB, maxB] the two projection intervals (running fmin / fmax from +inf / -inf):
+ *            o1 = maxA - minB,  o2 = maxB - minA,  o = o1 <= o2 ? o1 : o2,  len2 = nx * nx + ny * ny (unfused).
+ *            The axis is unusable when len2 == 0 or when o / sqrt(len2) is NaN; otherwise d = o / sqrt(len2).
+ *   result   the axis with the smallest d wins under strict <, taken in axis order (the first of equal axes wins; the first usable
+ *            axis wins over nothing, whatever its d): depth = d, (nx, ny) = (+-nx / len, +-ny / len) with len = sqrt(len2) and
+ *            + when o1 <= o2 — B then lies on the axis's positive side, and moving B by depth along the normal separates the
+ *            pair.  With no usable axis: depth = +inf, normal (0, 0), axis = 0xFFFF, flags = C2D_CONTACT_NO_AXIS.
+ *   hit      is not derived from depth: it is the pairwise boolean itself (c2d_sat_poly_pairs_rows / c2d_sat_rect_pairs_verts on
+ *            the pair), for every input bit pattern, the non-finite rule above included.  For finite inputs with no overflow,
+ *            hit == (depth >= 0) on every pair that has a usable axis.
+ * The implementation evaluates axes in another order and in parallel; its results equal this sequential rule.  +0 and -0 compare
+ * equal in depth, nx and ny.  A depth < 0 says "separated", and -depth is a lower bound of the distance.
+ *
+ *   a, b / d_a, n_a, d_b, n_b : the two sets, as for the cross forms (polygon sets may differ in `rows`; a and b may be the same
+ *                memory).
+ *   d_pairs    : u32[n_pairs][2], exactly what the cross and broad lists emit: entry p is (row_base + i, col_base + j).
+ *   d_n_pairs  : optional device uint64 — the d_count a list call filled.  When given, only the first min(n_pairs, *d_n_pairs)
+ *                entries are processed (the count is read on the device), so a caller passes n_pairs = the list's capacity and
+ *                the count straight from the list call.  d_out[p] for p at or beyond that bound is not touched.
+ *   row_base, col_base : the global indices of A_0 and B_0, as for the cross forms.
+ *   d_out      : c2d_contact[n_pairs], 16-byte aligned; entry p is the contact of list entry p.
+ * A pair whose index falls outside [base, base + n) reads no vertex memory and gets hit = 0, flags = C2D_CONTACT_BAD_PAIR,
+ * depth = 0, normal (0, 0), axis = 0xFFFF; so does a pair with a polygon whose vertex count is outside 1..rows ("in no pair").
+ * Either is reported by the next c2d_stream_synchronize / c2d_ctx_check_async, as a bad vertex count is elsewhere.  n_pairs == 0
+ * is a no-op.  NULL arguments, `rows` out of range, a misaligned d_out and the like are refused (C2D_ERR_INVALID_ARG) before a
+ * device is touched.  The calls use no ctx scratch; they are asynchronous on `stream` and graph-capturable. */
+#define C2D_CONTACT_NO_AXIS 1   /* no usable axis: depth = +inf, normal (0, 0), axis = 0xFFFF */
+#define C2D_CONTACT_BAD_PAIR 2  /* an index outside its set, or a polygon with a bad vertex count: nothing was computed */
+
+typedef struct c2d_contact {      /* 16 bytes, 16-byte aligned output */
+    float    depth;               /* min over usable axes of overlap / |axis|; < 0: separated, -depth is a lower bound of the distance */
+    float    nx, ny;              /* unit axis, oriented from A towards B; (0, 0) when no axis is usable */
+    uint16_t axis;                /* 0..ka-1: edge of A, ka..ka+kb-1: edge of B (rectangles: 0..3, 4..7); 0xFFFF: none */
+    uint8_t  hit;                 /* the boolean of the pairwise test for this pair, for every input bit pattern */
+    uint8_t  flags;               /* C2D_CONTACT_NO_AXIS, C2D_CONTACT_BAD_PAIR */
+} c2d_contact;
+
+int c2d_poly_pair_contacts(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b,
+                           const uint32_t* d_pairs, size_t n_pairs, const unsigned long long* d_n_pairs,
+                           size_t row_base, size_t col_base,
+                           c2d_contact* d_out, c2d_stream stream);
+
+int c2d_rect_pair_contacts(c2d_ctx* ctx, const float* const d_a[8], size_t n_a, const float* const d_b[8], size_t n_b,
+                           const uint32_t* d_pairs, size_t n_pairs, const unsigned long long* d_n_pairs,
+                           size_t row_base, size_t col_base,
+                           c2d_contact* d_out, c2d_stream stream);
+
 /* ---- binned polygon batches ---------------------------------------------------
  * The padded layout above moves 16 vertex rows per polygon whatever the polygons are: with
  * K ~ U{3..16} that is 259 bytes per pair for 155 bytes of real vertices, and no kernel can
