@@ -2,7 +2,10 @@
 """Differential fuzz of c2d_poly_pair_contacts / c2d_rect_pair_contacts against the CPU restatement of their contract
 (tests/contact_ref.py, pinned by tests/test_contact_ref_cpu.py): random set sizes, row layouts, vertex-count ranges, densities,
 strides and pointer offsets, bases, list lengths and device counts, clockwise polygons, points and segments, outliers, NaN / inf
-in real slots, junk in the padded slots, tied shapes.  Prints its seed; a mismatch names its configuration.
+in real slots, junk in the padded slots, tied shapes; and, one configuration in five, a few hundred near-tied pairs (polygons or
+quads whose two best axes are not parallel and 2^-28 .. 2^-10 apart, tests/contact_cases.py) at a power-of-two scale of 2^-52 .. 2^52,
+where the kernel's first pass has to tell a decided axis from one too close to call.  Prints its seed; a mismatch names its
+configuration.
 usage: contact_fuzz.py [configs] [seed]     (no seed: the commit's, tests/tools/fuzz_seed.py)"""
 import importlib
 import importlib.util
@@ -16,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 from __graft_entry__ import load_package  # noqa: E402
+import contact_cases as cases  # noqa: E402
 import contact_ref as ref  # noqa: E402
 
 pkg = load_package()
@@ -46,11 +50,28 @@ def one(eng, rng, idx, announce=None):
     """One configuration; `announce(text)` is called with its description BEFORE any GPU work.  Returns (ok, (description, pairs))."""
     n_a, n_b = (int(rng.choice([1, 2, 63, 64, 65, 257, int(rng.integers(1, 600))])) for _ in range(2))
     length = int(rng.choice([1, 63, 64, 65, 257, int(rng.integers(1, 5000))]))
+    near_tie = bool(rng.random() < 0.2)
+    if near_tie:
+        n_a = n_b = length = int(rng.integers(200, 600))
     rb, cb = (int(rng.choice([0, 0, 7, 1 << 20, (1 << 32) - 700])) for _ in range(2))
     cap = length + int(rng.choice([0, 0, 1, 100]))
     n_dev = rng.choice([None, length, max(length - 1, 0), length // 2, cap + 5])
-    rects = bool(rng.random() < 0.3)
-    if rects:
+    rects = bool(rng.random() < (0.5 if near_tie else 0.3))
+    if near_tie:
+        lo = float(rng.uniform(-28.0, -20.0))
+        g_log2, k, seed = (lo, lo + float(rng.uniform(2.0, 10.0))), int(rng.integers(-52, 53)), int(rng.integers(1 << 30))
+        desc = (f"config {idx}: near-ties, {'quads' if rects else 'polygons'} {n_a} x {n_b} (generator seed {seed}, |g| in 2^{g_log2[0]:.1f} .. 2^{g_log2[1]:.1f}, "
+                f"scale 2^{k}), list {length} in {cap}, count {n_dev}, bases {rb}, {cb}")
+        if rects:
+            a, b = (np.ldexp(x, k).astype(np.float32) for x in cases.near_tie_quad_sets(n_a, seed, g_log2))
+            keep = [eng.to_device(a), eng.to_device(b)]
+            pa, pb = [keep[0].row(q) for q in range(8)], [keep[1].row(q) for q in range(8)]
+        else:
+            a, b = (cases.scaled_poly_set(x, k) for x in cases.near_tie_poly_sets(n_a, seed, g_log2))
+            sa, keep = pbf.upload(eng, a, int(rng.integers(0, 4)), n_a + int(rng.integers(0, 9)))
+            sb, keep_b = pbf.upload(eng, b, int(rng.integers(0, 4)), n_b + int(rng.integers(0, 9)))
+            keep = list(keep) + list(keep_b)
+    elif rects:
         a = (rng.uniform(-3, 3, (1, n_a)) + rng.uniform(-2, 2, (8, n_a))).astype(np.float32)
         b = a if (n_a == n_b and rng.random() < 0.3) else (rng.uniform(-3, 3, (1, n_b)) + rng.uniform(-2, 2, (8, n_b))).astype(np.float32)
         if rng.random() < 0.3:
@@ -69,7 +90,11 @@ def one(eng, rng, idx, announce=None):
         desc = f"config {idx}: polygons {n_a} x {n_b}, A {da}, B {'= A' if same else db}, list {length} in {cap}, count {n_dev}, bases {rb}, {cb}"
     if announce is not None:
         announce(desc)
-    pairs = random_list(rng, n_a, n_b, length)
+    if near_tie:      # pair (A_i, B_i) is the near-tie: the diagonal in a shuffled order (rows change inside a wave)
+        order = rng.permutation(n_a)
+        pairs = np.stack([order, order], axis=1).astype(np.int64)
+    else:
+        pairs = random_list(rng, n_a, n_b, length)
     listed = np.full((cap, 2), 0xFFFFFFFF, np.uint32)
     listed[:length] = ((pairs + (rb, cb)) & 0xFFFFFFFF).astype(np.uint32)
     # what the call sees is the u32 list minus the bases: an entry that wrapped is judged as the call judges it
