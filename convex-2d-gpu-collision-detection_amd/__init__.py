@@ -24,6 +24,11 @@ from .binding import (  # noqa: F401
     POLY_DT,
     POLY_POSE_DT,
     CONTACT_DT,
+    MANIFOLD_DT,
+    MANIFOLD_REF_IS_B,
+    MANIFOLD_P0_CLIPPED,
+    MANIFOLD_P1_CLIPPED,
+    MANIFOLD_OUTSIDE_SLAB,
     make_polygon,
     library_path,
     load_library,

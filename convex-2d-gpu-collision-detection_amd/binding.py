@@ -31,6 +31,11 @@ POLY_POSE_DT = np.dtype([("theta", "<f4"), ("obstacle", POLY_DT)])              
 CONTACT_DT = np.dtype([("depth", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("axis", "<u2"), ("hit", "u1"), ("flags", "u1")])   # c2d_contact
 CONTACT_NO_AXIS, CONTACT_BAD_PAIR = 1, 2
 
+# contact manifolds (include/c2d.h, "contact manifolds: up to two contact points per listed pair")
+MANIFOLD_DT = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("d0", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("d1", "<f4"), ("feature", "<u2"), ("count", "u1"),
+                        ("flags", "u1"), ("reserved", "<u4")])   # c2d_manifold
+MANIFOLD_REF_IS_B, MANIFOLD_P0_CLIPPED, MANIFOLD_P1_CLIPPED, MANIFOLD_OUTSIDE_SLAB = 1, 2, 4, 8
+
 
 class C2DError(RuntimeError):
     def __init__(self, status: int, what: str, detail: str = ""):
@@ -162,6 +167,8 @@ _SIGNATURES = {
                                            C.c_void_p]),
     "c2d_poly_pair_contacts": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
                                          C.c_void_p, C.c_void_p]),
+    "c2d_poly_pair_manifolds": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "c2d_rect_pair_contacts": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                          C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_bins_create": (C.c_int, [C.c_void_p, C.POINTER(_PolyBin), C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -746,10 +753,20 @@ class Engine:
         self._check(self.lib.c2d_rect_pair_contacts(self.h, a, n_a, b, n_b, _ptr_of(pairs), n_pairs, _ptr_of(n_pairs_dev), row_base, col_base,
                                                     _ptr_of(out), C.c_void_p(stream)), "c2d_rect_pair_contacts")
 
-    def _contacts_of_list(self, name: str, arrays: Sequence, list_call, contacts_call, check_async: bool = False):
+    def poly_pair_manifolds(self, a: _PolySet, b: _PolySet, pairs, n_pairs: int, contacts, manifolds, n_pairs_dev=None, row_base: int = 0,
+                            col_base: int = 0, stream: int = 0):
+        """c2d_poly_pair_manifolds: poly_pair_contacts into contacts[p] (CONTACT_DT[n_pairs]) and, in the same device call, the
+        manifold of list entry p into manifolds[p] (MANIFOLD_DT[n_pairs]); both outputs required and 16-byte aligned"""
+        if not isinstance(a, _PolySet) or not isinstance(b, _PolySet):
+            raise ValueError("need two poly_set() descriptions")
+        self._check(self.lib.c2d_poly_pair_manifolds(self.h, C.byref(a), C.byref(b), _ptr_of(pairs), n_pairs, _ptr_of(n_pairs_dev), row_base, col_base,
+                                                     _ptr_of(contacts), _ptr_of(manifolds), C.c_void_p(stream)), "c2d_poly_pair_manifolds")
+
+    def _contacts_of_list(self, name: str, arrays: Sequence, list_call, contacts_call, check_async: bool = False, manifolds: bool = False):
         """The one shape of the *_contacts_host functions: a count-only list call sizes the buffers, then the list call and the
         contacts call run back to back on the list's DEVICE count (no read-back between them).  list_call(pairs, capacity, count),
-        contacts_call(pairs, capacity, count, out).  Frees `arrays` and its own on every way out.  -> (pairs, contacts)"""
+        contacts_call(pairs, capacity, count, out).  Frees `arrays` and its own on every way out.  -> (pairs, contacts)
+        manifolds: contacts_call(pairs, capacity, count, out, manifolds_out) fills a second output; -> (pairs, contacts, manifolds)"""
         arrays = [x for x in arrays if x is not None]
         try:
             d_cnt = self.zeros(1, np.uint64)
@@ -759,16 +776,20 @@ class Engine:
             if check_async:
                 self.check_async()
             if total == 0:
-                return np.zeros((0, 2), np.uint32), np.zeros(0, CONTACT_DT)
+                return (np.zeros((0, 2), np.uint32), np.zeros(0, CONTACT_DT)) + ((np.zeros(0, MANIFOLD_DT),) if manifolds else ())
             d_pairs, d_out = self.empty((total, 2), np.uint32), self.empty(total, CONTACT_DT)
             arrays += [d_pairs, d_out]
+            outs = [d_out]
+            if manifolds:
+                outs.append(self.empty(total, MANIFOLD_DT))
+                arrays.append(outs[1])
             self.memset(d_cnt, 0, 8)
             list_call(d_pairs, total, d_cnt)
-            contacts_call(d_pairs, total, d_cnt, d_out)
-            pairs, contacts = d_pairs.get(), d_out.get()
+            contacts_call(d_pairs, total, d_cnt, *outs)
+            got = (d_pairs.get(),) + tuple(x.get() for x in outs)
             if int(d_cnt.get()[0]) != total:
                 raise C2DError(-2, name, "the list call counted a different total than the count-only call")
-            return pairs, contacts
+            return got
         finally:
             for x in arrays:
                 x.free()
@@ -777,6 +798,14 @@ class Engine:
         """Host convenience: the sets of poly_broad_pairs_host (vx_b None: the same set) -> (pairs u32 [total][2], contacts
         CONTACT_DT[total]): the colliding pairs through the broad phase (broad=False: the N x M list) and their contacts, computed
         on the list's device count."""
+        return self._poly_contacts_host("poly_contacts_host", False, vx_a, vy_a, k_a, vx_b, vy_b, k_b, upper, broad)
+
+    def poly_manifolds_host(self, vx_a, vy_a, k_a, vx_b=None, vy_b=None, k_b=None, upper: bool = False, broad: bool = True):
+        """Host convenience: poly_contacts_host through c2d_poly_pair_manifolds -> (pairs u32 [total][2], contacts CONTACT_DT[total],
+        manifolds MANIFOLD_DT[total])."""
+        return self._poly_contacts_host("poly_manifolds_host", True, vx_a, vy_a, k_a, vx_b, vy_b, k_b, upper, broad)
+
+    def _poly_contacts_host(self, name: str, manifolds: bool, vx_a, vy_a, k_a, vx_b, vy_b, k_b, upper: bool, broad: bool):
         vx_a, vy_a, k_a = self._host_poly_set(vx_a, vy_a, k_a)
         same = vx_b is None
         if same:
@@ -789,13 +818,14 @@ class Engine:
         n_a = vx_a.shape[1]
         n_b = n_a if same else vx_b.shape[1]
         if n_a == 0 or n_b == 0:
-            return np.zeros((0, 2), np.uint32), np.zeros(0, CONTACT_DT)
+            return (np.zeros((0, 2), np.uint32), np.zeros(0, CONTACT_DT)) + ((np.zeros(0, MANIFOLD_DT),) if manifolds else ())
         arrays = self._to_device_all([vx_a, vy_a, k_a] + ([] if same else [vx_b, vy_b, k_b]))
         a = self.poly_set(*arrays[:3], n_a, vx_a.shape[0])
         b = a if same else self.poly_set(*arrays[3:], n_b, vx_b.shape[0])
         lister = self.sat_poly_broad_pairs if broad else self.sat_poly_cross_pairs
-        return self._contacts_of_list("poly_contacts_host", arrays, lambda pairs, cap, cnt: lister(a, b, pairs, cap, cnt, upper=upper),
-                                      lambda pairs, cap, cnt, out: self.poly_pair_contacts(a, b, pairs, cap, out, n_pairs_dev=cnt), check_async=True)
+        call = self.poly_pair_manifolds if manifolds else self.poly_pair_contacts
+        return self._contacts_of_list(name, arrays, lambda pairs, cap, cnt: lister(a, b, pairs, cap, cnt, upper=upper),
+                                      lambda pairs, cap, cnt, *outs: call(a, b, pairs, cap, *outs, n_pairs_dev=cnt), check_async=True, manifolds=manifolds)
 
     def rect_contacts_host(self, a_planes: np.ndarray, b_planes: Optional[np.ndarray] = None, upper: bool = False, broad: bool = True):
         """Host convenience: the sets of rect_broad_pairs_host (b_planes None: the same set) -> (pairs u32 [total][2], contacts

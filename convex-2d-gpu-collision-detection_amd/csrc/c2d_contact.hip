@@ -1,6 +1,7 @@
 // c2d_contact.hip — contact queries for gfx950 (MI355X): for each listed pair (A_i, B_j) the minimum-translation contact over the
 // pairwise test's own axes — a signed depth, a unit normal from A to B, the axis it came from — and the boolean of the pairwise
-// test itself (c2d_poly_pair_contacts, c2d_rect_pair_contacts; include/c2d.h).
+// test itself (c2d_poly_pair_contacts, c2d_rect_pair_contacts; include/c2d.h) — and, for polygons, the same contact
+// with its manifold of up to two points in one fused call (c2d_poly_pair_manifolds; poly_manifold below).
 //
 // The rule (the contract of include/c2d.h), per axis n in axis order, with [minA, maxA] and [minB, maxB] the projection intervals
 // the pairwise test computes on n:
@@ -31,6 +32,11 @@ static_assert(sizeof(c2d_contact) == 16 && offsetof(c2d_contact, axis) == 12 && 
 constexpr int kContactBlock = 256;
 constexpr int kContactMaxGrid = 1 << 16;   // blocks per launch; the kernel grid-strides beyond it
 constexpr uint32_t kContactNoAxis = 0xFFFFu;
+constexpr uint32_t kManifoldNoFeature = 0xFFFFu;
+
+static_assert(sizeof(c2d_manifold) == 32 && offsetof(c2d_manifold, x1) == 12 && offsetof(c2d_manifold, y1) == 16 && offsetof(c2d_manifold, feature) == 24 &&
+                  offsetof(c2d_manifold, count) == 26 && offsetof(c2d_manifold, flags) == 27 && offsetof(c2d_manifold, reserved) == 28,
+              "the kernel stores a manifold as two halves of four dwords");
 
 // what a pick leaves behind: the contact without its `hit`
 struct ContactValue {
@@ -158,6 +164,86 @@ C2D_DEV bool rect_contact_axes(const float (&r1)[8], const float (&r2)[8], Pick&
     return !sep;
 }
 
+// ---- the manifold of one polygon pair on its winning axis (include/c2d.h "contact manifolds") ---------------------
+// e, (nx, ny), len = sqrt(len2) and pos = (o1 <= o2) are the winning axis as the contact rule saw it.  Every vertex index is a
+// compile-time slot: the deepest vertex, its two neighbours and the reference edge are carried through selects.  Slots >= k repeat
+// vertex 0 (poly_load), so "next of k - 1" is slot k (slot 16 is slot 0), a padding slot never beats vertex 0 under the strict
+// compare, and the interval of R over all 16 slots is the contact rule's own.  The record leaves as two dwordx4 halves:
+// m0 = {x0, y0, d0, x1}, m1 = {y1, d1, feature | count << 16 | flags << 24, 0}.
+C2D_DEV void poly_manifold(const PolyObj& A, const PolyObj& B, uint32_t e, float nx, float ny, float len, bool pos, uint4& m0, uint4& m1)
+{
+    constexpr int K = C2D_POLY_KMAX;
+    const float inf = __builtin_inff();
+    const bool ref_b = e >= (uint32_t)A.k;
+    const int r = (int)e - (ref_b ? A.k : 0);
+    const int kI = ref_b ? A.k : B.k;
+    const bool up = ref_b != pos;   // sigma > 0: (R is A) == pos
+    PolyObj R, I;
+#pragma unroll
+    for (int f = 0; f < K; f++) {
+        R.x[f] = ref_b ? B.x[f] : A.x[f];
+        R.y[f] = ref_b ? B.y[f] : A.y[f];
+        I.x[f] = ref_b ? A.x[f] : B.x[f];
+        I.y[f] = ref_b ? A.y[f] : B.y[f];
+    }
+    // step 1: the face value F, from R's interval; step 4: the reference edge's two vertices (slots r and r + 1)
+    float mnr = inf, mxr = -inf;
+    float rx0 = R.x[0], ry0 = R.y[0], rx1 = R.x[0], ry1 = R.y[0];
+    const int r1 = (r + 1) & (K - 1);
+#pragma unroll
+    for (int f = 0; f < K; f++) {
+        poly_minmax(nx, ny, R.x[f], R.y[f], mnr, mxr);
+        if (f == r) { rx0 = R.x[f]; ry0 = R.y[f]; }
+        if (f == r1) { rx1 = R.x[f]; ry1 = R.y[f]; }
+    }
+    const float face = up ? mxr : mnr;
+    // step 2: the deepest vertex of I, first of equals, a NaN never replaces
+    float pr[K];
+#pragma unroll
+    for (int f = 0; f < K; f++) pr[f] = nx * I.x[f] + ny * I.y[f];
+    int w = 0;
+    float pw = pr[0];
+#pragma unroll
+    for (int f = 1; f < K; f++) {
+        const bool deeper = up ? pr[f] < pw : pr[f] > pw;
+        w = deeper ? f : w;
+        pw = deeper ? pr[f] : pw;
+    }
+    // step 3: its neighbours, and the other end u of the incident edge
+    const int prv = w == 0 ? kI - 1 : w - 1, nxt = (w + 1) & (K - 1);
+    float xw = I.x[0], yw = I.y[0], xn = I.x[0], yn = I.y[0], pn = pr[0], xp = I.x[0], yp = I.y[0], pp = pr[0];
+#pragma unroll
+    for (int f = 0; f < K; f++) {
+        if (f == w) { xw = I.x[f]; yw = I.y[f]; }
+        if (f == nxt) { xn = I.x[f]; yn = I.y[f]; pn = pr[f]; }
+        if (f == prv) { xp = I.x[f]; yp = I.y[f]; pp = pr[f]; }
+    }
+    const bool back = up ? pp < pn : pp > pn;
+    const float xu = back ? xp : xn, yu = back ? yp : yn;
+    const uint32_t feature = (uint32_t)(back ? prv : w);
+    // step 4: the slab of the reference edge
+    const float tau0 = ny * rx0 - nx * ry0, tau1 = ny * rx1 - nx * ry1;
+    const float lo = tau0 <= tau1 ? tau0 : tau1, hi = tau0 <= tau1 ? tau1 : tau0;
+    // step 5: each end against the original other end
+    const float tw = ny * xw - nx * yw, tu = ny * xu - nx * yu;
+    const bool c0 = tw < lo || tw > hi, c1 = tu < lo || tu > hi;
+    const float s0 = ((tw < lo ? lo : hi) - tw) / (tu - tw), s1 = ((tu < lo ? lo : hi) - tu) / (tw - tu);
+    const float cx0 = xw + (xu - xw) * s0, cy0 = yw + (yu - yw) * s0;
+    const float cx1 = xu + (xw - xu) * s1, cy1 = yu + (yw - yu) * s1;
+    const bool single = kI == 1;
+    const bool outside = !single && ((tw < lo && tu < lo) || (tw > hi && tu > hi));
+    const bool two = !single && !outside;
+    const float x0 = two && c0 ? cx0 : xw, y0 = two && c0 ? cy0 : yw;
+    const float x1 = c1 ? cx1 : xu, y1 = c1 ? cy1 : yu;
+    // step 6: the depths, from the final coordinates
+    const float p0 = nx * x0 + ny * y0, p1 = nx * x1 + ny * y1;
+    const float d0 = (up ? face - p0 : p0 - face) / len, d1 = (up ? face - p1 : p1 - face) / len;
+    const uint32_t flags = (ref_b ? (uint32_t)C2D_MANIFOLD_REF_IS_B : 0u) | (two && c0 ? (uint32_t)C2D_MANIFOLD_P0_CLIPPED : 0u) |
+                           (two && c1 ? (uint32_t)C2D_MANIFOLD_P1_CLIPPED : 0u) | (outside ? (uint32_t)C2D_MANIFOLD_OUTSIDE_SLAB : 0u);
+    m0 = make_uint4(__float_as_uint(x0), __float_as_uint(y0), __float_as_uint(d0), two ? __float_as_uint(x1) : 0u);
+    m1 = make_uint4(two ? __float_as_uint(y1) : 0u, two ? __float_as_uint(d1) : 0u, (single ? 0u : feature) | (two ? 2u << 16 : 1u << 16) | (flags << 24), 0u);
+}
+
 // The shape policies of the contact kernel:
 //   S::Set                 the device-side description of one set (a kernel argument);  S::size(set): its objects
 //   S::present(set, i)     false: object i is in no pair (a polygon with a vertex count outside 1..rows)
@@ -199,11 +285,12 @@ struct RectContactShape {
 };
 
 // One pair per lane.  Entry p of the list is processed when p < min(n_pairs, *d_n); nothing else of `out` is touched.  A pair with
-// an index outside its set, or with an absent object, reads no vertex and gets the BAD_PAIR contact.
-template <class S>
-__global__ __launch_bounds__(kContactBlock) void contact_kernel(typename S::Set A, typename S::Set B, const uint32_t* __restrict__ pairs, size_t n_pairs,
-                                                                const unsigned long long* __restrict__ d_n, size_t row_base, size_t col_base,
-                                                                c2d_contact* __restrict__ out, uint32_t* __restrict__ async_err)
+// an index outside its set, or with an absent object, reads no vertex and gets the BAD_PAIR contact.  kManifold (polygons): the
+// manifold of the pair goes to man[p] as well, as two more 16-byte stores; without it the routine is the contact kernel as it was.
+template <class S, bool kManifold>
+C2D_DEV void contact_pairs(const typename S::Set& A, const typename S::Set& B, const uint32_t* __restrict__ pairs, size_t n_pairs,
+                           const unsigned long long* __restrict__ d_n, size_t row_base, size_t col_base, c2d_contact* __restrict__ out,
+                           c2d_manifold* __restrict__ man, uint32_t* __restrict__ async_err)
 {
     size_t bound = n_pairs;
     if (d_n) {
@@ -233,6 +320,7 @@ __global__ __launch_bounds__(kContactBlock) void contact_kernel(typename S::Set 
             if (e) __hip_atomic_fetch_or(async_err, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         uint4 word = make_uint4(0u, 0u, 0u, kContactNoAxis | ((uint32_t)C2D_CONTACT_BAD_PAIR << 24));   // depth 0, normal (0, 0), hit 0
+        uint4 m0 = make_uint4(0u, 0u, 0u, 0u), m1 = make_uint4(0u, 0u, kManifoldNoFeature, 0u);   // no point, no feature
         const unsigned long long vm = __ballot(valid);
         if (vm != 0ull) {   // (wave-uniform)
             // Lanes without a valid pair compute the first valid lane's pair and drop the result: every index used below is inside
@@ -250,18 +338,56 @@ __global__ __launch_bounds__(kContactBlock) void contact_kernel(typename S::Set 
             FastPick fast;
             const bool hit = S::axes(a, b, fast);
             ContactValue c;
+            float wnx = 0.0f, wny = 0.0f, wlen = 1.0f;   // the winning axis as the rule saw it: raw normal, sqrt(len2), o1 <= o2
+            bool wpos = true;
             if (fast.decided()) {
                 c = fast.value();
+                if constexpr (kManifold) {
+                    wnx = fast.nx; wny = fast.ny; wlen = __builtin_sqrtf(fast.len2); wpos = fast.pos;
+                }
             } else {
                 ExactPick exact;
                 (void)S::axes(a, b, exact);
                 c = exact.value();
+                if constexpr (kManifold) {
+                    wnx = exact.nx; wny = exact.ny; wlen = exact.len; wpos = exact.pos;
+                }
             }
             if (valid)
                 word = make_uint4(__float_as_uint(c.depth), __float_as_uint(c.nx), __float_as_uint(c.ny), c.axis | (hit ? 1u << 16 : 0u) | (c.flags << 24));
+            if constexpr (kManifold) {
+                uint4 v0, v1;
+                poly_manifold(a, b, c.axis, wnx, wny, wlen, wpos, v0, v1);   // (axis 0xFFFF: computes on axis (0, 0) and is dropped)
+                if (valid && c.axis != kContactNoAxis) {
+                    m0 = v0;
+                    m1 = v1;
+                }
+            }
         }
-        if (in) reinterpret_cast<uint4*>(out)[p] = word;   // d_out is 16-byte aligned (checked on the host)
+        if (in) {
+            reinterpret_cast<uint4*>(out)[p] = word;   // d_out is 16-byte aligned (checked on the host)
+            if constexpr (kManifold) {
+                reinterpret_cast<uint4*>(man)[2 * p] = m0;
+                reinterpret_cast<uint4*>(man)[2 * p + 1] = m1;
+            }
+        }
     }
+}
+
+template <class S>
+__global__ __launch_bounds__(kContactBlock) void contact_kernel(typename S::Set A, typename S::Set B, const uint32_t* __restrict__ pairs, size_t n_pairs,
+                                                                const unsigned long long* __restrict__ d_n, size_t row_base, size_t col_base,
+                                                                c2d_contact* __restrict__ out, uint32_t* __restrict__ async_err)
+{
+    contact_pairs<S, false>(A, B, pairs, n_pairs, d_n, row_base, col_base, out, nullptr, async_err);
+}
+
+__global__ __launch_bounds__(kContactBlock) void manifold_kernel(PolySetDev A, PolySetDev B, const uint32_t* __restrict__ pairs, size_t n_pairs,
+                                                                 const unsigned long long* __restrict__ d_n, size_t row_base, size_t col_base,
+                                                                 c2d_contact* __restrict__ out, c2d_manifold* __restrict__ man,
+                                                                 uint32_t* __restrict__ async_err)
+{
+    contact_pairs<PolyContactShape, true>(A, B, pairs, n_pairs, d_n, row_base, col_base, out, man, async_err);
 }
 
 // the arguments both entry points share, then the launch
@@ -283,6 +409,25 @@ int contact_run(c2d_ctx* ctx, const char* what, const typename S::Set& A, const 
     return C2D_OK;
 }
 
+// c2d_poly_pair_manifolds: contact_run's checks with the second output, then the fused launch
+int manifold_run(c2d_ctx* ctx, const char* what, const PolySetDev& A, const PolySetDev& B, const uint32_t* d_pairs, size_t n_pairs,
+                 const unsigned long long* d_n_pairs, size_t row_base, size_t col_base, c2d_contact* d_contacts, c2d_manifold* d_manifolds, c2d_stream stream)
+{
+    if (int rc = cross_check_flags_bases(ctx, what, A.n, B.n, row_base, col_base, 0)) return rc;
+    if (!d_pairs) return cross_fail(ctx, what, "NULL pair list");
+    if (!d_contacts || !d_manifolds) return cross_fail(ctx, what, "NULL output");
+    if (reinterpret_cast<uintptr_t>(d_pairs) & 3u) return cross_fail(ctx, what, "the pair list must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_contacts) | reinterpret_cast<uintptr_t>(d_manifolds)) & 15u)
+        return cross_fail(ctx, what, "both outputs must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_n_pairs) & 7u) return cross_fail(ctx, what, "d_n_pairs must be 8-byte aligned");
+    if (n_pairs > kBaseLimit) return cross_fail(ctx, what, "n_pairs must stay below 2^62");
+    DeviceGuard dg(ctx->device);
+    hipLaunchKernelGGL(manifold_kernel, dim3(grid_for(n_pairs, kContactBlock, kContactMaxGrid)), dim3(kContactBlock), 0, (hipStream_t)stream, A, B, d_pairs,
+                       n_pairs, d_n_pairs, row_base, col_base, d_contacts, d_manifolds, ctx->d_async_err);
+    C2D_LAUNCH_CHECK(ctx);
+    return C2D_OK;
+}
+
 }  // namespace c2d
 
 using namespace c2d;
@@ -300,6 +445,20 @@ int c2d_poly_pair_contacts(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_s
     if (int rc = poly_set_check(ctx, what, "a", a, A)) return rc;
     if (int rc = poly_set_check(ctx, what, "b", b, B)) return rc;
     return contact_run<PolyContactShape>(ctx, what, A, B, d_pairs, n_pairs, d_n_pairs, row_base, col_base, d_out, stream);
+}
+
+int c2d_poly_pair_manifolds(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b, const uint32_t* d_pairs, size_t n_pairs,
+                            const unsigned long long* d_n_pairs, size_t row_base, size_t col_base, c2d_contact* d_contacts, c2d_manifold* d_manifolds,
+                            c2d_stream stream)
+{
+    const char* what = "c2d_poly_pair_manifolds";
+    if (!ctx) return C2D_ERR_INVALID_ARG;
+    if (!a || !b) return cross_fail(ctx, what, "NULL set");
+    if (n_pairs == 0) return C2D_OK;
+    PolySetDev A, B;
+    if (int rc = poly_set_check(ctx, what, "a", a, A)) return rc;
+    if (int rc = poly_set_check(ctx, what, "b", b, B)) return rc;
+    return manifold_run(ctx, what, A, B, d_pairs, n_pairs, d_n_pairs, row_base, col_base, d_contacts, d_manifolds, stream);
 }
 
 int c2d_rect_pair_contacts(c2d_ctx* ctx, const float* const d_a[8], size_t n_a, const float* const d_b[8], size_t n_b, const uint32_t* d_pairs,

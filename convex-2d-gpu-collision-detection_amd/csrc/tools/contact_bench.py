@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool: the contact queries (c2d_poly_pair_contacts / c2d_rect_pair_contacts) next to the list calls that feed them, one
+"""Developer tool: the contact queries (c2d_poly_pair_contacts / c2d_rect_pair_contacts, and c2d_poly_pair_manifolds) next to the list calls that feed them, one
 JSON line per configuration.  GPU only, no oracle (tests/test_gpu_contacts.py checks the values).
 
 Scenes: the sparse self-collision scenes of poly_broad_bench.py (K ~ U{3..16}, extent 200 * sqrt(N / 32768)) and broad_bench.py
@@ -10,6 +10,8 @@ median of --reps (>= 7) after a warm-up:
   contacts_ms     the contacts call alone on that list, bounded by the list's device count
   both_ms         the two back to back on the stream, no host synchronisation between them
   contacts_per_s  listed pairs / contacts_ms;   hits: the list's length
+  manifolds_ms    (polygon scenes) c2d_poly_pair_manifolds alone on the same list in the same run; manifolds_over_contacts is its
+                  ratio to contacts_ms — the contacts call is the yardstick
 The kernels' own times come from a separate run under `rocprofv3 --kernel-trace --stats -- python3 contact_bench.py --once`.
 usage: contact_bench.py [--n 131072] [--dense-n 3163] [--reps 7] [--once]"""
 import argparse
@@ -56,7 +58,7 @@ def main():
             ms.append(e0.elapsed_time(e1))
         return float(np.median(ms))
 
-    def report(config, n, list_call, contacts_call, total, extra=None):
+    def report(config, n, list_call, contacts_call, total, extra=None, manifolds_call=None):
         def both():
             if list_call is not None:
                 list_call()
@@ -64,6 +66,8 @@ def main():
 
         if args.once:
             both()
+            if manifolds_call is not None:
+                manifolds_call()
             stream.synchronize()
             return
         out = {"config": config, "n": n, "hits": total, "reps": reps}
@@ -73,6 +77,9 @@ def main():
         if list_call is not None:
             out["both_ms"] = round(timed(both), 4)
         out["contacts_per_s"] = round(total / (out["contacts_ms"] * 1e-3), 0)
+        if manifolds_call is not None:
+            out["manifolds_ms"] = round(timed(manifolds_call), 4)
+            out["manifolds_over_contacts"] = round(out["manifolds_ms"] / out["contacts_ms"], 3)
         out.update(extra or {})
         print(json.dumps(out), flush=True)
 
@@ -96,11 +103,16 @@ def main():
     def poly_contacts():
         eng.poly_pair_contacts(s, s, pairs.data_ptr(), total, out.data_ptr(), n_pairs_dev=cnt.data_ptr(), stream=sh)
 
+    man = torch.empty((max(total, 1), 32), dtype=torch.uint8, device=dev)
+
+    def poly_manifolds():
+        eng.poly_pair_manifolds(s, s, pairs.data_ptr(), total, out.data_ptr(), man.data_ptr(), n_pairs_dev=cnt.data_ptr(), stream=sh)
+
     poly_list()
-    report("sparse_polygons_self_upper", n, poly_list, poly_contacts, total, {"extent": round(float(extent), 2)})
+    report("sparse_polygons_self_upper", n, poly_list, poly_contacts, total, {"extent": round(float(extent), 2)}, poly_manifolds)
     hit_share = float((out.view(torch.int32)[:total, 3] >> 16 & 1).float().mean().item()) if total and not args.once else None
     assert hit_share in (None, 1.0), "a listed pair without `hit`"
-    del pairs, out
+    del pairs, out, man
 
     # -- sparse rectangles, self-collision -------------------------------------------------------------------------------
     poses = wl.random_obb_pose_planes(n, seed=0xB0AD, extent=extent)
@@ -139,7 +151,12 @@ def main():
     def dense_contacts():
         eng.poly_pair_contacts(sa, sb, dense.data_ptr(), m * m, dout.data_ptr(), stream=sh)
 
-    report("dense_polygon_list", m, None, dense_contacts, m * m)
+    dman = torch.empty((m * m, 32), dtype=torch.uint8, device=dev)
+
+    def dense_manifolds():
+        eng.poly_pair_manifolds(sa, sb, dense.data_ptr(), m * m, dout.data_ptr(), dman.data_ptr(), stream=sh)
+
+    report("dense_polygon_list", m, None, dense_contacts, m * m, None, dense_manifolds)
     eng.check_async()
     eng.close()
 

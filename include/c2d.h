@@ -456,6 +456,61 @@ int c2d_rect_pair_contacts(c2d_ctx* ctx, const float* const d_a[8], size_t n_a, 
                            size_t row_base, size_t col_base,
                            c2d_contact* d_out, c2d_stream stream);
 
+/* ---- contact manifolds: up to two contact points per listed pair ------------------
+ * An addition to 0.6 (c2d_version() stays 6), found by symbol lookup.
+ *
+ * c2d_poly_pair_manifolds: c2d_poly_pair_contacts and, fused into the same device call, WHERE the two polygons touch: the edge of
+ * the other polygon that faces the contact's own edge, clipped to that edge's extent — one or two points, each with its own signed
+ * penetration.  The sets, the list, d_n_pairs, the bases, the records at or beyond the bound (untouched, in BOTH outputs), bad
+ * pairs, the asynchronous error word, the refused arguments, "no ctx scratch" and graph capture are those of
+ * c2d_poly_pair_contacts.  Both outputs are required, and both are 16-byte aligned.
+ *   d_contacts[p]  : bit for bit what c2d_poly_pair_contacts writes for the same arguments.
+ *   d_manifolds[p] : the manifold of list entry p.  A contact with C2D_CONTACT_BAD_PAIR or C2D_CONTACT_NO_AXIS has the empty
+ *                    manifold: all coordinates and depths 0, feature = 0xFFFF, count = 0, flags = 0.
+ * Polygons only.  c2d_rect_pair_contacts uses the edge VECTORS of convex_collide as axes, and an edge vector is not the normal of
+ * any edge of a general quad, so "reference edge" has no meaning there: pass rectangles as 4-gons of a set with rows = 4.
+ *
+ * Arithmetic contract.  Everything is IEEE binary32, round to nearest, subnormals kept, nothing contracted;
+ * division is correctly rounded.  The contact rule above supplies the winning axis e, its raw (nx, ny), pos = (o1 <= o2) and
+ * len = sqrt(len2).
+ *   1. R = A when e < ka, else B (the REFERENCE polygon; its edge r = e or e - ka is the reference edge); I is the other polygon
+ *      (the INCIDENT one), with kI vertices.  sigma = +1 when (R is A) == pos, else -1.  F = sigma > 0 ? maxR : minR, with
+ *      [minR, maxR] the contact rule's own interval of R on this axis.
+ *   2. p_f = nx * x_f + ny * y_f for the vertices f < kI of I.  The deepest vertex w starts at f = 0; a later f replaces it only
+ *      under strict p_f < p_w (sigma > 0) or p_f > p_w (sigma < 0): compare and select, not fmin — the first of equals wins and a
+ *      NaN never replaces.
+ *   3. nxt = (w + 1) mod kI, prv = (w - 1 + kI) mod kI.  The other end of the incident edge is u = nxt, unless p_prv is strictly
+ *      deeper than p_nxt in the sense of step 2; then u = prv.  feature = (u == nxt) ? w : prv — the incident edge in I's own
+ *      numbering.  kI == 1: count = 1, point 0 is w, feature = 0, and steps 4 and 5 do not apply (no clip bit, no OUTSIDE_SLAB).
+ *   4. tau(x, y) = ny * x - nx * y (two products, one subtraction).  tau0, tau1 are tau at R's vertices r and (r + 1) mod kR;
+ *      lo = tau0 <= tau1 ? tau0 : tau1, hi the other.
+ *   5. Each end g of the incident edge is clipped against the ORIGINAL other end h: bound = lo if tau_g < lo, hi if tau_g > hi,
+ *      otherwise the end stays.  A clipped end becomes x = x_g + (x_h - x_g) * s, y = y_g + (y_h - y_g) * s with
+ *      s = (bound - tau_g) / (tau_h - tau_g), and its CLIPPED bit is set.  If both ends are below lo or both above hi:
+ *      count = 1, point 0 is w unclipped, OUTSIDE_SLAB is set.  Otherwise count = 2: point 0 from w, point 1 from u.
+ *   6. Each kept point: p = nx * x + ny * y from its final coordinates, d = (sigma > 0 ? F - p : p - F) / len.
+ * Both points are always reported, each with its own sign: a corner contact has d1 < 0 and the caller filters (a speculative
+ * solver wants exactly that).  Point 0 unclipped has d0 == depth of the contact.  Non-finite coordinates give whatever this
+ * arithmetic gives; +0 and -0 compare equal. */
+#define C2D_MANIFOLD_REF_IS_B      1  /* the reference edge belongs to B (axis >= ka) */
+#define C2D_MANIFOLD_P0_CLIPPED    2  /* point 0 was moved onto a side plane of the reference edge */
+#define C2D_MANIFOLD_P1_CLIPPED    4
+#define C2D_MANIFOLD_OUTSIDE_SLAB  8  /* the incident edge misses the reference edge's slab: count = 1, the deepest vertex unclipped */
+
+typedef struct c2d_manifold {   /* 32 bytes, 16-byte aligned output */
+    float    x0, y0, d0;        /* point 0 (starts at the deepest vertex of the incident polygon) and its signed depth */
+    float    x1, y1, d1;        /* point 1 (starts at the other end of the incident edge); 0, 0, 0 when count < 2 */
+    uint16_t feature;           /* incident edge, in the incident polygon's own numbering 0..k-1; 0xFFFF: none */
+    uint8_t  count;             /* 0, 1 or 2 */
+    uint8_t  flags;
+    uint32_t reserved;          /* written as 0 */
+} c2d_manifold;
+
+int c2d_poly_pair_manifolds(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b,
+                            const uint32_t* d_pairs, size_t n_pairs, const unsigned long long* d_n_pairs,
+                            size_t row_base, size_t col_base,
+                            c2d_contact* d_contacts, c2d_manifold* d_manifolds, c2d_stream stream);
+
 /* ---- binned polygon batches ---------------------------------------------------
  * The padded layout above moves 16 vertex rows per polygon whatever the polygons are: with
  * K ~ U{3..16} that is 259 bytes per pair for 155 bytes of real vertices, and no kernel can

@@ -1,0 +1,102 @@
+"""CPU tests of c2d_poly_pair_manifolds at the C-ABI boundary, after tests/test_contact_boundary.py: the header declares the entry and
+c2d_manifold, every shipped build exports the symbol, the Python mirror types it and lays the record out as a C compiler does, and
+argument errors come back as statuses.  No compute entry point reaches a device here."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG_DIR = os.path.join(ROOT, "convex-2d-gpu-collision-detection_amd")
+SYMBOL = "c2d_poly_pair_manifolds"
+BUILDS = [os.path.join(PKG_DIR, "lib", n) for n in ("libc2d.so", "libc2d_fmad1.so", "libc2d_fmad2.so", "libc2d_nopretest.so",
+                                                    "libc2d_movecheck.so", "libc2d_splitcheck.so")]
+BUILDS.append(os.path.join(PKG_DIR, "lib-rehearsal", "libc2d.so"))
+FIELDS = ["x0", "y0", "d0", "x1", "y1", "d1", "feature", "count", "flags", "reserved"]
+OFFSETS = [0, 4, 8, 12, 16, 20, 24, 26, 27, 28]
+FLAGS = {"C2D_MANIFOLD_REF_IS_B": 1, "C2D_MANIFOLD_P0_CLIPPED": 2, "C2D_MANIFOLD_P1_CLIPPED": 4, "C2D_MANIFOLD_OUTSIDE_SLAB": 8}
+
+
+def header_text():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "c2d.h")).read(), flags=re.S)
+
+
+def test_header_declares_the_entry_point_and_the_record():
+    text = header_text()
+    assert re.search(r"\bint\s+c2d_poly_pair_manifolds\s*\(\s*c2d_ctx\s*\*\s*\w*\s*,\s*const\s+c2d_poly_set\s*\*\s*a\s*,\s*const\s+c2d_poly_set\s*\*\s*b\s*,"
+                     r"\s*const\s+uint32_t\s*\*\s*d_pairs\s*,\s*size_t\s+n_pairs\s*,\s*const\s+unsigned\s+long\s+long\s*\*\s*d_n_pairs\s*,"
+                     r"\s*size_t\s+row_base\s*,\s*size_t\s+col_base\s*,\s*c2d_contact\s*\*\s*d_contacts\s*,\s*c2d_manifold\s*\*\s*d_manifolds\s*,"
+                     r"\s*c2d_stream\s+stream\s*\)", text)
+    body = re.search(r"typedef\s+struct\s+c2d_manifold\s*\{([^}]*)\}\s*c2d_manifold\s*;", text).group(1)
+    names = [n.strip() for decl in body.split(";") if decl.strip() for n in re.sub(r"^\s*\w+\s+", "", decl.strip()).split(",")]
+    assert names == FIELDS
+    for name, value in FLAGS.items():
+        assert re.search(r"#define\s+%s\s+%d\b" % (name, value), text), name
+    # the header says what the call does not take
+    assert re.search(r"Polygons only\..*?rows = 4", open(os.path.join(ROOT, "include", "c2d.h")).read(), flags=re.S)
+
+
+@pytest.mark.parametrize("path", BUILDS, ids=lambda p: os.path.relpath(p, PKG_DIR))
+def test_every_build_exports_the_symbol(pkg, path):
+    assert os.path.exists(path), path
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    names = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+    assert SYMBOL in names, f"{os.path.basename(path)} does not export {SYMBOL}"
+
+
+def test_mirror_types_the_symbol_and_the_record(pkg, tmp_path):
+    from c2d_amd import binding
+
+    lib = pkg.load_library()
+    assert lib.c2d_version() == 6
+    assert SYMBOL in binding.EXPORTED_SYMBOLS
+    res, args = binding._SIGNATURES[SYMBOL]
+    assert res is C.c_int and len(args) == 11 and getattr(lib, SYMBOL).argtypes == args
+    assert args[1] == args[2] == C.POINTER(binding._PolySet)
+    # sizeof(c2d_manifold), the field offsets and the flag values, from a C program compiled against the header
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "c2d.h"\nint main(void){ printf("%zu", sizeof(c2d_manifold)); '
+                   + "".join('printf(" %%zu", offsetof(c2d_manifold, %s)); ' % f for f in FIELDS)
+                   + "".join('printf(" %%d", %s); ' % f for f in FLAGS) + "return 0; }\n")
+    exe = tmp_path / "layout"
+    subprocess.run(["gcc", "-std=c11", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    nums = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert nums[0] == 32 and nums[1:11] == OFFSETS
+    dt = pkg.MANIFOLD_DT
+    assert dt is binding.MANIFOLD_DT and dt.itemsize == 32 and list(dt.names) == FIELDS
+    assert [dt.fields[f][1] for f in FIELDS] == OFFSETS
+    assert [dt.fields[f][0] for f in FIELDS] == [np.dtype("<f4")] * 6 + [np.dtype("<u2"), np.dtype("u1"), np.dtype("u1"), np.dtype("<u4")]
+    assert nums[11:] == [pkg.MANIFOLD_REF_IS_B, pkg.MANIFOLD_P0_CLIPPED, pkg.MANIFOLD_P1_CLIPPED, pkg.MANIFOLD_OUTSIDE_SLAB] == list(FLAGS.values())
+
+
+def test_null_and_bad_arguments_are_rejected_without_a_device(pkg):
+    from c2d_amd import binding
+
+    lib = pkg.load_library()
+    s = binding._PolySet(16, 10, 0, 0x1000, 0x1000, 0x1000)
+    p, c, m = C.c_void_p(0x1000), C.c_void_p(0x2000), C.c_void_p(0x3000)
+    call = lib.c2d_poly_pair_manifolds
+    # no ctx: refused whatever else is passed
+    assert call(None, C.byref(s), C.byref(s), p, 4, None, 0, 0, c, m, None) == -1
+    assert call(None, None, None, None, 0, None, 0, 0, None, None, None) == -1
+    assert call(None, C.byref(s), C.byref(s), p, 4, None, 0, 0, C.c_void_p(0x2008), m, None) == -1   # (misaligned outputs too)
+    assert call(None, C.byref(s), C.byref(s), p, 4, None, 0, 0, c, C.c_void_p(0x3010 - 8), None) == -1
+    # (with a ctx, every other refusal is checked on the GPU: tests/test_gpu_manifolds.py::test_argument_errors)
+
+
+def test_host_convenience_checks_its_shapes_before_touching_a_device(pkg, wl):
+    eng = object.__new__(pkg.Engine)   # no ctx: the shape checks come first
+    vx, vy, k = wl.random_convex_polygon_set(8, seed=1)
+    for args in ((vx, vy[:, :7], k), (vx, vy, k[:7]), (vx[0], vy[0], k)):
+        with pytest.raises(ValueError):
+            pkg.Engine.poly_manifolds_host(eng, *args)
+    with pytest.raises(ValueError):
+        pkg.Engine.poly_manifolds_host(eng, vx, vy, k, None, vy, k)
+    with pytest.raises(ValueError):
+        pkg.Engine.poly_pair_manifolds(eng, None, None, 0, 0, 0, 0)
+    pairs, contacts, manifolds = pkg.Engine.poly_manifolds_host(eng, vx[:, :0], vy[:, :0], k[:0])
+    assert pairs.shape == (0, 2) and contacts.shape == (0,) and contacts.dtype == pkg.CONTACT_DT
+    assert manifolds.shape == (0,) and manifolds.dtype == pkg.MANIFOLD_DT
