@@ -29,6 +29,11 @@ from .binding import (  # noqa: F401
     MANIFOLD_P0_CLIPPED,
     MANIFOLD_P1_CLIPPED,
     MANIFOLD_OUTSIDE_SLAB,
+    DISTANCE_DT,
+    DISTANCE_EDGE_ON_B,
+    DISTANCE_INTERIOR,
+    DISTANCE_NO_CANDIDATE,
+    DISTANCE_BAD_PAIR,
     make_polygon,
     library_path,
     load_library,

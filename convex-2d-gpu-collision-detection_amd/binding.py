@@ -36,6 +36,11 @@ MANIFOLD_DT = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("d0", "<f4"), ("x1", "<f4
                         ("flags", "u1"), ("reserved", "<u4")])   # c2d_manifold
 MANIFOLD_REF_IS_B, MANIFOLD_P0_CLIPPED, MANIFOLD_P1_CLIPPED, MANIFOLD_OUTSIDE_SLAB = 1, 2, 4, 8
 
+# distance queries (include/c2d.h, "distance queries: separation and closest points for listed pairs")
+DISTANCE_DT = np.dtype([("dist", "<f4"), ("ax", "<f4"), ("ay", "<f4"), ("bx", "<f4"), ("by", "<f4"), ("edge", "<u2"), ("vert", "<u2"), ("hit", "u1"),
+                        ("flags", "u1"), ("reserved0", "<u2"), ("reserved1", "<u4")])   # c2d_distance
+DISTANCE_EDGE_ON_B, DISTANCE_INTERIOR, DISTANCE_NO_CANDIDATE, DISTANCE_BAD_PAIR = 1, 2, 4, 8
+
 
 class C2DError(RuntimeError):
     def __init__(self, status: int, what: str, detail: str = ""):
@@ -171,6 +176,10 @@ _SIGNATURES = {
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "c2d_rect_pair_contacts": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                          C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "c2d_poly_pair_distances": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                          C.c_void_p, C.c_void_p]),
+    "c2d_rect_pair_distances": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_bins_create": (C.c_int, [C.c_void_p, C.POINTER(_PolyBin), C.c_size_t, C.POINTER(C.c_void_p)]),
     "c2d_poly_bins_from_padded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "c2d_poly_bins_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -761,6 +770,24 @@ class Engine:
             raise ValueError("need two poly_set() descriptions")
         self._check(self.lib.c2d_poly_pair_manifolds(self.h, C.byref(a), C.byref(b), _ptr_of(pairs), n_pairs, _ptr_of(n_pairs_dev), row_base, col_base,
                                                      _ptr_of(contacts), _ptr_of(manifolds), C.c_void_p(stream)), "c2d_poly_pair_manifolds")
+
+    # -- distance queries (include/c2d.h "distance queries: separation and closest points for listed pairs") -----------------
+    def poly_pair_distances(self, a: _PolySet, b: _PolySet, pairs, n_pairs: int, out, n_pairs_dev=None, row_base: int = 0, col_base: int = 0,
+                            stream: int = 0):
+        """c2d_poly_pair_distances: out[p] (DISTANCE_DT[n_pairs], 16-byte aligned) = the pairwise boolean of list entry p and, when it
+        is not hit, the distance of the two polygons with its two closest points; the list, n_pairs_dev and the bases as for
+        poly_pair_contacts"""
+        if not isinstance(a, _PolySet) or not isinstance(b, _PolySet):
+            raise ValueError("need two poly_set() descriptions")
+        self._check(self.lib.c2d_poly_pair_distances(self.h, C.byref(a), C.byref(b), _ptr_of(pairs), n_pairs, _ptr_of(n_pairs_dev), row_base, col_base,
+                                                     _ptr_of(out), C.c_void_p(stream)), "c2d_poly_pair_distances")
+
+    def rect_pair_distances(self, a_planes: Sequence, n_a: int, b_planes: Sequence, n_b: int, pairs, n_pairs: int, out, n_pairs_dev=None,
+                            row_base: int = 0, col_base: int = 0, stream: int = 0):
+        """c2d_rect_pair_distances: poly_pair_distances for two rectangle sets given as 8 vertex planes each"""
+        a, b = self._cross_planes(a_planes, b_planes)
+        self._check(self.lib.c2d_rect_pair_distances(self.h, a, n_a, b, n_b, _ptr_of(pairs), n_pairs, _ptr_of(n_pairs_dev), row_base, col_base,
+                                                     _ptr_of(out), C.c_void_p(stream)), "c2d_rect_pair_distances")
 
     def _contacts_of_list(self, name: str, arrays: Sequence, list_call, contacts_call, check_async: bool = False, manifolds: bool = False):
         """The one shape of the *_contacts_host functions: a count-only list call sizes the buffers, then the list call and the

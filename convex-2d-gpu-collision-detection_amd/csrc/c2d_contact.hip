@@ -10,7 +10,8 @@
 //     depth = d, normal = +-n / sqrt(len2) with + when o1 <= o2.
 // One pair per lane; the lanes of a wave hold unrelated pairs, so every loop runs over all vertex slots with compile-time indices
 // (c2d_poly_pair.hpp).  The pair list is row-major: the lanes of a wave mostly share their row, so A is loaded through one
-// wave-uniform index when they all do; B is a gather.  Each contact leaves as one 16-byte store.
+// wave-uniform index when they all do; B is a gather (listed_pairs, c2d_pair_list.hpp, which the distance queries share).  Each
+// contact leaves as one 16-byte store.
 //
 // One square root and one division per PAIR instead of one per axis (DESIGN.md §5.11 has the proof).  A first pass estimates every
 // axis's d as q = o * v_rsq_f32(len2) and keeps the smallest and the second smallest estimate.  With len2 in [2^-100, 2^100] and
@@ -20,17 +21,13 @@
 // larger than the best axis's, so the sequential rule picks that axis whatever the rounded values are, and its d and normal are
 // computed once with the correctly rounded sqrt and divisions.  A pair with an axis outside those ranges, a NaN anywhere, or two
 // estimates too close to call (ties: parallel edges, touching or equal shapes) runs the sequential rule itself in a second pass.
-#include "c2d_cross.hpp"
-#include "c2d_math.hpp"
-#include "c2d_poly_pair.hpp"
+#include "c2d_pair_list.hpp"
 
 namespace c2d {
 
 static_assert(sizeof(c2d_contact) == 16 && offsetof(c2d_contact, axis) == 12 && offsetof(c2d_contact, hit) == 14 && offsetof(c2d_contact, flags) == 15,
               "the kernel stores a contact as four dwords");
 
-constexpr int kContactBlock = 256;
-constexpr int kContactMaxGrid = 1 << 16;   // blocks per launch; the kernel grid-strides beyond it
 constexpr uint32_t kContactNoAxis = 0xFFFFu;
 constexpr uint32_t kManifoldNoFeature = 0xFFFFu;
 
@@ -244,188 +241,79 @@ C2D_DEV void poly_manifold(const PolyObj& A, const PolyObj& B, uint32_t e, float
     m1 = make_uint4(two ? __float_as_uint(y1) : 0u, two ? __float_as_uint(d1) : 0u, (single ? 0u : feature) | (two ? 2u << 16 : 1u << 16) | (flags << 24), 0u);
 }
 
-// The shape policies of the contact kernel:
-//   S::Set                 the device-side description of one set (a kernel argument);  S::size(set): its objects
-//   S::present(set, i)     false: object i is in no pair (a polygon with a vertex count outside 1..rows)
-//   S::load(set, i, obj)   object i in registers
+// The shapes of c2d_pair_list.hpp with what the contact kernels add:
 //   S::axes(a, b, pick)    the axes of the pairwise test of (a, b) to `pick`; returns the pairwise boolean
-struct PolyContactShape {
-    using Set = PolySetDev;
-    using Obj = PolyObj;
-    static constexpr uint32_t kAbsentErr = C2D_ASYNC_ERR_POLY_K;
-    static __host__ __device__ size_t size(const Set& X) { return X.n; }
-    static C2D_DEV bool present(const Set& X, size_t i)
-    {
-        int k;
-        return poly_count(X, i, k);
-    }
-    static C2D_DEV void load(const Set& X, size_t i, Obj& o) { poly_load(X, i, o); }
+struct PolyContactShape : PolyListShape {
     template <class Pick>
     static C2D_DEV bool axes(const Obj& a, const Obj& b, Pick& pick) { return poly_contact_axes(a, b, pick); }
 };
 
-struct RectContactSet {
-    const float* p[8];
-    size_t n;
-};
-
-struct RectContactShape {
-    using Set = RectContactSet;
-    struct Obj { float r[8]; };
-    static constexpr uint32_t kAbsentErr = 0u;
-    static __host__ __device__ size_t size(const Set& X) { return X.n; }
-    static C2D_DEV bool present(const Set&, size_t) { return true; }
-    static C2D_DEV void load(const Set& X, size_t i, Obj& o)
-    {
-#pragma unroll
-        for (int k = 0; k < 8; k++) o.r[k] = X.p[k][i];
-    }
+struct RectContactShape : RectListShape {
     template <class Pick>
     static C2D_DEV bool axes(const Obj& a, const Obj& b, Pick& pick) { return rect_contact_axes(a.r, b.r, pick); }
 };
 
-// One pair per lane.  Entry p of the list is processed when p < min(n_pairs, *d_n); nothing else of `out` is touched.  A pair with
-// an index outside its set, or with an absent object, reads no vertex and gets the BAD_PAIR contact.  kManifold (polygons): the
-// manifold of the pair goes to man[p] as well, as two more 16-byte stores; without it the routine is the contact kernel as it was.
+// The query of listed_pairs (c2d_pair_list.hpp): the contact of one pair per lane.  kManifold (polygons): the manifold of the pair
+// goes to man[p] as well, as two more 16-byte stores; without it the routine is the contact kernel as it was.
 template <class S, bool kManifold>
-C2D_DEV void contact_pairs(const typename S::Set& A, const typename S::Set& B, const uint32_t* __restrict__ pairs, size_t n_pairs,
-                           const unsigned long long* __restrict__ d_n, size_t row_base, size_t col_base, c2d_contact* __restrict__ out,
-                           c2d_manifold* __restrict__ man, uint32_t* __restrict__ async_err)
-{
-    size_t bound = n_pairs;
-    if (d_n) {
-        const unsigned long long listed = *d_n;
-        if (listed < (unsigned long long)bound) bound = (size_t)listed;
-    }
-    const uint32_t lane = threadIdx.x & 63u;
-    const size_t n_a = S::size(A), n_b = S::size(B);
-    const size_t step = (size_t)gridDim.x * kContactBlock;
-    // every lane of a wave makes the same trips (the loop variable is the wave's first entry): the ballots below see whole waves
-    for (size_t p0 = (size_t)blockIdx.x * kContactBlock + (threadIdx.x & ~63u); p0 < bound; p0 += step) {
-        const size_t p = p0 + lane;
-        const bool in = p < bound;
-        uint32_t gi = 0, gj = 0;
-        if (in) {
-            gi = pairs[2 * p];
-            gj = pairs[2 * p + 1];
-        }
-        // local indices; one below its base wraps to far above any n (n and the bases stay below 2^62)
-        const size_t i = (size_t)gi - row_base, j = (size_t)gj - col_base;
-        const bool ranged = in && i < n_a && j < n_b;
-        bool valid = false;
-        if (ranged) valid = S::present(A, i) && S::present(B, j);   // (the count planes are read inside the sets only)
-        const unsigned long long bad_index = __ballot(in && !ranged), absent = __ballot(ranged && !valid);
-        if (lane == 0) {
-            const uint32_t e = (bad_index ? C2D_ASYNC_ERR_PAIR_INDEX : 0u) | (absent ? S::kAbsentErr : 0u);
-            if (e) __hip_atomic_fetch_or(async_err, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        uint4 word = make_uint4(0u, 0u, 0u, kContactNoAxis | ((uint32_t)C2D_CONTACT_BAD_PAIR << 24));   // depth 0, normal (0, 0), hit 0
-        uint4 m0 = make_uint4(0u, 0u, 0u, 0u), m1 = make_uint4(0u, 0u, kManifoldNoFeature, 0u);   // no point, no feature
-        const unsigned long long vm = __ballot(valid);
-        if (vm != 0ull) {   // (wave-uniform)
-            // Lanes without a valid pair compute the first valid lane's pair and drop the result: every index used below is inside
-            // its set, and no branch of the pair routine depends on who is valid.  i, j < 2^32 for a valid pair (gi, gj are u32).
-            const int first = (int)__builtin_ctzll(vm);
-            const uint32_t i0 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)i, first);
-            const uint32_t j0 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)j, first);
-            const uint32_t ia = valid ? (uint32_t)i : i0, jb = valid ? (uint32_t)j : j0;
-            typename S::Obj a, b;
-            if (__ballot(ia != i0) == 0ull)
-                S::load(A, (size_t)i0, a);   // the whole wave is in one row: one wave-uniform index
-            else
-                S::load(A, (size_t)ia, a);
-            S::load(B, (size_t)jb, b);
-            FastPick fast;
-            const bool hit = S::axes(a, b, fast);
-            ContactValue c;
-            float wnx = 0.0f, wny = 0.0f, wlen = 1.0f;   // the winning axis as the rule saw it: raw normal, sqrt(len2), o1 <= o2
-            bool wpos = true;
-            if (fast.decided()) {
-                c = fast.value();
-                if constexpr (kManifold) {
-                    wnx = fast.nx; wny = fast.ny; wlen = __builtin_sqrtf(fast.len2); wpos = fast.pos;
-                }
-            } else {
-                ExactPick exact;
-                (void)S::axes(a, b, exact);
-                c = exact.value();
-                if constexpr (kManifold) {
-                    wnx = exact.nx; wny = exact.ny; wlen = exact.len; wpos = exact.pos;
-                }
-            }
-            if (valid)
-                word = make_uint4(__float_as_uint(c.depth), __float_as_uint(c.nx), __float_as_uint(c.ny), c.axis | (hit ? 1u << 16 : 0u) | (c.flags << 24));
+struct ContactWork {
+    uint4 word = make_uint4(0u, 0u, 0u, kContactNoAxis | ((uint32_t)C2D_CONTACT_BAD_PAIR << 24));   // depth 0, normal (0, 0), hit 0
+    uint4 m0 = make_uint4(0u, 0u, 0u, 0u), m1 = make_uint4(0u, 0u, kManifoldNoFeature, 0u);          // no point, no feature
+    C2D_DEV void pair(const typename S::Obj& a, const typename S::Obj& b, bool valid)
+    {
+        FastPick fast;
+        const bool hit = S::axes(a, b, fast);
+        ContactValue c;
+        float wnx = 0.0f, wny = 0.0f, wlen = 1.0f;   // the winning axis as the rule saw it: raw normal, sqrt(len2), o1 <= o2
+        bool wpos = true;
+        if (fast.decided()) {
+            c = fast.value();
             if constexpr (kManifold) {
-                uint4 v0, v1;
-                poly_manifold(a, b, c.axis, wnx, wny, wlen, wpos, v0, v1);   // (axis 0xFFFF: computes on axis (0, 0) and is dropped)
-                if (valid && c.axis != kContactNoAxis) {
-                    m0 = v0;
-                    m1 = v1;
-                }
+                wnx = fast.nx; wny = fast.ny; wlen = __builtin_sqrtf(fast.len2); wpos = fast.pos;
+            }
+        } else {
+            ExactPick exact;
+            (void)S::axes(a, b, exact);
+            c = exact.value();
+            if constexpr (kManifold) {
+                wnx = exact.nx; wny = exact.ny; wlen = exact.len; wpos = exact.pos;
             }
         }
-        if (in) {
-            reinterpret_cast<uint4*>(out)[p] = word;   // d_out is 16-byte aligned (checked on the host)
-            if constexpr (kManifold) {
-                reinterpret_cast<uint4*>(man)[2 * p] = m0;
-                reinterpret_cast<uint4*>(man)[2 * p + 1] = m1;
+        if (valid)
+            word = make_uint4(__float_as_uint(c.depth), __float_as_uint(c.nx), __float_as_uint(c.ny), c.axis | (hit ? 1u << 16 : 0u) | (c.flags << 24));
+        if constexpr (kManifold) {
+            uint4 v0, v1;
+            poly_manifold(a, b, c.axis, wnx, wny, wlen, wpos, v0, v1);   // (axis 0xFFFF: computes on axis (0, 0) and is dropped)
+            if (valid && c.axis != kContactNoAxis) {
+                m0 = v0;
+                m1 = v1;
             }
         }
     }
-}
+    C2D_DEV void store(size_t p, c2d_contact* __restrict__ out, c2d_manifold* __restrict__ man) const
+    {
+        reinterpret_cast<uint4*>(out)[p] = word;   // d_out is 16-byte aligned (checked on the host)
+        if constexpr (kManifold) {
+            reinterpret_cast<uint4*>(man)[2 * p] = m0;
+            reinterpret_cast<uint4*>(man)[2 * p + 1] = m1;
+        }
+    }
+};
 
 template <class S>
-__global__ __launch_bounds__(kContactBlock) void contact_kernel(typename S::Set A, typename S::Set B, const uint32_t* __restrict__ pairs, size_t n_pairs,
-                                                                const unsigned long long* __restrict__ d_n, size_t row_base, size_t col_base,
-                                                                c2d_contact* __restrict__ out, uint32_t* __restrict__ async_err)
-{
-    contact_pairs<S, false>(A, B, pairs, n_pairs, d_n, row_base, col_base, out, nullptr, async_err);
-}
-
-__global__ __launch_bounds__(kContactBlock) void manifold_kernel(PolySetDev A, PolySetDev B, const uint32_t* __restrict__ pairs, size_t n_pairs,
+__global__ __launch_bounds__(kPairListBlock) void contact_kernel(typename S::Set A, typename S::Set B, const uint32_t* __restrict__ pairs, size_t n_pairs,
                                                                  const unsigned long long* __restrict__ d_n, size_t row_base, size_t col_base,
-                                                                 c2d_contact* __restrict__ out, c2d_manifold* __restrict__ man,
-                                                                 uint32_t* __restrict__ async_err)
+                                                                 c2d_contact* __restrict__ out, uint32_t* __restrict__ async_err)
 {
-    contact_pairs<PolyContactShape, true>(A, B, pairs, n_pairs, d_n, row_base, col_base, out, man, async_err);
+    listed_pairs<S, ContactWork<S, false>>(A, B, pairs, n_pairs, d_n, row_base, col_base, async_err, out, (c2d_manifold*)nullptr);
 }
 
-// the arguments both entry points share, then the launch
-template <class S>
-int contact_run(c2d_ctx* ctx, const char* what, const typename S::Set& A, const typename S::Set& B, const uint32_t* d_pairs, size_t n_pairs,
-                const unsigned long long* d_n_pairs, size_t row_base, size_t col_base, c2d_contact* d_out, c2d_stream stream)
+__global__ __launch_bounds__(kPairListBlock) void manifold_kernel(PolySetDev A, PolySetDev B, const uint32_t* __restrict__ pairs, size_t n_pairs,
+                                                                  const unsigned long long* __restrict__ d_n, size_t row_base, size_t col_base,
+                                                                  c2d_contact* __restrict__ out, c2d_manifold* __restrict__ man,
+                                                                  uint32_t* __restrict__ async_err)
 {
-    if (int rc = cross_check_flags_bases(ctx, what, S::size(A), S::size(B), row_base, col_base, 0)) return rc;
-    if (!d_pairs) return cross_fail(ctx, what, "NULL pair list");
-    if (!d_out) return cross_fail(ctx, what, "NULL output");
-    if (reinterpret_cast<uintptr_t>(d_pairs) & 3u) return cross_fail(ctx, what, "the pair list must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return cross_fail(ctx, what, "the output must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_n_pairs) & 7u) return cross_fail(ctx, what, "d_n_pairs must be 8-byte aligned");
-    if (n_pairs > kBaseLimit) return cross_fail(ctx, what, "n_pairs must stay below 2^62");
-    DeviceGuard dg(ctx->device);
-    hipLaunchKernelGGL(contact_kernel<S>, dim3(grid_for(n_pairs, kContactBlock, kContactMaxGrid)), dim3(kContactBlock), 0, (hipStream_t)stream, A, B, d_pairs,
-                       n_pairs, d_n_pairs, row_base, col_base, d_out, ctx->d_async_err);
-    C2D_LAUNCH_CHECK(ctx);
-    return C2D_OK;
-}
-
-// c2d_poly_pair_manifolds: contact_run's checks with the second output, then the fused launch
-int manifold_run(c2d_ctx* ctx, const char* what, const PolySetDev& A, const PolySetDev& B, const uint32_t* d_pairs, size_t n_pairs,
-                 const unsigned long long* d_n_pairs, size_t row_base, size_t col_base, c2d_contact* d_contacts, c2d_manifold* d_manifolds, c2d_stream stream)
-{
-    if (int rc = cross_check_flags_bases(ctx, what, A.n, B.n, row_base, col_base, 0)) return rc;
-    if (!d_pairs) return cross_fail(ctx, what, "NULL pair list");
-    if (!d_contacts || !d_manifolds) return cross_fail(ctx, what, "NULL output");
-    if (reinterpret_cast<uintptr_t>(d_pairs) & 3u) return cross_fail(ctx, what, "the pair list must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_contacts) | reinterpret_cast<uintptr_t>(d_manifolds)) & 15u)
-        return cross_fail(ctx, what, "both outputs must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_n_pairs) & 7u) return cross_fail(ctx, what, "d_n_pairs must be 8-byte aligned");
-    if (n_pairs > kBaseLimit) return cross_fail(ctx, what, "n_pairs must stay below 2^62");
-    DeviceGuard dg(ctx->device);
-    hipLaunchKernelGGL(manifold_kernel, dim3(grid_for(n_pairs, kContactBlock, kContactMaxGrid)), dim3(kContactBlock), 0, (hipStream_t)stream, A, B, d_pairs,
-                       n_pairs, d_n_pairs, row_base, col_base, d_contacts, d_manifolds, ctx->d_async_err);
-    C2D_LAUNCH_CHECK(ctx);
-    return C2D_OK;
+    listed_pairs<PolyContactShape, ContactWork<PolyContactShape, true>>(A, B, pairs, n_pairs, d_n, row_base, col_base, async_err, out, man);
 }
 
 }  // namespace c2d
@@ -437,47 +325,32 @@ extern "C" {
 int c2d_poly_pair_contacts(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b, const uint32_t* d_pairs, size_t n_pairs,
                            const unsigned long long* d_n_pairs, size_t row_base, size_t col_base, c2d_contact* d_out, c2d_stream stream)
 {
-    const char* what = "c2d_poly_pair_contacts";
-    if (!ctx) return C2D_ERR_INVALID_ARG;
-    if (!a || !b) return cross_fail(ctx, what, "NULL set");
-    if (n_pairs == 0) return C2D_OK;
-    PolySetDev A, B;
-    if (int rc = poly_set_check(ctx, what, "a", a, A)) return rc;
-    if (int rc = poly_set_check(ctx, what, "b", b, B)) return rc;
-    return contact_run<PolyContactShape>(ctx, what, A, B, d_pairs, n_pairs, d_n_pairs, row_base, col_base, d_out, stream);
+    return poly_pair_list_call(ctx, "c2d_poly_pair_contacts", a, b, d_pairs, n_pairs, d_n_pairs, row_base, col_base, {d_out},
+                               [&](const PolySetDev& A, const PolySetDev& B, int grid) {
+                                   hipLaunchKernelGGL(contact_kernel<PolyContactShape>, dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs,
+                                                      n_pairs, d_n_pairs, row_base, col_base, d_out, ctx->d_async_err);
+                               });
 }
 
 int c2d_poly_pair_manifolds(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b, const uint32_t* d_pairs, size_t n_pairs,
                             const unsigned long long* d_n_pairs, size_t row_base, size_t col_base, c2d_contact* d_contacts, c2d_manifold* d_manifolds,
                             c2d_stream stream)
 {
-    const char* what = "c2d_poly_pair_manifolds";
-    if (!ctx) return C2D_ERR_INVALID_ARG;
-    if (!a || !b) return cross_fail(ctx, what, "NULL set");
-    if (n_pairs == 0) return C2D_OK;
-    PolySetDev A, B;
-    if (int rc = poly_set_check(ctx, what, "a", a, A)) return rc;
-    if (int rc = poly_set_check(ctx, what, "b", b, B)) return rc;
-    return manifold_run(ctx, what, A, B, d_pairs, n_pairs, d_n_pairs, row_base, col_base, d_contacts, d_manifolds, stream);
+    return poly_pair_list_call(ctx, "c2d_poly_pair_manifolds", a, b, d_pairs, n_pairs, d_n_pairs, row_base, col_base, {d_contacts, d_manifolds},
+                               [&](const PolySetDev& A, const PolySetDev& B, int grid) {
+                                   hipLaunchKernelGGL(manifold_kernel, dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs, n_pairs,
+                                                      d_n_pairs, row_base, col_base, d_contacts, d_manifolds, ctx->d_async_err);
+                               });
 }
 
 int c2d_rect_pair_contacts(c2d_ctx* ctx, const float* const d_a[8], size_t n_a, const float* const d_b[8], size_t n_b, const uint32_t* d_pairs,
                            size_t n_pairs, const unsigned long long* d_n_pairs, size_t row_base, size_t col_base, c2d_contact* d_out, c2d_stream stream)
 {
-    const char* what = "c2d_rect_pair_contacts";
-    if (!ctx) return C2D_ERR_INVALID_ARG;
-    if (!d_a || !d_b) return cross_fail(ctx, what, "NULL argument");
-    if (n_pairs == 0) return C2D_OK;
-    RectContactSet A, B;
-    A.n = n_a;
-    B.n = n_b;
-    for (int k = 0; k < 8; k++) {
-        if (!d_a[k] || !d_b[k]) return cross_fail(ctx, what, "NULL plane");
-        if ((reinterpret_cast<uintptr_t>(d_a[k]) | reinterpret_cast<uintptr_t>(d_b[k])) & 3u) return cross_fail(ctx, what, "planes must be 4-byte aligned");
-        A.p[k] = d_a[k];
-        B.p[k] = d_b[k];
-    }
-    return contact_run<RectContactShape>(ctx, what, A, B, d_pairs, n_pairs, d_n_pairs, row_base, col_base, d_out, stream);
+    return rect_pair_list_call(ctx, "c2d_rect_pair_contacts", d_a, n_a, d_b, n_b, d_pairs, n_pairs, d_n_pairs, row_base, col_base, {d_out},
+                               [&](const RectListSet& A, const RectListSet& B, int grid) {
+                                   hipLaunchKernelGGL(contact_kernel<RectContactShape>, dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs,
+                                                      n_pairs, d_n_pairs, row_base, col_base, d_out, ctx->d_async_err);
+                               });
 }
 
 }  // extern "C"

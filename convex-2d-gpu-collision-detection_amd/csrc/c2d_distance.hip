@@ -1,0 +1,183 @@
+// c2d_distance.hip — distance queries for gfx950 (MI355X): for each listed pair (A_i, B_j) the boolean of the pairwise test and, when
+// the pair is separated, the Euclidean distance of the two shapes with the two points that realise it (c2d_poly_pair_distances,
+// c2d_rect_pair_distances; include/c2d.h "distance queries").
+//
+// The rule (the contract of include/c2d.h).  A candidate is an edge of one shape and a vertex of the other: side 0 takes A's edges
+// e = 0 .. ka - 1 against B's vertices v = 0 .. kb - 1, side 1 B's edges against A's vertices.  Per candidate, with the edge
+// (x0, y0) -> (x1, y1) and the vertex (xp, yp), everything binary32 and unfused:
+//     ex = x1 - x0, ey = y1 - y0, qx = xp - x0, qy = yp - y0, len2 = ex * ex + ey * ey, s = qx * ex + qy * ey
+//     region 0: s <= 0: c = (x0, y0);  region 1: else s >= len2: c = (x1, y1);  region 2: else t = s / len2, c = (x0 + t * ex, y0 + t * ey)
+//     d2 = (xp - cx)^2 + (yp - cy)^2; unusable when d2 is NaN.
+// In the order side, e, v the first usable candidate is the first best and a later one replaces it only under strict d2 < best.
+//
+// One pair per lane on the frame of c2d_pair_list.hpp.  The lanes of a wave hold unrelated pairs, so the vertices stay in registers
+// and every vertex index is a compile-time slot: the sweep always works on the edge from slot 0 to slot 1 of the edge polygon and
+// turns that polygon by one slot per trip, so the edge loop stays rolled (one body of K candidates instead of K * K) and the polygon
+// is back in place after K trips.  poly_load's padding repeats vertex 0, which closes the polygon for free: slot k is vertex 0, and
+// slot 16 is slot 0.  The padding is NOT neutral otherwise: a padded candidate reaches vertex 0 directly, a real one reaches the
+// same point through t, and the two d2 can differ by a rounding — so slots with e >= k or v >= k are masked out of the pick.
+#include "c2d_pair_list.hpp"
+
+namespace c2d {
+
+static_assert(sizeof(c2d_distance) == 32 && offsetof(c2d_distance, ax) == 4 && offsetof(c2d_distance, bx) == 12 && offsetof(c2d_distance, by) == 16 &&
+                  offsetof(c2d_distance, edge) == 20 && offsetof(c2d_distance, vert) == 22 && offsetof(c2d_distance, hit) == 24 &&
+                  offsetof(c2d_distance, flags) == 25 && offsetof(c2d_distance, reserved0) == 26 && offsetof(c2d_distance, reserved1) == 28,
+              "the kernel stores a distance as two halves of four dwords");
+
+constexpr uint32_t kDistanceNone = 0xFFFFFFFFu;   // edge = vert = 0xFFFF
+constexpr uint32_t kDistanceInterior = 1u << 8, kDistanceSide1 = 1u << 9;   // in DistancePick::code
+
+// The sequential pick.  code = v | e << 4 | (region 2) << 8 | side << 9 of the best candidate so far; kDistanceNone: none yet.
+struct DistancePick {
+    float best = __builtin_inff(), cx = 0.0f, cy = 0.0f, px = 0.0f, py = 0.0f;   // d2, the closest point on the edge, the vertex
+    uint32_t code = kDistanceNone;
+};
+
+// One side: the kp edges of P against the kq vertices of Q, in the order e, v.  P is turned by one slot per trip and ends as it began.
+template <int K>
+C2D_DEV void distance_side(float (&px)[K], float (&py)[K], int kp, const float (&qx)[K], const float (&qy)[K], int kq, uint32_t side_bits, DistancePick& pick)
+{
+    constexpr int kEdgeUnroll = K <= 4 ? K : 1;   // rectangles: 16 candidates per side, flat; polygons: one body of 16 per trip
+#pragma unroll kEdgeUnroll
+    for (int e = 0; e < K; e++) {
+        const float x0 = px[0], y0 = py[0], x1 = px[1], y1 = py[1];
+        const float ex = x1 - x0, ey = y1 - y0;
+        const float len2 = ex * ex + ey * ey;
+        const bool live_e = e < kp;
+        const uint32_t code_e = side_bits | ((uint32_t)e << 4);
+#pragma unroll
+        for (int v = 0; v < K; v++) {
+            const float xq = qx[v], yq = qy[v];
+            const float ux = xq - x0, uy = yq - y0;
+            const float s = ux * ex + uy * ey;
+            const bool r0 = s <= 0.0f, r1 = s >= len2;   // (region 0 first; a NaN s fails both and takes region 2)
+            const float t = s / len2;
+            const float tx = x0 + t * ex, ty = y0 + t * ey;
+            const float cx = r0 ? x0 : (r1 ? x1 : tx), cy = r0 ? y0 : (r1 ? y1 : ty);
+            const float dx = xq - cx, dy = yq - cy;
+            const float d2 = dx * dx + dy * dy;
+            const bool take = live_e && v < kq && !__builtin_isnan(d2) && (pick.code == kDistanceNone || d2 < pick.best);
+            pick.best = take ? d2 : pick.best;
+            pick.cx = take ? cx : pick.cx;
+            pick.cy = take ? cy : pick.cy;
+            pick.px = take ? xq : pick.px;
+            pick.py = take ? yq : pick.py;
+            pick.code = take ? (code_e | (uint32_t)v | ((r0 || r1) ? 0u : kDistanceInterior)) : pick.code;
+        }
+        const float fx = px[0], fy = py[0];
+#pragma unroll
+        for (int r = 0; r + 1 < K; r++) {
+            px[r] = px[r + 1];
+            py[r] = py[r + 1];
+        }
+        px[K - 1] = fx;
+        py[K - 1] = fy;
+    }
+}
+
+// Both sides of one pair to the record's two halves: d0 = {dist, ax, ay, bx}, d1 = {by, edge | vert << 16, hit | flags << 8, 0}.
+template <int K>
+C2D_DEV void distance_record(float (&ax)[K], float (&ay)[K], int ka, float (&bx)[K], float (&by)[K], int kb, uint4& d0, uint4& d1)
+{
+    DistancePick pick;
+    distance_side<K>(ax, ay, ka, bx, by, kb, 0u, pick);
+    distance_side<K>(bx, by, kb, ax, ay, ka, kDistanceSide1, pick);
+    if (pick.code == kDistanceNone) {
+        d0 = make_uint4(__float_as_uint(__builtin_inff()), 0u, 0u, 0u);
+        d1 = make_uint4(0u, kDistanceNone, (uint32_t)C2D_DISTANCE_NO_CANDIDATE << 8, 0u);
+        return;
+    }
+    const bool on_b = (pick.code & kDistanceSide1) != 0u;
+    const uint32_t flags = (on_b ? (uint32_t)C2D_DISTANCE_EDGE_ON_B : 0u) | ((pick.code & kDistanceInterior) ? (uint32_t)C2D_DISTANCE_INTERIOR : 0u);
+    const float pax = on_b ? pick.px : pick.cx, pay = on_b ? pick.py : pick.cy, pbx = on_b ? pick.cx : pick.px, pby = on_b ? pick.cy : pick.py;
+    d0 = make_uint4(__float_as_uint(__builtin_sqrtf(pick.best)), __float_as_uint(pax), __float_as_uint(pay), __float_as_uint(pbx));
+    d1 = make_uint4(__float_as_uint(pby), ((pick.code >> 4) & 15u) | ((pick.code & 15u) << 16), flags << 8, 0u);
+}
+
+// The shapes of c2d_pair_list.hpp with what the distance kernel adds:
+//   S::collide(a, b)             the pairwise boolean of the pair
+//   S::record(a, b, d0, d1)      the record of a pair that is not hit (a and b are turned and restored)
+struct PolyDistanceShape : PolyListShape {
+    static C2D_DEV bool collide(const Obj& a, const Obj& b) { return poly_collide(a, b); }
+    static C2D_DEV void record(Obj& a, Obj& b, uint4& d0, uint4& d1) { distance_record<C2D_POLY_KMAX>(a.x, a.y, a.k, b.x, b.y, b.k, d0, d1); }
+};
+
+struct RectDistanceShape : RectListShape {
+    static C2D_DEV bool collide(const Obj& a, const Obj& b) { return rect_collide(a.r, b.r); }
+    static C2D_DEV void record(Obj& a, Obj& b, uint4& d0, uint4& d1)
+    {
+        float ax[4], ay[4], bx[4], by[4];
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+            ax[v] = a.r[2 * v]; ay[v] = a.r[2 * v + 1];
+            bx[v] = b.r[2 * v]; by[v] = b.r[2 * v + 1];
+        }
+        distance_record<4>(ax, ay, 4, bx, by, 4, d0, d1);
+    }
+};
+
+// The query of listed_pairs: starts as the BAD_PAIR record; a hit pair gets {0, (0, 0), (0, 0), 0xFFFF, 0xFFFF, 1, 0}.
+template <class S>
+struct DistanceWork {
+    uint4 d0 = make_uint4(0u, 0u, 0u, 0u), d1 = make_uint4(0u, kDistanceNone, (uint32_t)C2D_DISTANCE_BAD_PAIR << 8, 0u);
+    C2D_DEV void pair(const typename S::Obj& a_in, const typename S::Obj& b_in, bool valid)
+    {
+        const bool hit = S::collide(a_in, b_in);
+        uint4 v0 = make_uint4(0u, 0u, 0u, 0u), v1 = make_uint4(0u, kDistanceNone, 1u, 0u);
+        if (__ballot(valid && !hit) != 0ull) {   // (wave-uniform) a wave all of whose pairs are hit has no candidate to look at
+            typename S::Obj a = a_in, b = b_in;
+            uint4 s0, s1;
+            S::record(a, b, s0, s1);
+            if (!hit) {
+                v0 = s0;
+                v1 = s1;
+            }
+        }
+        if (valid) {
+            d0 = v0;
+            d1 = v1;
+        }
+    }
+    C2D_DEV void store(size_t p, c2d_distance* __restrict__ out) const
+    {
+        reinterpret_cast<uint4*>(out)[2 * p] = d0;   // d_out is 16-byte aligned (checked on the host)
+        reinterpret_cast<uint4*>(out)[2 * p + 1] = d1;
+    }
+};
+
+template <class S>
+__global__ __launch_bounds__(kPairListBlock) void distance_kernel(typename S::Set A, typename S::Set B, const uint32_t* __restrict__ pairs, size_t n_pairs,
+                                                                  const unsigned long long* __restrict__ d_n, size_t row_base, size_t col_base,
+                                                                  c2d_distance* __restrict__ out, uint32_t* __restrict__ async_err)
+{
+    listed_pairs<S, DistanceWork<S>>(A, B, pairs, n_pairs, d_n, row_base, col_base, async_err, out);
+}
+
+}  // namespace c2d
+
+using namespace c2d;
+
+extern "C" {
+
+int c2d_poly_pair_distances(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b, const uint32_t* d_pairs, size_t n_pairs,
+                            const unsigned long long* d_n_pairs, size_t row_base, size_t col_base, c2d_distance* d_out, c2d_stream stream)
+{
+    return poly_pair_list_call(ctx, "c2d_poly_pair_distances", a, b, d_pairs, n_pairs, d_n_pairs, row_base, col_base, {d_out},
+                               [&](const PolySetDev& A, const PolySetDev& B, int grid) {
+                                   hipLaunchKernelGGL(distance_kernel<PolyDistanceShape>, dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs,
+                                                      n_pairs, d_n_pairs, row_base, col_base, d_out, ctx->d_async_err);
+                               });
+}
+
+int c2d_rect_pair_distances(c2d_ctx* ctx, const float* const d_a[8], size_t n_a, const float* const d_b[8], size_t n_b, const uint32_t* d_pairs,
+                            size_t n_pairs, const unsigned long long* d_n_pairs, size_t row_base, size_t col_base, c2d_distance* d_out, c2d_stream stream)
+{
+    return rect_pair_list_call(ctx, "c2d_rect_pair_distances", d_a, n_a, d_b, n_b, d_pairs, n_pairs, d_n_pairs, row_base, col_base, {d_out},
+                               [&](const RectListSet& A, const RectListSet& B, int grid) {
+                                   hipLaunchKernelGGL(distance_kernel<RectDistanceShape>, dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs,
+                                                      n_pairs, d_n_pairs, row_base, col_base, d_out, ctx->d_async_err);
+                               });
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Developer tool: the contact queries (c2d_poly_pair_contacts / c2d_rect_pair_contacts, and c2d_poly_pair_manifolds) next to the list calls that feed them, one
-JSON line per configuration.  GPU only, no oracle (tests/test_gpu_contacts.py checks the values).
+"""Developer tool: the contact queries (c2d_poly_pair_contacts / c2d_rect_pair_contacts, and c2d_poly_pair_manifolds) and the distance queries
+(c2d_poly_pair_distances / c2d_rect_pair_distances) next to the list calls that feed them, one JSON line per configuration.  GPU only, no oracle (tests/test_gpu_contacts.py checks the values).
 
 Scenes: the sparse self-collision scenes of poly_broad_bench.py (K ~ U{3..16}, extent 200 * sqrt(N / 32768)) and broad_bench.py
 (rectangles of random_obb_pose_planes at the same density), C2D_CROSS_UPPER with B = A; and one dense polygon list of about 1e7
@@ -12,6 +12,9 @@ median of --reps (>= 7) after a warm-up:
   contacts_per_s  listed pairs / contacts_ms;   hits: the list's length
   manifolds_ms    (polygon scenes) c2d_poly_pair_manifolds alone on the same list in the same run; manifolds_over_contacts is its
                   ratio to contacts_ms — the contacts call is the yardstick
+  distances_ms    the distances call alone on the same list in the same run; distances_over_contacts its ratio to contacts_ms,
+                  distances_per_s listed pairs / distances_ms, separated_share the share of the list that is not hit (a wave of
+                  hit pairs skips the candidate loops: the broad lists are all hit, the dense list is mostly separated)
 The kernels' own times come from a separate run under `rocprofv3 --kernel-trace --stats -- python3 contact_bench.py --once`.
 usage: contact_bench.py [--n 131072] [--dense-n 3163] [--reps 7] [--once]"""
 import argparse
@@ -58,7 +61,7 @@ def main():
             ms.append(e0.elapsed_time(e1))
         return float(np.median(ms))
 
-    def report(config, n, list_call, contacts_call, total, extra=None, manifolds_call=None):
+    def report(config, n, list_call, contacts_call, total, extra=None, manifolds_call=None, distances_call=None, distances_out=None):
         def both():
             if list_call is not None:
                 list_call()
@@ -68,6 +71,8 @@ def main():
             both()
             if manifolds_call is not None:
                 manifolds_call()
+            if distances_call is not None:
+                distances_call()
             stream.synchronize()
             return
         out = {"config": config, "n": n, "hits": total, "reps": reps}
@@ -80,6 +85,12 @@ def main():
         if manifolds_call is not None:
             out["manifolds_ms"] = round(timed(manifolds_call), 4)
             out["manifolds_over_contacts"] = round(out["manifolds_ms"] / out["contacts_ms"], 3)
+        if distances_call is not None:
+            out["distances_ms"] = round(timed(distances_call), 4)
+            out["distances_over_contacts"] = round(out["distances_ms"] / out["contacts_ms"], 3)
+            out["distances_per_s"] = round(total / (out["distances_ms"] * 1e-3), 0)
+            if total:     # byte 24 of a record is `hit`
+                out["separated_share"] = round(1.0 - float(distances_out[:total, 24].float().mean().item()), 4)
         out.update(extra or {})
         print(json.dumps(out), flush=True)
 
@@ -108,11 +119,16 @@ def main():
     def poly_manifolds():
         eng.poly_pair_manifolds(s, s, pairs.data_ptr(), total, out.data_ptr(), man.data_ptr(), n_pairs_dev=cnt.data_ptr(), stream=sh)
 
+    dist = torch.empty((max(total, 1), 32), dtype=torch.uint8, device=dev)
+
+    def poly_distances():
+        eng.poly_pair_distances(s, s, pairs.data_ptr(), total, dist.data_ptr(), n_pairs_dev=cnt.data_ptr(), stream=sh)
+
     poly_list()
-    report("sparse_polygons_self_upper", n, poly_list, poly_contacts, total, {"extent": round(float(extent), 2)}, poly_manifolds)
+    report("sparse_polygons_self_upper", n, poly_list, poly_contacts, total, {"extent": round(float(extent), 2)}, poly_manifolds, poly_distances, dist)
     hit_share = float((out.view(torch.int32)[:total, 3] >> 16 & 1).float().mean().item()) if total and not args.once else None
     assert hit_share in (None, 1.0), "a listed pair without `hit`"
-    del pairs, out, man
+    del pairs, out, man, dist
 
     # -- sparse rectangles, self-collision -------------------------------------------------------------------------------
     poses = wl.random_obb_pose_planes(n, seed=0xB0AD, extent=extent)
@@ -134,9 +150,14 @@ def main():
     def rect_contacts():
         eng.rect_pair_contacts(pp, n, pp, n, rpairs.data_ptr(), rtotal, rout.data_ptr(), n_pairs_dev=cnt.data_ptr(), stream=sh)
 
+    rdist = torch.empty((max(rtotal, 1), 32), dtype=torch.uint8, device=dev)
+
+    def rect_distances():
+        eng.rect_pair_distances(pp, n, pp, n, rpairs.data_ptr(), rtotal, rdist.data_ptr(), n_pairs_dev=cnt.data_ptr(), stream=sh)
+
     rect_list()
-    report("sparse_rectangles_self_upper", n, rect_list, rect_contacts, rtotal, {"extent": round(float(extent), 2)})
-    del rpairs, rout
+    report("sparse_rectangles_self_upper", n, rect_list, rect_contacts, rtotal, {"extent": round(float(extent), 2)}, None, rect_distances, rdist)
+    del rpairs, rout, rdist
 
     # -- one dense polygon list: every pair of two sets ------------------------------------------------------------------
     m = args.dense_n
@@ -156,7 +177,10 @@ def main():
     def dense_manifolds():
         eng.poly_pair_manifolds(sa, sb, dense.data_ptr(), m * m, dout.data_ptr(), dman.data_ptr(), stream=sh)
 
-    report("dense_polygon_list", m, None, dense_contacts, m * m, None, dense_manifolds)
+    def dense_distances():      # (into the manifolds' buffer: the same 32 bytes per entry, and the manifolds leg is over by then)
+        eng.poly_pair_distances(sa, sb, dense.data_ptr(), m * m, dman.data_ptr(), stream=sh)
+
+    report("dense_polygon_list", m, None, dense_contacts, m * m, None, dense_manifolds, dense_distances, dman)
     eng.check_async()
     eng.close()
 

@@ -511,6 +511,70 @@ int c2d_poly_pair_manifolds(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_
                             size_t row_base, size_t col_base,
                             c2d_contact* d_contacts, c2d_manifold* d_manifolds, c2d_stream stream);
 
+/* ---- distance queries: separation and closest points for listed pairs -------------
+ * Additions to 0.6 (c2d_version() stays 6), found by symbol lookup like the contact calls.
+ *
+ * c2d_poly_pair_distances / c2d_rect_pair_distances: for each pair of a list the boolean of the pairwise test and, when the pair is
+ * not hit, how far apart the two shapes are and which two points realise that distance.  (A contact's -depth is only a lower bound
+ * of it: when the closest features are two vertices, no axis of the pairwise test gives the distance.)  The sets, d_pairs,
+ * d_n_pairs, the bases, the records at or beyond min(n_pairs, *d_n_pairs) (untouched), bad pairs, the asynchronous error word,
+ * n_pairs == 0 (a no-op), the refused arguments (NULL, a misaligned output, n_pairs >= 2^62, ...; refused before a device is
+ * touched), "no ctx scratch", the single launch and graph capture are those of c2d_poly_pair_contacts / c2d_rect_pair_contacts.
+ *   d_out : c2d_distance[n_pairs], 16-byte aligned; entry p is the distance record of list entry p.
+ *
+ * Arithmetic contract.  Everything is IEEE binary32, round to nearest, subnormals kept, nothing contracted in any
+ * build; division and square root are correctly rounded.
+ *   hit         the pairwise boolean itself (c2d_sat_poly_pairs_rows / c2d_sat_rect_pairs_verts of the same build on the pair), for
+ *               every input bit pattern: exactly the `hit` of the contact calls.  When hit: dist = 0, both points (0, 0),
+ *               edge = vert = 0xFFFF, flags = 0 (how deep is the contact calls' business).
+ *   candidates  when not hit, the result is the minimum over candidates (edge, vertex).  Side 0: edge e of A (e = 0..ka-1, from
+ *               vertex e to vertex (e + 1) mod ka) against vertex v of B (v = 0..kb-1).  Side 1: edge e of B against vertex v of A.
+ *               Rectangles are the four vertices of their planes, k = 4.
+ *   per candidate, the edge running (x0, y0) -> (x1, y1) and the vertex being (xp, yp):
+ *               ex = x1 - x0, ey = y1 - y0, qx = xp - x0, qy = yp - y0, len2 = ex * ex + ey * ey, s = qx * ex + qy * ey.
+ *               Region 0: if s <= 0 the closest point (cx, cy) is (x0, y0) itself.  Region 1: else if s >= len2 it is (x1, y1)
+ *               itself.  Region 2: else t = s / len2, cx = x0 + t * ex, cy = y0 + t * ey (product, then sum).
+ *               dx = xp - cx, dy = yp - cy, d2 = dx * dx + dy * dy.  A NaN s fails both compares and reaches region 2, so d2 is
+ *               NaN.  A candidate is unusable when d2 is NaN; a d2 of +inf is usable.  A zero-length edge always lands in region 0
+ *               or 1, so nothing divides by zero.
+ *   the pick    candidates are taken in the order side, then e, then v.  The first usable one is the first best; a later one
+ *               replaces it only under strict d2 < best (compare and select, not fmin).  Equivalently: the smallest d2 wins, and
+ *               among equal d2 the smallest side * 256 + e * 16 + v.  Exact ties are the rule, not the exception: every
+ *               vertex-to-vertex minimum is reached by up to four candidates with the same bits.
+ *   the record  dist = sqrt(best), edge = e, vert = v.  On side 0 the closest point goes to (ax, ay) and the vertex to (bx, by); on
+ *               side 1 it is the other way round and C2D_DISTANCE_EDGE_ON_B is set.  C2D_DISTANCE_INTERIOR is set in region 2.
+ *               No usable candidate: dist = +inf, points (0, 0), edge = vert = 0xFFFF, C2D_DISTANCE_NO_CANDIDATE.  A bad pair (as
+ *               for the contact calls): everything 0, edge = vert = 0xFFFF, C2D_DISTANCE_BAD_PAIR.
+ * The implementation may evaluate candidates in another order; its results equal this sequential rule.  +0 and -0 compare equal
+ * in the five floats.  For disjoint convex polygons this minimum is the Euclidean distance of the two polygons, and the two points
+ * are a closest pair.  For non-convex input nothing is promised about what the numbers mean, only their bits. */
+#define C2D_DISTANCE_EDGE_ON_B    1  /* the winning edge belongs to B and the vertex to A (side 1) */
+#define C2D_DISTANCE_INTERIOR     2  /* the closest point lies strictly inside the edge (region 2) */
+#define C2D_DISTANCE_NO_CANDIDATE 4  /* not hit, and no usable candidate: dist = +inf */
+#define C2D_DISTANCE_BAD_PAIR     8  /* as C2D_CONTACT_BAD_PAIR */
+
+typedef struct c2d_distance {   /* 32 bytes, 16-byte aligned output */
+    float    dist;              /*  0: Euclidean distance; 0 when hit */
+    float    ax, ay;            /*  4: the closest point on A */
+    float    bx, by;            /* 12: the closest point on B */
+    uint16_t edge;              /* 20: index of the winning edge in its own polygon (0..k-1); 0xFFFF: none */
+    uint16_t vert;              /* 22: index of the winning vertex in the other polygon; 0xFFFF: none */
+    uint8_t  hit;               /* 24: the pairwise boolean, for every input bit pattern */
+    uint8_t  flags;             /* 25 */
+    uint16_t reserved0;         /* 26: written as 0 */
+    uint32_t reserved1;         /* 28: written as 0 */
+} c2d_distance;
+
+int c2d_poly_pair_distances(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b,
+                            const uint32_t* d_pairs, size_t n_pairs, const unsigned long long* d_n_pairs,
+                            size_t row_base, size_t col_base,
+                            c2d_distance* d_out, c2d_stream stream);
+
+int c2d_rect_pair_distances(c2d_ctx* ctx, const float* const d_a[8], size_t n_a, const float* const d_b[8], size_t n_b,
+                            const uint32_t* d_pairs, size_t n_pairs, const unsigned long long* d_n_pairs,
+                            size_t row_base, size_t col_base,
+                            c2d_distance* d_out, c2d_stream stream);
+
 /* ---- binned polygon batches ---------------------------------------------------
  * The padded layout above moves 16 vertex rows per polygon whatever the polygons are: with
  * K ~ U{3..16} that is 259 bytes per pair for 155 bytes of real vertices, and no kernel can
