@@ -1,6 +1,7 @@
-"""Inputs shared by the contact tests (test_contact_ref_cpu.py, test_contact_near_ties_cpu.py, test_gpu_contacts.py,
-test_gpu_contact_ties.py) and tests/tools/contact_fuzz.py: seeded sets and pair lists only, no expectations.  A polygon set is
-(vx f32[rows][n], vy, k u8[n]); a rectangle set is planes f32[8][n]."""
+"""Inputs shared by the tests of the list-driven queries (test_contact_ref_cpu.py, test_contact_near_ties_cpu.py, pair_list_harness.py
+with its dense sets and hard batches, test_gpu_pair_list_contract.py, pair_list_graph_check.py, test_gpu_contacts.py,
+test_gpu_contact_ties.py, test_gpu_manifolds.py, test_gpu_distances.py) and tests/tools/contact_fuzz.py: seeded sets and pair lists
+only, no expectations.  A polygon set is (vx f32[rows][n], vy, k u8[n]); a rectangle set is planes f32[8][n]."""
 import numpy as np
 
 F = np.float32

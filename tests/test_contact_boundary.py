@@ -83,7 +83,7 @@ def test_null_and_bad_arguments_are_rejected_without_a_device(pkg):
     assert poly(None, None, None, None, 0, None, 0, 0, None, None) == -1
     assert rect(None, None, 0, None, 0, None, 0, None, 0, 0, None, None) == -1
     assert poly(None, C.byref(s), C.byref(s), p, 4, None, 0, 0, C.c_void_p(0x2008), None) == -1   # (a misaligned output too)
-    # (with a ctx, every other refusal is checked on the GPU: tests/test_gpu_contacts.py::test_argument_errors)
+    # (with a ctx, every other refusal is checked on the GPU: tests/test_gpu_pair_list_contract.py::test_argument_errors[contacts])
 
 
 def test_host_conveniences_check_their_shapes_before_touching_a_device(pkg, wl):

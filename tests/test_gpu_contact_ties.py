@@ -15,26 +15,11 @@ sys.path.insert(0, HERE)
 import contact_cases as cases  # noqa: E402
 import contact_ref as ref  # noqa: E402
 import contact_bands as ties  # noqa: E402
-import test_gpu_contacts as base  # noqa: E402   (the upload, run() with its guard bands, the comparisons)
+import pair_list_harness as h  # noqa: E402   (the upload, run() with its guard bands, the comparisons)
 
 pytestmark = pytest.mark.gpu
 FUZZ_SEED = 20262
-
-
-def diagonal(n):
-    return np.stack([np.arange(n), np.arange(n)], axis=1).astype(np.uint32)
-
-
-def rect_pairwise_gpu(eng, a, b, pairs):
-    """the boolean of c2d_sat_rect_pairs_verts on the listed pairs"""
-    i, j = base.local(pairs)
-    d = eng.to_device(np.concatenate([a[:, i], b[:, j]]))
-    d_out = eng.zeros(len(pairs), np.uint8)
-    eng.sat_rect_pairs_verts([d.row(k) for k in range(16)], len(pairs), d_out)
-    out = d_out.get()
-    d.free()
-    d_out.free()
-    return out
+Q = h.CONTACTS
 
 
 def assert_same_by_band(got, want, terms, what):
@@ -55,31 +40,31 @@ def test_near_ties(eng, oracle):
     qa, qb = cases.near_tie_quad_sets()
     for name, a, b in (("polygons", pa, pb), ("boxes as 4-gons", ba, bb)):
         n = a[0].shape[1]
-        pairs = diagonal(n)
+        pairs = h.diag(n)
         idx = np.arange(n)
         want, terms = ref.poly_contacts(a, b, idx, idx), ref.poly_axis_terms(a, b, idx, idx)
-        assert np.array_equal(want["hit"], base.oracle_hits(oracle, a, b, pairs))
-        ua, ub = base.Uploaded(eng, a), base.Uploaded(eng, b)
-        got = base.run(eng, base.poly_call(eng, ua.set, ub.set), pairs)
+        assert np.array_equal(want["hit"], h.oracle_hits(oracle, a, b, pairs))
+        ua, ub = h.Uploaded(eng, a), h.Uploaded(eng, b)
+        got = Q.run(eng, Q.poly_call(eng, ua.set, ub.set), pairs)
         assert_same_by_band(got, want, terms, name)
-        assert np.array_equal(got["hit"], base.pairwise_gpu(eng, a, b, pairs)), name
+        assert np.array_equal(got["hit"], h.pairwise_gpu(eng, a, b, pairs)), name
         order = np.random.default_rng(8301).permutation(n)
-        got = base.run(eng, base.poly_call(eng, ua.set, ub.set), pairs[order])
+        got = Q.run(eng, Q.poly_call(eng, ua.set, ub.set), pairs[order])
         assert_same_by_band(got, want[order], {f: terms[f][order] for f in terms}, name + ", shuffled")
         ua.free()
         ub.free()
     for name, a, b in (("boxes", bra, brb), ("quads", qa, qb)):
         n = a.shape[1]
-        pairs = diagonal(n)
+        pairs = h.diag(n)
         idx = np.arange(n)
         want, terms = ref.rect_contacts(a, b, idx, idx), ref.rect_axis_terms(a, b, idx, idx)
         assert np.array_equal(want["hit"], oracle.sat_rect_pairs_verts(np.concatenate([a, b]))[0])
-        da, db = base.RectsOnDevice(eng, a), base.RectsOnDevice(eng, b)
-        got = base.run(eng, base.rect_call(eng, da, db), pairs)
+        da, db = h.RectsOnDevice(eng, a), h.RectsOnDevice(eng, b)
+        got = Q.run(eng, Q.rect_call(eng, da, db), pairs)
         assert_same_by_band(got, want, terms, name)
-        assert np.array_equal(got["hit"], rect_pairwise_gpu(eng, a, b, pairs)), name
+        assert np.array_equal(got["hit"], h.rect_pairwise_gpu(eng, a, b, pairs)), name
         order = np.random.default_rng(8302).permutation(n)
-        got = base.run(eng, base.rect_call(eng, da, db), pairs[order])
+        got = Q.run(eng, Q.rect_call(eng, da, db), pairs[order])
         assert_same_by_band(got, want[order], {f: terms[f][order] for f in terms}, name + ", shuffled")
         da.free()
         db.free()
@@ -98,24 +83,24 @@ def test_window_edges(eng, oracle, wl):
     """The 48 x 48 polygon batch of the hard inputs and 200 rectangles per set, multiplied exactly by 2^k for k in -54 .. -46,
     26 .. 32 and 46 .. 54: len2 crosses 2^-100 and 2^100 and |o| crosses 2^60 pair by pair (the CPU file asserts the shares)."""
     a, b, pairs, k = cases.window_edge_poly_batch(wl)
-    want = ref.poly_contacts(a, b, *base.local(pairs))
-    ua, ub = base.Uploaded(eng, a), base.Uploaded(eng, b)
-    got = base.run(eng, base.poly_call(eng, ua.set, ub.set), pairs)
+    want = ref.poly_contacts(a, b, *h.local(pairs))
+    ua, ub = h.Uploaded(eng, a), h.Uploaded(eng, b)
+    got = Q.run(eng, Q.poly_call(eng, ua.set, ub.set), pairs)
     ua.free()
     ub.free()
     assert_same_by_scale(got, want, k, "polygons")
-    assert np.array_equal(got["hit"], base.oracle_hits(oracle, a, b, pairs))
-    assert np.array_equal(got["hit"], base.pairwise_gpu(eng, a, b, pairs))
+    assert np.array_equal(got["hit"], h.oracle_hits(oracle, a, b, pairs))
+    assert np.array_equal(got["hit"], h.pairwise_gpu(eng, a, b, pairs))
     ra, rb, pairs, k = cases.window_edge_rect_batch(oracle, wl)
-    i, j = base.local(pairs)
+    i, j = h.local(pairs)
     want = ref.rect_contacts(ra, rb, i, j)
-    da, db = base.RectsOnDevice(eng, ra), base.RectsOnDevice(eng, rb)
-    got = base.run(eng, base.rect_call(eng, da, db), pairs)
+    da, db = h.RectsOnDevice(eng, ra), h.RectsOnDevice(eng, rb)
+    got = Q.run(eng, Q.rect_call(eng, da, db), pairs)
     da.free()
     db.free()
     assert_same_by_scale(got, want, k, "rectangles")
     assert np.array_equal(got["hit"], oracle.sat_rect_pairs_verts(np.concatenate([ra[:, i], rb[:, j]]))[0])
-    assert np.array_equal(got["hit"], rect_pairwise_gpu(eng, ra, rb, pairs))
+    assert np.array_equal(got["hit"], h.rect_pairwise_gpu(eng, ra, rb, pairs))
     eng.check_async()
 
 
@@ -125,17 +110,17 @@ def test_mixed_scales_in_one_wave(eng, oracle, wl):
     the list cut by the device count five entries into a wave, for eleven waves: the lanes beyond the count compute the pair of the
     wave's first lane, which is of each of the eleven kinds in turn."""
     a, b, pairs, k = cases.mixed_scale_poly_batch(wl)
-    want = ref.poly_contacts(a, b, *base.local(pairs))
-    ua, ub = base.Uploaded(eng, a), base.Uploaded(eng, b)
-    got = base.run(eng, base.poly_call(eng, ua.set, ub.set), pairs)
+    want = ref.poly_contacts(a, b, *h.local(pairs))
+    ua, ub = h.Uploaded(eng, a), h.Uploaded(eng, b)
+    got = Q.run(eng, Q.poly_call(eng, ua.set, ub.set), pairs)
     assert_same_by_scale(got, want, k, "mixed scales")
-    assert np.array_equal(got["hit"], base.oracle_hits(oracle, a, b, pairs))
-    assert np.array_equal(got["hit"], base.pairwise_gpu(eng, a, b, pairs))
+    assert np.array_equal(got["hit"], h.oracle_hits(oracle, a, b, pairs))
+    assert np.array_equal(got["hit"], h.pairwise_gpu(eng, a, b, pairs))
     waves = 64 * np.arange(1, (len(pairs) - 5) // 64)
     assert set(k[waves].tolist()) == set(cases.MIXED_SCALE_K), "a scale begins no wave of the list: the cut lists below would miss it"
     starts = [int(waves[k[waves] == kk][0]) for kk in cases.MIXED_SCALE_K]      # per kind, the first wave that begins with it
     for s in starts:
-        got = base.run(eng, base.poly_call(eng, ua.set, ub.set), pairs, n_dev=int(s) + 5)
+        got = Q.run(eng, Q.poly_call(eng, ua.set, ub.set), pairs, n_dev=int(s) + 5)
         assert_same_by_scale(got[:s + 5], want[:s + 5], k[:s + 5], f"mixed scales, device count {s + 5}")
     ua.free()
     ub.free()
@@ -148,16 +133,16 @@ def test_list_longer_than_one_grid(eng, oracle, wl):
     127 records beyond it keep the band bytes (run() checks them).  The whole output is compared."""
     ra, rb = cases.rect_sets(oracle, wl)
     mixed = cases.all_pairs(500, 500)[::41][:4099]
-    want = ref.rect_contacts(ra, rb, *base.local(mixed))
+    want = ref.rect_contacts(ra, rb, *h.local(mixed))
     assert len(mixed) == 4099 and 0.02 < want["hit"].mean() < 0.5
     total = (1 << 24) + 197
     tile = np.arange(total) % 4099
     listed = mixed[tile]
     want32 = np.ascontiguousarray(want).view(np.uint32).reshape(-1, 4)
-    da, db = base.RectsOnDevice(eng, ra), base.RectsOnDevice(eng, rb)
+    da, db = h.RectsOnDevice(eng, ra), h.RectsOnDevice(eng, rb)
     for n_dev in (None, (1 << 24) + 70):
         bound = total if n_dev is None else n_dev
-        got = base.run(eng, base.rect_call(eng, da, db), listed, n_dev=n_dev)[:bound]
+        got = Q.run(eng, Q.rect_call(eng, da, db), listed, n_dev=n_dev)[:bound]
         got32 = np.ascontiguousarray(got).view(np.uint32).reshape(-1, 4)
         whole = bound // 4099 * 4099
         differs = np.concatenate([(got32[:whole].reshape(-1, 4099, 4) != want32[None]).any(axis=2).ravel(),

@@ -2,9 +2,7 @@
 tests/contact_ref.py — the numpy restatement of the contract of include/c2d.h, pinned by tests/test_contact_ref_cpu.py — floats
 bit for bit (+0 and -0 equal), and `hit` also equals the pairwise GPU path and the oracle.  Every output buffer handed to the
 library sits between guard bands that are checked afterwards."""
-import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,128 +12,18 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import contact_cases as cases  # noqa: E402
 import contact_ref as ref  # noqa: E402
+import pair_list_harness as h  # noqa: E402
+from pair_list_harness import RectsOnDevice, Uploaded, local, oracle_hits, pairwise_gpu  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-GUARD = 4            # guard records in front of and behind every output
-BAND = 0xA5
-
-
-class Uploaded:
-    """A polygon set on the device: every plane row shifted by `offset` floats, `stride` >= n elements between vertex rows, NaN in
-    the gaps.  .set is the c2d_poly_set; .sub(r0, r1) the shard of polygons [r0, r1) (pointer offset, the same stride)."""
-
-    def __init__(self, eng, s, offset=0, stride=None, with_k=True):
-        vx, vy, k = s
-        self.eng, self.rows, self.n = eng, vx.shape[0], vx.shape[1]
-        self.stride = self.n if stride is None else stride
-        host = np.full((2, self.rows * self.stride + offset), np.nan, np.float32)
-        for p, v in enumerate((vx, vy)):
-            for r in range(self.rows):
-                host[p, offset + r * self.stride: offset + r * self.stride + self.n] = v[r]
-        self.d = eng.to_device(host)
-        self.px, self.py = self.d.row(0) + 4 * offset, self.d.row(1) + 4 * offset
-        self.dk = eng.to_device(k) if (k is not None and with_k) else None
-        self.set = self.sub(0, self.n)
-
-    def sub(self, r0, r1):
-        return self.eng.poly_set(self.px + 4 * r0, self.py + 4 * r0, None if self.dk is None else self.dk.ptr + r0, r1 - r0, self.rows, self.stride)
-
-    def free(self):
-        self.d.free()
-        if self.dk is not None:
-            self.dk.free()
-
-
-class RectsOnDevice:
-    def __init__(self, eng, planes):
-        self.n = planes.shape[1]
-        self.d = eng.to_device(planes)
-        self.ptrs = [self.d.row(k) for k in range(8)]
-
-    def free(self):
-        self.d.free()
-
-
-def run(eng, call, pairs, capacity=None, n_dev=None, expect_error=False):
-    """call(d_pairs, capacity, d_out, d_n) queues the contacts call.  -> CONTACT_DT[capacity]: the output, taken from between two guard
-    bands that must be intact; every record at or beyond min(capacity, n_dev) must be untouched as well (it reads as BAND bytes)."""
-    cap = len(pairs) if capacity is None else capacity
-    host_pairs = np.full((max(cap, 1), 2), 0xFFFFFFFF, np.uint32)   # entries beyond the list: indices no set has
-    host_pairs[:len(pairs)] = pairs
-    d_pairs = eng.to_device(host_pairs)
-    d_out = eng.empty(cap + 2 * GUARD, ref.CONTACT_DT)
-    eng.memset(d_out, BAND, d_out.nbytes)
-    d_n = None if n_dev is None else eng.to_device(np.array([n_dev], np.uint64))
-    try:
-        call(d_pairs, cap, d_out.ptr + 16 * GUARD, d_n)
-        if expect_error:
-            with pytest.raises(Exception) as e:
-                eng.synchronize()
-            assert getattr(e.value, "status", None) == -1
-            eng.synchronize()
-            eng.check_async()      # reported once, then clear
-        else:
-            eng.synchronize()
-        out = d_out.get()
-    finally:
-        for x in (d_pairs, d_out, d_n):
-            if x is not None:
-                x.free()
-    raw = out.view(np.uint8).reshape(-1, 16)
-    assert (raw[:GUARD] == BAND).all() and (raw[GUARD + cap:] == BAND).all(), "written outside the output"
-    bound = cap if n_dev is None else min(cap, n_dev)
-    assert (raw[GUARD + bound: GUARD + cap] == BAND).all(), "written at or beyond min(n_pairs, *d_n_pairs)"
-    return out[GUARD: GUARD + cap]
-
-
-def poly_call(eng, a, b, row_base=0, col_base=0):
-    return lambda d_pairs, cap, out, d_n: eng.poly_pair_contacts(a, b, d_pairs, cap, out, n_pairs_dev=d_n, row_base=row_base, col_base=col_base)
-
-
-def rect_call(eng, a, b, row_base=0, col_base=0):
-    return lambda d_pairs, cap, out, d_n: eng.rect_pair_contacts(a.ptrs, a.n, b.ptrs, b.n, d_pairs, cap, out, n_pairs_dev=d_n, row_base=row_base,
-                                                                 col_base=col_base)
-
-
-def assert_same(got, want, what):
-    ok = ref.same(got, want)
-    if not ok.all():
-        q = int(np.flatnonzero(~ok)[0])
-        raise AssertionError(f"{what}: {int((~ok).sum())} of {len(want)} contacts differ; first at {q}: got {got[q]}, want {want[q]}")
-
-
-def local(pairs):
-    return pairs[:, 0].astype(np.int64), pairs[:, 1].astype(np.int64)
-
-
-def pairwise_gpu(eng, a, b, pairs):
-    """the boolean of c2d_sat_poly_pairs_rows on the listed pairs (both sets in 16 rows)"""
-    i, j = local(pairs)
-    vx, vy = np.stack([a[0][:, i], b[0][:, j]]), np.stack([a[1][:, i], b[1][:, j]])
-    k = np.stack([a[2][i], b[2][j]])
-    d = [eng.to_device(x) for x in (vx, vy, k)]
-    d_out = eng.zeros(len(pairs), np.uint8)
-    eng.sat_poly_pairs_rows(*d, len(pairs), vx.shape[1], d_out)
-    out = d_out.get()
-    for x in d + [d_out]:
-        x.free()
-    return out
-
-
-def oracle_hits(oracle, a, b, pairs):
-    i, j = local(pairs)
-    return oracle.sat_poly_pairs(np.stack([a[0][:, i], b[0][:, j]]), np.stack([a[1][:, i], b[1][:, j]]), np.stack([a[2][i], b[2][j]]))[0]
+Q = h.CONTACTS
+run, poly_call, rect_call, assert_same = Q.run, Q.poly_call, Q.rect_call, Q.assert_same
 
 
 @pytest.fixture(scope="module")
 def dense(wl, oracle):
     """two sets of about 300 polygons in a small box with the reference contacts of ALL their pairs, computed once"""
-    a, b = cases.dense_poly_sets(wl)
-    pairs = cases.all_pairs(a[0].shape[1], b[0].shape[1])
-    want = ref.poly_contacts(a, b, *local(pairs))
-    want.setflags(write=False)
-    share = want["hit"].mean()
-    assert 0.1 < share < 0.5, share
+    a, b, pairs, want = h.dense(wl, Q)
     assert np.array_equal(want["hit"], oracle_hits(oracle, a, b, pairs))
     return a, b, pairs, want
 
@@ -202,22 +90,12 @@ def test_layout_variants(eng, wl):
     us.free()
 
 
-HARD = None
-
-
-def hard_batches(wl):
-    global HARD
-    if HARD is None:
-        HARD = cases.hard_poly_batches(wl)
-    return HARD
-
-
 @pytest.mark.parametrize("name", ["clockwise", "clockwise_both", "repeated_vertices", "k1_k2", "touching", "equal_shapes", "equal_boxes", "scale_1e30",
                                   "scale_1e-30", "scale_1e-42", "scale_1e18", "scale_1e-18", "non_finite_vertex0", "non_finite_later_vertex",
                                   "overflowing_len2"])
 def test_hard_inputs(eng, oracle, wl, name):
     """one small batch per class; on the finite, non-overflowing ones hit == (depth >= 0) wherever an axis was usable"""
-    a, b, pairs, finite = hard_batches(wl)[name]
+    a, b, pairs, finite = h.hard_batches(wl)[name]
     want = ref.poly_contacts(a, b, *local(pairs))
     ua, ub = Uploaded(eng, a), Uploaded(eng, b)
     got = run(eng, poly_call(eng, ua.set, ub.set), pairs)
@@ -310,24 +188,6 @@ def test_rectangles(eng, oracle, wl):
     eng.check_async()
 
 
-def test_device_count_bounds_the_work(eng, dense):
-    """n_pairs = capacity with the count on the device: smaller (only that many records are written), equal, larger (clamped to
-    n_pairs), and no count at all.  run() checks the guard bands and every record beyond the bound."""
-    a, b, pairs, want = dense
-    ua, ub = Uploaded(eng, a), Uploaded(eng, b)
-    sel = np.arange(5, len(pairs), 311)[:300]
-    for n_dev in (0, 1, 63, 64, 137, 299, 300, 301, 1 << 40, (1 << 64) - 1, None):
-        got = run(eng, poly_call(eng, ua.set, ub.set), pairs[sel], capacity=300, n_dev=n_dev)
-        bound = 300 if n_dev is None else min(300, n_dev)
-        assert_same(got[:bound], want[sel][:bound], f"device count {n_dev}")
-    # a capacity above the list, as a caller passes it: the count says where the list ends
-    got = run(eng, poly_call(eng, ua.set, ub.set), pairs[sel], capacity=1000, n_dev=300)
-    assert_same(got[:300], want[sel], "capacity 1000, count 300")
-    eng.check_async()
-    ua.free()
-    ub.free()
-
-
 def test_pipeline_through_the_broad_phase(eng, wl, oracle):
     """poly_contacts_host and rect_contacts_host (broad phase -> list -> contacts on the list's device count) on a sparse scene of
     4099 objects give the pairs and contacts of the cross list followed by the contacts call."""
@@ -362,95 +222,3 @@ def test_pipeline_through_the_broad_phase(eng, wl, oracle):
         assert contacts.tobytes() == direct.tobytes()
         assert_same(contacts, ref.rect_contacts(ra, sb, *local(cross)), "rectangle pipeline")
     eng.check_async()
-
-
-def test_argument_errors(eng, pkg, wl):
-    a = wl.random_convex_polygon_set(100, seed=5, extent=3.0)
-    ua = Uploaded(eng, a)
-    S = ua.set
-    d_pairs = eng.zeros((16, 2), np.uint32)
-    d_out = eng.zeros(16, ref.CONTACT_DT)
-    d_n = eng.zeros(1, np.uint64)
-    mk = lambda **kw: eng.poly_set(kw.get("vx", ua.px), kw.get("vy", ua.py), ua.dk, kw.get("n", 100), kw.get("rows", 16), kw.get("stride", 0))  # noqa: E731
-    planes = [ua.px] * 8
-    raw = eng.lib.c2d_poly_pair_contacts
-    assert raw(eng.h, None, C.byref(S), d_pairs.ptr, 16, None, 0, 0, d_out.ptr, None) == -1
-    assert raw(eng.h, C.byref(S), None, d_pairs.ptr, 16, None, 0, 0, d_out.ptr, None) == -1
-    bad = [
-        lambda: eng.poly_pair_contacts(mk(vx=0), S, d_pairs, 16, d_out),                       # a NULL plane
-        lambda: eng.poly_pair_contacts(S, mk(vy=0), d_pairs, 16, d_out),
-        lambda: eng.poly_pair_contacts(mk(rows=0), S, d_pairs, 16, d_out),                     # rows 0 or 17
-        lambda: eng.poly_pair_contacts(S, mk(rows=17), d_pairs, 16, d_out),
-        lambda: eng.poly_pair_contacts(mk(stride=99), S, d_pairs, 16, d_out),                  # stride < n
-        lambda: eng.poly_pair_contacts(mk(vx=ua.px + 2), S, d_pairs, 16, d_out),               # a misaligned plane
-        lambda: eng.poly_pair_contacts(S, S, None, 16, d_out),                                 # no list
-        lambda: eng.poly_pair_contacts(S, S, d_pairs, 16, None),                               # no output
-        lambda: eng.poly_pair_contacts(S, S, d_pairs, 15, d_out.ptr + 8),                      # output not 16-byte aligned
-        lambda: eng.poly_pair_contacts(S, S, d_pairs.ptr + 2, 15, d_out),                      # list not 4-byte aligned
-        lambda: eng.poly_pair_contacts(S, S, d_pairs, 16, d_out, n_pairs_dev=d_n.ptr + 4),     # count not 8-byte aligned
-        lambda: eng.poly_pair_contacts(S, S, d_pairs, 16, d_out, row_base=1 << 62),            # bases beyond 2^62
-        lambda: eng.poly_pair_contacts(S, S, d_pairs, 16, d_out, col_base=1 << 62),
-        lambda: eng.rect_pair_contacts(planes[:7] + [0], 100, planes, 100, d_pairs, 16, d_out),
-        lambda: eng.rect_pair_contacts(planes, 100, planes[:7] + [0], 100, d_pairs, 16, d_out),
-        lambda: eng.rect_pair_contacts(planes, 100, planes, 100, None, 16, d_out),
-        lambda: eng.rect_pair_contacts(planes, 100, planes, 100, d_pairs, 16, None),
-        lambda: eng.rect_pair_contacts(planes, 100, planes, 100, d_pairs, 15, d_out.ptr + 4),
-        lambda: eng.rect_pair_contacts(planes, 100, planes, 100, d_pairs, 16, d_out, col_base=1 << 62),
-    ]
-    for q, call in enumerate(bad):
-        with pytest.raises(pkg.C2DError) as e:
-            call()
-        assert e.value.status == -1, q
-    eng.poly_pair_contacts(S, S, None, 0, None)                      # n_pairs == 0: a no-op
-    eng.rect_pair_contacts(planes, 100, planes, 100, None, 0, None)
-    eng.synchronize()
-    assert (d_out.get().view(np.uint8) == 0).all(), "a refused call wrote something"
-    for x in (d_pairs, d_out, d_n, ua):
-        x.free()
-
-
-def test_graph_capture_follows_the_device_count():
-    """One capture of a contacts call with d_n_pairs, replayed with different counts written to the device in between
-    (tests/contact_graph_check.py, its own process: torch has to be imported before libc2d.so)."""
-    out = subprocess.run([sys.executable, os.path.join(HERE, "contact_graph_check.py")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    assert "contact graph ok" in out.stdout
-
-
-def test_bad_pairs_read_nothing_and_are_reported_once(eng, wl):
-    """Indices equal to n, 0xFFFFFFFF and below the base, in either column, and polygons with a vertex count of 0 and 17: those
-    entries carry BAD_PAIR, every other entry is correct, and the error is reported once by the next synchronise.  The planes end
-    where their allocations end; the guard (contact_kernel: `ranged`, `valid`) lets no such index reach a load."""
-    n_a, n_b, rb, cb = 50, 64, 1000, 5
-    a = wl.random_convex_polygon_set(n_a, seed=8001, extent=2.5)
-    b = wl.random_convex_polygon_set(n_b, seed=8002, kmax=8, extent=2.5, rows=8)
-    kb = b[2].copy()
-    kb[[3, 40]] = [0, 17]
-    b = (b[0], b[1], kb)
-    d = [eng.to_device(x) for x in (*a, *b)]        # exact allocations: nothing behind the last plane row
-    sa, sb = eng.poly_set(d[0], d[1], d[2], n_a, 16), eng.poly_set(d[3], d[4], d[5], n_b, 8)
-    good = cases.all_pairs(n_a, n_b)[::7].astype(np.int64) + (rb, cb)
-    bad = np.array([[rb + n_a, cb], [0xFFFFFFFF, cb + 1], [rb - 1, cb + 2], [rb + 1, cb + n_b], [rb + 2, 0xFFFFFFFF], [rb + 3, cb - 1],
-                    [0, 0], [0xFFFFFFFF, 0xFFFFFFFF], [rb + n_a + 70, cb + 3]], np.int64)
-    listed = good.copy()
-    at = np.array([0, 1, 63, 64, 65, 200, 255, 256, len(good) - 1])
-    listed[at] = bad
-    want = ref.poly_contacts(a, b, listed[:, 0] - rb, listed[:, 1] - cb)
-    assert (want["flags"][at] == ref.BAD_PAIR).all() and (want["flags"] == ref.BAD_PAIR).sum() > len(at)   # (the bad counts as well)
-    assert (want["flags"] != ref.BAD_PAIR).sum() > 300
-    eng.check_async()
-    got = run(eng, poly_call(eng, sa, sb, row_base=rb, col_base=cb), listed.astype(np.uint32), expect_error=True)
-    assert_same(got, want, "list with bad pairs")
-    # the same with rectangles (no absent objects there: only the indices)
-    ra = np.ascontiguousarray(np.concatenate([a[0][:4], a[1][:4]])[[0, 4, 1, 5, 2, 6, 3, 7]])
-    da = RectsOnDevice(eng, ra)
-    want = ref.rect_contacts(ra, ra, listed[:, 0] - rb, listed[:, 1] - cb)
-    got = run(eng, rect_call(eng, da, da, row_base=rb, col_base=cb), listed.astype(np.uint32), expect_error=True)
-    assert_same(got, want, "rectangle list with bad pairs")
-    # a clean call afterwards reports nothing
-    sound = good[(kb[good[:, 1] - cb] >= 1) & (kb[good[:, 1] - cb] <= 8)][:10]
-    clean = run(eng, poly_call(eng, sa, sb, row_base=rb, col_base=cb), sound.astype(np.uint32))
-    assert (clean["flags"] & ref.BAD_PAIR == 0).all()
-    eng.check_async()
-    for x in d + [da]:
-        x.free()

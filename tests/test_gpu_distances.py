@@ -2,10 +2,8 @@
 tests/distance_ref.py — the numpy restatement of the contract of include/c2d.h, pinned by tests/test_distance_ref_cpu.py — floats
 bit for bit (+0 and -0 equal), and `hit` also equals the pairwise GPU path.  Every output buffer handed to the library sits between
 guard bands that are checked afterwards."""
-import ctypes as C
 import importlib.util
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,84 +13,19 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import contact_cases as cases  # noqa: E402
 import distance_ref as ref  # noqa: E402
-import test_gpu_contacts as base  # noqa: E402   (the uploads, the pairwise GPU path)
+import pair_list_harness as h  # noqa: E402
+from pair_list_harness import BAND, RectsOnDevice, Uploaded, local, pairwise_gpu, rect_pairwise_gpu  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-GUARD = 4            # guard records in front of and behind every output
-BAND = 0xA5
 FUZZ_SEED = 20263
-Uploaded, RectsOnDevice, local, pairwise_gpu = base.Uploaded, base.RectsOnDevice, base.local, base.pairwise_gpu
-
-
-def run(eng, call, pairs, capacity=None, n_dev=None, expect_error=False):
-    """call(d_pairs, capacity, d_out, d_n) queues the distances call.  -> DISTANCE_DT[capacity]: the output, taken from between two
-    guard bands that must be intact; every record at or beyond min(capacity, n_dev) must be untouched as well (it reads as BAND bytes)."""
-    cap = len(pairs) if capacity is None else capacity
-    host_pairs = np.full((max(cap, 1), 2), 0xFFFFFFFF, np.uint32)   # entries beyond the list: indices no set has
-    host_pairs[:len(pairs)] = pairs
-    d_pairs = eng.to_device(host_pairs)
-    d_out = eng.empty(cap + 2 * GUARD, ref.DISTANCE_DT)
-    eng.memset(d_out, BAND, d_out.nbytes)
-    d_n = None if n_dev is None else eng.to_device(np.array([n_dev], np.uint64))
-    try:
-        call(d_pairs, cap, d_out.ptr + 32 * GUARD, d_n)
-        if expect_error:
-            with pytest.raises(Exception) as e:
-                eng.synchronize()
-            assert getattr(e.value, "status", None) == -1
-            eng.synchronize()
-            eng.check_async()      # reported once, then clear
-        else:
-            eng.synchronize()
-        out = d_out.get()
-    finally:
-        for x in (d_pairs, d_out, d_n):
-            if x is not None:
-                x.free()
-    raw = out.view(np.uint8).reshape(-1, 32)
-    assert (raw[:GUARD] == BAND).all() and (raw[GUARD + cap:] == BAND).all(), "written outside the output"
-    bound = cap if n_dev is None else min(cap, n_dev)
-    assert (raw[GUARD + bound: GUARD + cap] == BAND).all(), "written at or beyond min(n_pairs, *d_n_pairs)"
-    return out[GUARD: GUARD + cap]
-
-
-def poly_call(eng, a, b, row_base=0, col_base=0):
-    return lambda d_pairs, cap, out, d_n: eng.poly_pair_distances(a, b, d_pairs, cap, out, n_pairs_dev=d_n, row_base=row_base, col_base=col_base)
-
-
-def rect_call(eng, a, b, row_base=0, col_base=0):
-    return lambda d_pairs, cap, out, d_n: eng.rect_pair_distances(a.ptrs, a.n, b.ptrs, b.n, d_pairs, cap, out, n_pairs_dev=d_n, row_base=row_base,
-                                                                  col_base=col_base)
-
-
-def assert_same(got, want, what):
-    ok = ref.same(got, want)
-    if not ok.all():
-        q = int(np.flatnonzero(~ok)[0])
-        raise AssertionError(f"{what}: {int((~ok).sum())} of {len(want)} records differ; first at {q}: got {got[q]}, want {want[q]}")
-
-
-def rect_pairwise_gpu(eng, a, b, pairs):
-    """the boolean of c2d_sat_rect_pairs_verts on the listed pairs"""
-    i, j = local(pairs)
-    d = eng.to_device(np.concatenate([a[:, i], b[:, j]]))
-    d_out = eng.zeros(len(pairs), np.uint8)
-    eng.sat_rect_pairs_verts([d.row(k) for k in range(16)], len(pairs), d_out)
-    out = d_out.get()
-    d.free()
-    d_out.free()
-    return out
+Q = h.DISTANCES
+run, poly_call, rect_call, assert_same = Q.run, Q.poly_call, Q.rect_call, Q.assert_same
 
 
 @pytest.fixture(scope="module")
 def dense(wl):
     """the dense sets (300 x 311 polygons) with the reference records of ALL their pairs, computed once"""
-    a, b = cases.dense_poly_sets(wl)
-    pairs = cases.all_pairs(a[0].shape[1], b[0].shape[1])
-    want = ref.poly_distances(a, b, *local(pairs))
-    want.setflags(write=False)
-    assert 0.1 < want["hit"].mean() < 0.5
-    return a, b, pairs, want
+    return h.dense(wl, Q)
 
 
 def test_values_for_every_list_length(eng, dense):
@@ -122,23 +55,6 @@ def test_dense_batch_in_order_and_shuffled(eng, dense):
     assert np.array_equal(got["hit"], pairwise_gpu(eng, a, b, pairs)), "hit differs from c2d_sat_poly_pairs_rows"
     order = np.random.default_rng(8301).permutation(len(pairs))
     assert_same(run(eng, poly_call(eng, ua.set, ub.set), pairs[order]), want[order], "all pairs, shuffled")
-    eng.check_async()
-    ua.free()
-    ub.free()
-
-
-def test_device_count_bounds_the_work(eng, dense):
-    """n_pairs = capacity with the count on the device: smaller, equal, larger (clamped to n_pairs), and no count at all.  run() checks
-    the guard bands and every record beyond the bound."""
-    a, b, pairs, want = dense
-    ua, ub = Uploaded(eng, a), Uploaded(eng, b)
-    sel = np.arange(5, len(pairs), 311)[:300]
-    for n_dev in (0, 1, 63, 64, 137, 299, 300, 301, 1 << 40, (1 << 64) - 1, None):
-        got = run(eng, poly_call(eng, ua.set, ub.set), pairs[sel], capacity=300, n_dev=n_dev)
-        bound = 300 if n_dev is None else min(300, n_dev)
-        assert_same(got[:bound], want[sel][:bound], f"device count {n_dev}")
-    got = run(eng, poly_call(eng, ua.set, ub.set), pairs[sel], capacity=1000, n_dev=300)
-    assert_same(got[:300], want[sel], "capacity 1000, count 300")
     eng.check_async()
     ua.free()
     ub.free()
@@ -188,16 +104,6 @@ def test_layout_variants(eng, wl):
     us.free()
 
 
-HARD = None
-
-
-def hard_batches(wl):
-    global HARD
-    if HARD is None:
-        HARD = cases.hard_poly_batches(wl)
-    return HARD
-
-
 HARD_NAMES = ["clockwise", "clockwise_both", "repeated_vertices", "k1_k2", "touching", "equal_shapes", "equal_boxes", "scale_1e30", "scale_1e-30",
               "scale_1e-42", "scale_1e18", "scale_1e-18", "non_finite_vertex0", "non_finite_later_vertex", "overflowing_len2"]
 
@@ -206,8 +112,8 @@ HARD_NAMES = ["clockwise", "clockwise_both", "repeated_vertices", "k1_k2", "touc
 def test_hard_inputs(eng, wl, name):
     """one small batch per class of tests/contact_cases.py: where masking the padding, the closing edge, k = 1 / 2, exact ties and
     non-finite input go wrong"""
-    a, b, pairs, finite = hard_batches(wl)[name]
-    assert sorted(hard_batches(wl)) == sorted(HARD_NAMES), "a batch of hard_poly_batches is not run"
+    a, b, pairs, finite = h.hard_batches(wl)[name]
+    assert sorted(h.hard_batches(wl)) == sorted(HARD_NAMES), "a batch of hard_poly_batches is not run"
     want = ref.poly_distances(a, b, *local(pairs))
     ua, ub = Uploaded(eng, a), Uploaded(eng, b)
     got = run(eng, poly_call(eng, ua.set, ub.set), pairs)
@@ -256,7 +162,7 @@ def test_boxes_on_a_grid_many_way_ties(eng):
     candidates with the same bits, the winner among them is the rule's first, and the two calls give the same records"""
     (pa, pb), (ra, rb) = grid_boxes()
     n = pa[0].shape[1]
-    pairs = np.stack([np.arange(n), np.arange(n)], axis=1).astype(np.uint32)
+    pairs = h.diag(n)
     want = ref.poly_distances(pa, pb, *local(pairs))
     assert (want["hit"] == 0).all() and (want["flags"] & ref.INTERIOR != 0).mean() > 0.2 and (want["flags"] & ref.INTERIOR == 0).mean() > 0.2
     assert ref.same(ref.rect_distances(ra, rb, *local(pairs)), want).all()
@@ -309,44 +215,6 @@ def test_rectangles(eng, oracle, wl):
     for x in (da, db, d_sa, d_sb):
         x.free()
     eng.check_async()
-
-
-def test_bad_pairs_read_nothing_and_are_reported_once(eng, wl):
-    """Indices equal to n, 0xFFFFFFFF and below the base, in either column, and polygons with a vertex count of 0 and 17: those
-    entries carry BAD_PAIR, every other entry is correct, and the error is reported once by the next synchronise.  The planes end
-    where their allocations end."""
-    n_a, n_b, rb, cb = 50, 64, 1000, 5
-    a = wl.random_convex_polygon_set(n_a, seed=8001, extent=2.5)
-    b = wl.random_convex_polygon_set(n_b, seed=8002, kmax=8, extent=2.5, rows=8)
-    kb = b[2].copy()
-    kb[[3, 40]] = [0, 17]
-    b = (b[0], b[1], kb)
-    d = [eng.to_device(x) for x in (*a, *b)]        # exact allocations: nothing behind the last plane row
-    sa, sb = eng.poly_set(d[0], d[1], d[2], n_a, 16), eng.poly_set(d[3], d[4], d[5], n_b, 8)
-    good = cases.all_pairs(n_a, n_b)[::7].astype(np.int64) + (rb, cb)
-    bad = np.array([[rb + n_a, cb], [0xFFFFFFFF, cb + 1], [rb - 1, cb + 2], [rb + 1, cb + n_b], [rb + 2, 0xFFFFFFFF], [rb + 3, cb - 1],
-                    [0, 0], [0xFFFFFFFF, 0xFFFFFFFF], [rb + n_a + 70, cb + 3]], np.int64)
-    listed = good.copy()
-    at = np.array([0, 1, 63, 64, 65, 200, 255, 256, len(good) - 1])
-    listed[at] = bad
-    want = ref.poly_distances(a, b, listed[:, 0] - rb, listed[:, 1] - cb)
-    assert (want["flags"][at] == ref.BAD_PAIR).all() and (want["flags"] == ref.BAD_PAIR).sum() > len(at)   # (the bad counts as well)
-    assert (want["flags"] != ref.BAD_PAIR).sum() > 300
-    eng.check_async()
-    got = run(eng, poly_call(eng, sa, sb, row_base=rb, col_base=cb), listed.astype(np.uint32), expect_error=True)
-    assert_same(got, want, "list with bad pairs")
-    ra = np.ascontiguousarray(np.concatenate([a[0][:4], a[1][:4]])[[0, 4, 1, 5, 2, 6, 3, 7]])
-    da = RectsOnDevice(eng, ra)
-    want = ref.rect_distances(ra, ra, listed[:, 0] - rb, listed[:, 1] - cb)
-    got = run(eng, rect_call(eng, da, da, row_base=rb, col_base=cb), listed.astype(np.uint32), expect_error=True)
-    assert_same(got, want, "rectangle list with bad pairs")
-    # a clean call afterwards reports nothing
-    sound = good[(kb[good[:, 1] - cb] >= 1) & (kb[good[:, 1] - cb] <= 8)][:10]
-    clean = run(eng, poly_call(eng, sa, sb, row_base=rb, col_base=cb), sound.astype(np.uint32))
-    assert (clean["flags"] & ref.BAD_PAIR == 0).all()
-    eng.check_async()
-    for x in d + [da]:
-        x.free()
 
 
 def test_pipeline_from_the_list_calls(eng, wl):
@@ -410,60 +278,6 @@ def test_list_longer_than_one_grid(eng, oracle, wl):
     da.free()
     db.free()
     eng.check_async()
-
-
-def test_argument_errors(eng, pkg, wl):
-    a = wl.random_convex_polygon_set(100, seed=5, extent=3.0)
-    ua = Uploaded(eng, a)
-    S = ua.set
-    d_pairs = eng.zeros((16, 2), np.uint32)
-    d_out = eng.zeros(16, ref.DISTANCE_DT)
-    d_n = eng.zeros(1, np.uint64)
-    mk = lambda **kw: eng.poly_set(kw.get("vx", ua.px), kw.get("vy", ua.py), ua.dk, kw.get("n", 100), kw.get("rows", 16), kw.get("stride", 0))  # noqa: E731
-    planes = [ua.px] * 8
-    raw = eng.lib.c2d_poly_pair_distances
-    assert raw(eng.h, None, C.byref(S), d_pairs.ptr, 16, None, 0, 0, d_out.ptr, None) == -1
-    assert raw(eng.h, C.byref(S), None, d_pairs.ptr, 16, None, 0, 0, d_out.ptr, None) == -1
-    bad = [
-        lambda: eng.poly_pair_distances(mk(vx=0), S, d_pairs, 16, d_out),                       # a NULL plane
-        lambda: eng.poly_pair_distances(S, mk(vy=0), d_pairs, 16, d_out),
-        lambda: eng.poly_pair_distances(mk(rows=0), S, d_pairs, 16, d_out),                     # rows 0 or 17
-        lambda: eng.poly_pair_distances(S, mk(rows=17), d_pairs, 16, d_out),
-        lambda: eng.poly_pair_distances(mk(stride=99), S, d_pairs, 16, d_out),                  # stride < n
-        lambda: eng.poly_pair_distances(mk(vx=ua.px + 2), S, d_pairs, 16, d_out),               # a misaligned plane
-        lambda: eng.poly_pair_distances(S, S, None, 16, d_out),                                 # no list
-        lambda: eng.poly_pair_distances(S, S, d_pairs, 16, None),                               # no output
-        lambda: eng.poly_pair_distances(S, S, d_pairs, 15, d_out.ptr + 8),                      # output not 16-byte aligned
-        lambda: eng.poly_pair_distances(S, S, d_pairs.ptr + 2, 15, d_out),                      # list not 4-byte aligned
-        lambda: eng.poly_pair_distances(S, S, d_pairs, 16, d_out, n_pairs_dev=d_n.ptr + 4),     # count not 8-byte aligned
-        lambda: eng.poly_pair_distances(S, S, d_pairs, 1 << 62 | 1, d_out),                     # n_pairs beyond 2^62
-        lambda: eng.poly_pair_distances(S, S, d_pairs, 16, d_out, row_base=1 << 62),            # bases beyond 2^62
-        lambda: eng.poly_pair_distances(S, S, d_pairs, 16, d_out, col_base=1 << 62),
-        lambda: eng.rect_pair_distances(planes[:7] + [0], 100, planes, 100, d_pairs, 16, d_out),
-        lambda: eng.rect_pair_distances(planes, 100, planes[:7] + [0], 100, d_pairs, 16, d_out),
-        lambda: eng.rect_pair_distances(planes, 100, planes, 100, None, 16, d_out),
-        lambda: eng.rect_pair_distances(planes, 100, planes, 100, d_pairs, 16, None),
-        lambda: eng.rect_pair_distances(planes, 100, planes, 100, d_pairs, 15, d_out.ptr + 4),
-        lambda: eng.rect_pair_distances(planes, 100, planes, 100, d_pairs, 16, d_out, col_base=1 << 62),
-    ]
-    for q, call in enumerate(bad):
-        with pytest.raises(pkg.C2DError) as e:
-            call()
-        assert e.value.status == -1, q
-    eng.poly_pair_distances(S, S, None, 0, None)                      # n_pairs == 0: a no-op
-    eng.rect_pair_distances(planes, 100, planes, 100, None, 0, None)
-    eng.synchronize()
-    assert (d_out.get().view(np.uint8) == 0).all(), "a refused call wrote something"
-    for x in (d_pairs, d_out, d_n, ua):
-        x.free()
-
-
-def test_graph_capture_follows_the_device_count():
-    """One capture of a distances call with d_n_pairs, replayed with different counts written to the device in between
-    (tests/distance_graph_check.py, its own process: torch has to be imported before libc2d.so)."""
-    out = subprocess.run([sys.executable, os.path.join(HERE, "distance_graph_check.py")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    assert "distance graph ok" in out.stdout
 
 
 def test_fuzzer_configurations_at_a_fixed_seed(eng):

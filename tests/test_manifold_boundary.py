@@ -84,7 +84,7 @@ def test_null_and_bad_arguments_are_rejected_without_a_device(pkg):
     assert call(None, None, None, None, 0, None, 0, 0, None, None, None) == -1
     assert call(None, C.byref(s), C.byref(s), p, 4, None, 0, 0, C.c_void_p(0x2008), m, None) == -1   # (misaligned outputs too)
     assert call(None, C.byref(s), C.byref(s), p, 4, None, 0, 0, c, C.c_void_p(0x3010 - 8), None) == -1
-    # (with a ctx, every other refusal is checked on the GPU: tests/test_gpu_manifolds.py::test_argument_errors)
+    # (with a ctx, every other refusal is checked on the GPU: tests/test_gpu_pair_list_contract.py::test_argument_errors[manifolds])
 
 
 def test_host_convenience_checks_its_shapes_before_touching_a_device(pkg, wl):
