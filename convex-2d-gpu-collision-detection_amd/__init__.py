@@ -34,6 +34,8 @@ from .binding import (  # noqa: F401
     DISTANCE_INTERIOR,
     DISTANCE_NO_CANDIDATE,
     DISTANCE_BAD_PAIR,
+    RAY_HIT_DT,
+    RAY_START_INSIDE,
     make_polygon,
     library_path,
     load_library,

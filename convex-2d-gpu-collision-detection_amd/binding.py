@@ -41,6 +41,10 @@ DISTANCE_DT = np.dtype([("dist", "<f4"), ("ax", "<f4"), ("ay", "<f4"), ("bx", "<
                         ("flags", "u1"), ("reserved0", "<u2"), ("reserved1", "<u4")])   # c2d_distance
 DISTANCE_EDGE_ON_B, DISTANCE_INTERIOR, DISTANCE_NO_CANDIDATE, DISTANCE_BAD_PAIR = 1, 2, 4, 8
 
+# ray queries (include/c2d.h, "ray queries: the nearest hit of every segment against a polygon set")
+RAY_HIT_DT = np.dtype([("poly", "<u4"), ("t", "<f4"), ("u", "<f4"), ("edge", "<u2"), ("hit", "u1"), ("flags", "u1")])   # c2d_ray_hit
+RAY_START_INSIDE = 1
+
 
 class C2DError(RuntimeError):
     def __init__(self, status: int, what: str, detail: str = ""):
@@ -180,6 +184,7 @@ _SIGNATURES = {
                                           C.c_void_p, C.c_void_p]),
     "c2d_rect_pair_distances": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                           C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "c2d_poly_ray_casts": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(_PolySet), C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_bins_create": (C.c_int, [C.c_void_p, C.POINTER(_PolyBin), C.c_size_t, C.POINTER(C.c_void_p)]),
     "c2d_poly_bins_from_padded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "c2d_poly_bins_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -788,6 +793,18 @@ class Engine:
         a, b = self._cross_planes(a_planes, b_planes)
         self._check(self.lib.c2d_rect_pair_distances(self.h, a, n_a, b, n_b, _ptr_of(pairs), n_pairs, _ptr_of(n_pairs_dev), row_base, col_base,
                                                      _ptr_of(out), C.c_void_p(stream)), "c2d_rect_pair_distances")
+
+    # -- ray queries (include/c2d.h "ray queries: the nearest hit of every segment against a polygon set") -----------------
+    def poly_ray_casts(self, rays: Sequence, n_rays: int, b: _PolySet, out, col_base: int = 0, stream: int = 0):
+        """c2d_poly_ray_casts: out[r] (RAY_HIT_DT[n_rays], 16-byte aligned) = the first polygon of b that the segment from
+        (ox, oy)[r] to (ox + dx, oy + dy)[r] touches, with t, the edge and u; rays = the four planes ox, oy, dx, dy (f32[n_rays]
+        each); b from poly_set(); a hit reports col_base + j"""
+        if rays is None or len(rays) != 4:
+            raise ValueError("need the four ray planes ox, oy, dx, dy")
+        if not isinstance(b, _PolySet):
+            raise ValueError("need a poly_set() description")
+        planes = (C.c_void_p * 4)(*[_ptr_of(p) for p in rays])
+        self._check(self.lib.c2d_poly_ray_casts(self.h, planes, n_rays, C.byref(b), col_base, _ptr_of(out), C.c_void_p(stream)), "c2d_poly_ray_casts")
 
     def _contacts_of_list(self, name: str, arrays: Sequence, list_call, contacts_call, check_async: bool = False, manifolds: bool = False):
         """The one shape of the *_contacts_host functions: a count-only list call sizes the buffers, then the list call and the

@@ -1,0 +1,246 @@
+// c2d_ray.hip — ray queries for gfx950 (MI355X): for every segment o -> o + d of a list the polygon of a set B it touches first, and
+// where (c2d_poly_ray_casts; include/c2d.h "ray queries").  An R x M reduction: no R x M object is ever written.
+//
+// The rule (the contract of include/c2d.h).  Per ray, polygon j and live edge e < k, from vertex e at (x0, y0) to vertex (e + 1) mod k
+// at (x1, y1), everything binary32 and unfused, each product first and then the difference:
+//     ex = x1 - x0, ey = y1 - y0, wx = x0 - ox, wy = y0 - oy, den = dx * ey - dy * ex, tn = wx * ey - wy * ex, un = wx * dy - wy * dx
+//     usable:  den > 0 && 0 <= tn <= den && 0 <= un <= den,  or  den < 0 && den <= tn <= 0 && den <= un <= 0;  then t = tn / den, u = un / den
+//     inside:  no live tn is NaN, and exactly one sign occurs among the live tn; an inside polygon is the candidate t = 0
+// Polygons in order of j, per polygon the inside candidate and then the edges in order of e; a candidate replaces the best only under
+// strict t < best.  So the smallest t wins, among equal t the smallest j, then inside before edges, then the smallest e.
+//
+// Mapping: rays over lanes, polygons wave-uniform.  A block of 256 lanes owns 256 rays (four VGPRs) and a strip of consecutive column
+// tiles of B (c2d_ray_strips.hpp).  Per tile it stages 64 polygons in LDS: per live edge one 16-byte entry {x0, y0, ex, ey}, the edge
+// vector made once per polygon by the rule's own two subtractions, and the count.  The polygon index is wave-uniform, so the edge loop
+// runs to that polygon's own k and every LDS read is a broadcast; per edge a lane makes the three cross products and the compares,
+// and the two divisions become one (t alone) under a wave-uniform "some lane has a usable edge" branch.
+//
+// Three launches on the stream, no scratch, nothing read back:
+//   1. ray_init_kernel      every record's first eight bytes (poly, t) = all ones: "nothing yet"
+//   2. ray_main_kernel      per ray and strip the smallest (t, j) as a 64-bit key, t's bits (a -0 made +0) in the high word and
+//                           col_base + j in the low word: for 0 <= t <= 1 the order of the bits is the order of t.  The strips of a
+//                           row tile meet in an atomic minimum on those eight bytes, which does not depend on who arrives first.
+//   3. ray_finalise_kernel  one lane per ray: re-evaluates the winning polygon alone (at most 16 edges) by the rule's own sequence
+//                           and writes the whole record with one 16-byte store.
+#include "c2d_cross.hpp"
+#include "c2d_math.hpp"
+#include "c2d_poly_pair.hpp"   // PolySetDev, poly_set_check, poly_count
+#include "c2d_ray_strips.hpp"
+
+namespace c2d {
+
+static_assert(sizeof(c2d_ray_hit) == 16 && offsetof(c2d_ray_hit, poly) == 0 && offsetof(c2d_ray_hit, t) == 4 && offsetof(c2d_ray_hit, u) == 8 &&
+                  offsetof(c2d_ray_hit, edge) == 12 && offsetof(c2d_ray_hit, hit) == 14 && offsetof(c2d_ray_hit, flags) == 15,
+              "the kernels treat a ray hit as four dwords, (poly, t) being the 64-bit key");
+
+constexpr int kRayBlock = 256;   // rays per block: one per lane
+constexpr int kRayCols = 64;     // polygons of B per staged tile
+constexpr int kRayK = C2D_POLY_KMAX;
+constexpr unsigned long long kRayNoKey = ~0ull;
+constexpr uint32_t kRayNone16 = 0xFFFFu;
+
+struct RayPlanes {
+    const float* ox;
+    const float* oy;
+    const float* dx;
+    const float* dy;
+};
+
+// the three cross products of one (ray, edge)
+struct RayEdge {
+    float den, tn, un;
+};
+
+C2D_DEV RayEdge ray_edge(float ox, float oy, float dx, float dy, float x0, float y0, float ex, float ey)
+{
+    const float wx = x0 - ox, wy = y0 - oy;
+    return RayEdge{dx * ey - dy * ex, wx * ey - wy * ex, wx * dy - wy * dx};
+}
+
+// The rule's two cases folded into one by den's sign bit: with tn, un and den flipped where den is negative the second case reads as
+// the first (a zero of either sign passes both "<= 0" and ">= 0", before and after the flip; a NaN fails either way; |den| > 0 fails
+// for a den of +-0 or NaN).  Compares only, joined without branches: the boolean is the rule's for every bit pattern.
+C2D_DEV bool ray_edge_usable(const RayEdge& c)
+{
+    const uint32_t sgn = __float_as_uint(c.den) & 0x80000000u;
+    const float den = __uint_as_float(__float_as_uint(c.den) ^ sgn), tn = __uint_as_float(__float_as_uint(c.tn) ^ sgn),
+                un = __uint_as_float(__float_as_uint(c.un) ^ sgn);
+    return (int)(den > 0.0f) & (int)(tn >= 0.0f) & (int)(tn <= den) & (int)(un >= 0.0f) & (int)(un <= den);
+}
+
+__global__ __launch_bounds__(kRayBlock) void ray_init_kernel(size_t n_rays, c2d_ray_hit* __restrict__ out)
+{
+    const size_t step = (size_t)gridDim.x * kRayBlock;
+    for (size_t r = (size_t)blockIdx.x * kRayBlock + threadIdx.x; r < n_rays; r += step) reinterpret_cast<unsigned long long*>(out)[2 * r] = kRayNoKey;
+}
+
+// Block b: row tile b / strips, strip b % strips of the col_tiles column tiles of B.
+__global__ __launch_bounds__(kRayBlock) void ray_main_kernel(RayPlanes R, size_t n_rays, PolySetDev B, uint32_t col_base, size_t col_tiles, uint32_t strips,
+                                                             c2d_ray_hit* __restrict__ out, uint32_t* __restrict__ async_err)
+{
+    __shared__ __attribute__((aligned(16))) float4 s_edge[kRayCols][kRayK];   // 16 KiB: {x0, y0, ex, ey} of every live edge
+    __shared__ int s_k[kRayCols];                                             // the count; 0: not in any hit (out of range, or beyond n)
+    const uint32_t lane = threadIdx.x;
+    const size_t r = (size_t)(blockIdx.x / strips) * kRayBlock + lane;
+    const bool row_valid = r < n_rays;
+    // a lane without a ray carries NaN: every compare below fails, and it writes nothing
+    const float nan = __builtin_nanf("");
+    const float ox = row_valid ? R.ox[r] : nan, oy = row_valid ? R.oy[r] : nan, dx = row_valid ? R.dx[r] : nan, dy = row_valid ? R.dy[r] : nan;
+    size_t tile0, tiles;
+    ray_strip_tiles(col_tiles, (size_t)strips, (size_t)(blockIdx.x % strips), tile0, tiles);
+
+    float best_t = __builtin_inff();
+    uint32_t best_j = 0xFFFFFFFFu;
+#pragma unroll 1
+    for (size_t tile = tile0; tile < tile0 + tiles; tile++) {
+        const size_t j0 = tile * (size_t)kRayCols;
+        const uint32_t nj = (uint32_t)(B.n - j0 < (size_t)kRayCols ? B.n - j0 : (size_t)kRayCols);
+        __syncthreads();   // the previous tile's readers are done
+        {
+            const uint32_t c = lane & 63u, g = lane >> 6;
+            const size_t j = j0 + c;
+            int k = 0;
+            bool bad = false;
+            if (c < nj) {
+                bad = !poly_count(B, j, k);
+                k = bad ? 0 : k;
+            }
+            if (g == 0) {   // (one whole wave)
+                s_k[c] = k;
+                if (__ballot(bad) != 0ull && c == 0) __hip_atomic_fetch_or(async_err, C2D_ASYNC_ERR_POLY_K, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+#pragma unroll
+            for (int m = 0; m < kRayK / 4; m++) {
+                const int e = (int)g + 4 * m;
+                if (e < k) {   // e, e1 < k <= B.rows: inside the planes
+                    const int e1 = e + 1 < k ? e + 1 : 0;
+                    const float x0 = B.vx[(size_t)e * B.stride + j], y0 = B.vy[(size_t)e * B.stride + j];
+                    const float x1 = B.vx[(size_t)e1 * B.stride + j], y1 = B.vy[(size_t)e1 * B.stride + j];
+                    s_edge[c][e] = make_float4(x0, y0, x1 - x0, y1 - y0);
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (uint32_t c = 0; c < nj; c++) {
+            const int k = __builtin_amdgcn_readfirstlane(s_k[c]);
+            if (k == 0) continue;   // (wave-uniform)
+            bool pos = false, neg = false, unordered = false;
+            float tmin = __builtin_inff();
+#pragma unroll 1
+            for (int e = 0; e < k; e++) {
+                const float4 q = s_edge[c][e];   // (one address for the wave: a broadcast)
+                const RayEdge x = ray_edge(ox, oy, dx, dy, q.x, q.y, q.z, q.w);
+                pos |= x.tn > 0.0f;
+                neg |= x.tn < 0.0f;
+                unordered |= __builtin_isnan(x.tn);
+                const bool usable = ray_edge_usable(x);
+                if (__ballot(usable) != 0ull) {   // (wave-uniform) rare: a ray crosses few of the edges it looks at
+                    const float t = x.tn / x.den;
+                    tmin = (usable && t < tmin) ? t : tmin;
+                }
+            }
+            const bool inside = !unordered && (pos != neg);
+            const float tj = inside ? 0.0f : tmin;
+            const bool take = tj < best_t;   // strict: the first of equal polygons stays
+            best_t = take ? tj : best_t;
+            best_j = take ? (uint32_t)j0 + c : best_j;
+        }
+    }
+    if (row_valid && best_j != 0xFFFFFFFFu) {
+        const uint32_t tb = best_t == 0.0f ? 0u : __float_as_uint(best_t);   // -0 -> +0: then the bits order as t does
+        const unsigned long long key = ((unsigned long long)tb << 32) | (unsigned long long)(col_base + best_j);
+        __hip_atomic_fetch_min(reinterpret_cast<unsigned long long*>(out) + 2 * r, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// One lane per ray: the record of the key's polygon by the rule's own sequence (the key holds the winner's t and col_base + j).
+__global__ __launch_bounds__(kRayBlock) void ray_finalise_kernel(RayPlanes R, size_t n_rays, PolySetDev B, uint32_t col_base, c2d_ray_hit* __restrict__ out)
+{
+    const size_t step = (size_t)gridDim.x * kRayBlock;
+    for (size_t r = (size_t)blockIdx.x * kRayBlock + threadIdx.x; r < n_rays; r += step) {
+        const unsigned long long key = reinterpret_cast<const unsigned long long*>(out)[2 * r];
+        uint4 rec = make_uint4(0xFFFFFFFFu, __float_as_uint(__builtin_inff()), 0u, kRayNone16);   // nothing chosen
+        const uint32_t poly = (uint32_t)key;
+        const size_t j = (size_t)(poly - col_base);   // the main pass wrote it: j < B.n (checked all the same: nothing outside B is read)
+        if (key != kRayNoKey && j < B.n) {
+            const float ox = R.ox[r], oy = R.oy[r], dx = R.dx[r], dy = R.dy[r];
+            int k;
+            (void)poly_count(B, j, k);   // in range: the polygon was in a hit
+            k = k > B.rows ? B.rows : k;
+            bool pos = false, neg = false, unordered = false;
+            float best_t = __builtin_inff(), best_u = 0.0f;
+            uint32_t best_e = kRayNone16;
+            for (int e = 0; e < k; e++) {
+                const int e1 = e + 1 < k ? e + 1 : 0;
+                const float x0 = B.vx[(size_t)e * B.stride + j], y0 = B.vy[(size_t)e * B.stride + j];
+                const float x1 = B.vx[(size_t)e1 * B.stride + j], y1 = B.vy[(size_t)e1 * B.stride + j];
+                const RayEdge x = ray_edge(ox, oy, dx, dy, x0, y0, x1 - x0, y1 - y0);
+                pos |= x.tn > 0.0f;
+                neg |= x.tn < 0.0f;
+                unordered |= __builtin_isnan(x.tn);
+                if (ray_edge_usable(x)) {
+                    const float t = x.tn / x.den, u = x.un / x.den;
+                    const bool take = t < best_t;
+                    best_t = take ? t : best_t;
+                    best_u = take ? u : best_u;
+                    best_e = take ? (uint32_t)e : best_e;
+                }
+            }
+            if (!unordered && (pos != neg))
+                rec = make_uint4(poly, 0u, 0u, kRayNone16 | (1u << 16) | ((uint32_t)C2D_RAY_START_INSIDE << 24));
+            else if (best_e != kRayNone16)
+                rec = make_uint4(poly, __float_as_uint(best_t), __float_as_uint(best_u), best_e | (1u << 16));
+        }
+        reinterpret_cast<uint4*>(out)[r] = rec;   // d_out is 16-byte aligned (checked on the host)
+    }
+}
+
+}  // namespace c2d
+
+using namespace c2d;
+
+extern "C" {
+
+int c2d_poly_ray_casts(c2d_ctx* ctx, const float* const d_rays[4], size_t n_rays, const c2d_poly_set* b, size_t col_base, c2d_ray_hit* d_out,
+                       c2d_stream stream)
+{
+    const char* what = "c2d_poly_ray_casts";
+    if (!ctx) return C2D_ERR_INVALID_ARG;
+    if (!d_rays || !b || !d_out) return cross_fail(ctx, what, "NULL argument");
+    if (n_rays == 0) return C2D_OK;
+    PolySetDev B{nullptr, nullptr, nullptr, 0, 0, (int)b->rows};
+    if (b->n == 0) {   // (no plane is read: only `rows` is looked at)
+        if (b->rows < 1 || b->rows > (uint32_t)C2D_POLY_KMAX) return cross_fail(ctx, what, "set b: rows must be 1..C2D_POLY_KMAX");
+    } else if (int rc = poly_set_check(ctx, what, "b", b, B)) {
+        return rc;
+    }
+    for (int p = 0; p < 4; p++) {
+        if (!d_rays[p]) return cross_fail(ctx, what, "NULL ray plane");
+        if (reinterpret_cast<uintptr_t>(d_rays[p]) & 3u) return cross_fail(ctx, what, "ray planes must be 4-byte aligned");
+    }
+    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return cross_fail(ctx, what, "the output must be 16-byte aligned");
+    if (B.n > kIndexLimit || col_base > kIndexLimit - B.n) return cross_fail(ctx, what, "col_base + n_b must not exceed 2^32");
+    if (n_rays > kIndexLimit) return cross_fail(ctx, what, "n_rays must not exceed 2^32");
+
+    DeviceGuard dg(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const RayPlanes R{d_rays[0], d_rays[1], d_rays[2], d_rays[3]};
+    const int flat_grid = grid_for(n_rays, kRayBlock, 1 << 16);
+    hipLaunchKernelGGL(ray_init_kernel, dim3(flat_grid), dim3(kRayBlock), 0, s, n_rays, d_out);
+    C2D_LAUNCH_CHECK(ctx);
+    if (B.n != 0) {
+        const size_t row_tiles = (n_rays + kRayBlock - 1) / kRayBlock, col_tiles = (B.n + kRayCols - 1) / kRayCols;
+        const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 1;
+        const size_t strips = ray_strip_count(row_tiles, col_tiles, (size_t)cus * 8);   // eight blocks of 256 fill a CU
+        // row_tiles <= 2^24; with more than one strip, row_tiles * strips <= 8 * cus
+        hipLaunchKernelGGL(ray_main_kernel, dim3((unsigned)(row_tiles * strips)), dim3(kRayBlock), 0, s, R, n_rays, B, (uint32_t)col_base, col_tiles,
+                           (uint32_t)strips, d_out, ctx->d_async_err);
+        C2D_LAUNCH_CHECK(ctx);
+    }
+    hipLaunchKernelGGL(ray_finalise_kernel, dim3(flat_grid), dim3(kRayBlock), 0, s, R, n_rays, B, (uint32_t)col_base, d_out);
+    C2D_LAUNCH_CHECK(ctx);
+    return C2D_OK;
+}
+
+}  // extern "C"

@@ -575,6 +575,63 @@ int c2d_rect_pair_distances(c2d_ctx* ctx, const float* const d_a[8], size_t n_a,
                             size_t row_base, size_t col_base,
                             c2d_distance* d_out, c2d_stream stream);
 
+/* ---- ray queries: the nearest hit of every segment against a polygon set ---------
+ * An addition to 0.6 (c2d_version() stays 6), found by symbol lookup like the calls above.
+ *
+ * c2d_poly_ray_casts: for each of n_rays segments from o to o + d — a roadmap edge, the sweep of a reference point, a range-finder
+ * beam — WHICH polygon of the set b it touches first and WHERE: the polygon, the parameter t of the hit point o + t * d, the edge
+ * that was hit and the position u on it.  An R x M reduction: nothing of size n_rays x n_b is written, and no row is left for the
+ * caller to reduce.  d = (0, 0) is the point query "which polygon contains o".
+ *   d_rays     : four planes ox, oy, dx, dy, f32[n_rays] each; any 4-byte alignment.
+ *   b          : the polygon set, as for the cross forms: rows, stride, d_k == NULL (every polygon has `rows` vertices), shards by
+ *                pointer offset.  Padded vertex slots (index >= the polygon's count) are never interpreted.  A polygon with a vertex
+ *                count outside 1..rows is in no hit; the error is reported by the next c2d_stream_synchronize /
+ *                c2d_ctx_check_async, exactly as for the cross forms.
+ *   col_base   : the global index of B_0: a hit reports col_base + j.
+ *   d_out      : c2d_ray_hit[n_rays], 16-byte aligned; entry r is the record of ray r.  Records at or beyond n_rays are never touched.
+ *
+ * Arithmetic contract.  Everything is IEEE binary32, round to nearest, subnormals kept, nothing contracted in any
+ * build; division is correctly rounded.
+ *   per ray, polygon j and live edge e < k, the edge running from vertex e at (x0, y0) to vertex (e + 1) mod k at (x1, y1), each
+ *   product first, then the difference:
+ *               ex = x1 - x0, ey = y1 - y0, wx = x0 - ox, wy = y0 - oy,
+ *               den = dx * ey - dy * ex,  tn = wx * ey - wy * ex,  un = wx * dy - wy * dx.
+ *   usable edge decided without a division: den > 0 && tn >= 0 && tn <= den && un >= 0 && un <= den, or
+ *               den < 0 && tn <= 0 && tn >= den && un <= 0 && un >= den.  A NaN fails every compare; den == 0 (a parallel or a
+ *               zero-length edge) is unusable.  A usable edge has t = tn / den and u = un / den.
+ *   origin inside  polygon j when no live tn is NaN and exactly one sign occurs among the live tn: some tn > 0 or some tn < 0, but
+ *               not both.  So a zero-length edge (tn = +-0) is neutral, a polygon with k = 1 contains nothing, a clockwise polygon
+ *               works, and an origin on the boundary of a proper polygon counts as inside.  An inside polygon is the candidate t = 0.
+ *   the pick    polygons are visited in order of j, per polygon the inside candidate first and then the edges in order of e.  The
+ *               best starts at +inf with nothing chosen; a candidate replaces it only under strict t < best (compare and select), so
+ *               a NaN t never wins.  Equivalently: the smallest t wins, among equal t the smallest j, then inside before edges,
+ *               then the smallest e.  Ties are real: a ray through a vertex reaches the same t on two edges, duplicated obstacles
+ *               reach it on two polygons.
+ *   the record  an edge winner: hit = 1, poly = col_base + j, its t and u, edge = e, flags = 0.  An inside winner: hit = 1,
+ *               poly = col_base + j, t = 0, u = 0, edge = 0xFFFF, flags = C2D_RAY_START_INSIDE.  Nothing chosen: hit = 0,
+ *               poly = 0xFFFFFFFF, t = +inf, u = 0, edge = 0xFFFF, flags = 0.
+ * The implementation evaluates polygons in parallel; its results equal this sequential rule.  +0 and -0 compare equal in t and u.
+ * t is never NaN; u can be (inf / inf, with an infinite coordinate), and then any NaN stands for it.
+ * For non-convex input nothing is promised about what "inside" means, only the bits.
+ *
+ * n_rays == 0 is a no-op; n_b == 0 writes the no-hit record for every ray.  A NULL argument, `rows` out of range, a misaligned d_out,
+ * col_base + n_b > 2^32 and n_rays > 2^32 are refused (C2D_ERR_INVALID_ARG) before a device is touched.  The call is asynchronous
+ * on `stream` with no host synchronisation, and deterministic: two runs give the same bytes.  It uses no ctx scratch and is
+ * graph-capturable (three kernel nodes in a chain). */
+#define C2D_RAY_START_INSIDE 1   /* the origin lies in (or on) the winning polygon: t = 0, u = 0, edge = 0xFFFF */
+
+typedef struct c2d_ray_hit {     /* 16 bytes, 16-byte aligned output */
+    uint32_t poly;               /*  0: col_base + j of the winning polygon; 0xFFFFFFFF: none */
+    float    t;                  /*  4: hit point = o + t * d, 0 <= t <= 1; +inf: none */
+    float    u;                  /*  8: position on the winning edge, v[e] + u * (v[e+1] - v[e]); 0 when none / START_INSIDE */
+    uint16_t edge;               /* 12: 0..k-1; 0xFFFF: none or START_INSIDE */
+    uint8_t  hit;                /* 14 */
+    uint8_t  flags;              /* 15 */
+} c2d_ray_hit;
+
+int c2d_poly_ray_casts(c2d_ctx* ctx, const float* const d_rays[4] /* ox, oy, dx, dy: f32[n_rays] each */, size_t n_rays,
+                       const c2d_poly_set* b, size_t col_base, c2d_ray_hit* d_out, c2d_stream stream);
+
 /* ---- binned polygon batches ---------------------------------------------------
  * The padded layout above moves 16 vertex rows per polygon whatever the polygons are: with
  * K ~ U{3..16} that is 259 bytes per pair for 155 bytes of real vertices, and no kernel can
