@@ -2,6 +2,7 @@
 restatements of the contracts of include/c2d.h, pinned by tests/test_manifold_ref_cpu.py and tests/test_contact_ref_cpu.py — floats
 bit for bit (+0 and -0 equal, NaN equal to NaN), and the contact output equals c2d_poly_pair_contacts' on the same list byte for
 byte.  Both output buffers sit between guard bands that are checked afterwards."""
+import importlib.util
 import os
 import sys
 
@@ -18,6 +19,7 @@ import pair_list_harness as h  # noqa: E402
 from pair_list_harness import Uploaded, diag, local  # noqa: E402
 
 pytestmark = pytest.mark.gpu
+FUZZ_SEED = 2026
 LIST_LENGTHS = [0, 1, 63, 64, 65, 255, 256, 257, 4099]
 Q = h.MANIFOLDS
 assert_same = Q.assert_same
@@ -190,3 +192,20 @@ def test_grid_stride_second_trip(eng, batch, n_dev):
         tiles = raw[:reps * cases.BATCH].reshape(reps, cases.BATCH, -1)
         assert all((tiles[q] == first).all() for q in range(reps)), "a later repetition differs from the first"
         assert (raw[reps * cases.BATCH: bound] == first[:tail]).all(), "the last, partial repetition differs"
+
+
+def test_fuzzer_configurations_at_a_fixed_seed(eng):
+    """tests/tools/manifold_fuzz.py at a fixed seed, each configuration from its own stream (seed, index): sixteen configurations,
+    near-tied polygons among them"""
+    spec = importlib.util.spec_from_file_location("manifold_fuzz", os.path.join(HERE, "tools", "manifold_fuzz.py"))
+    fz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fz)
+    seen, compared = [], 0
+    for i in range(16):
+        ok, (desc, n) = fz.one(eng, np.random.default_rng([FUZZ_SEED, i]), i)
+        assert ok, desc
+        seen.append(desc)
+        compared += n
+    assert any("near-ties, polygons" in d for d in seen) and any("B = A" in d for d in seen), seen
+    assert compared > 1000
+    eng.check_async()

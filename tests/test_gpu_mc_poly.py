@@ -3,6 +3,7 @@ hit counts, stop points and output rows must equal the CPU oracle's restatement 
 polygons": sample_rectangle utils.cu:144-157 and the loop of compute_collision_probability.cu:119-139 generalised, the
 interval test of utils.cu:172-180 on true normals) bit for bit; probabilities are checked against closed forms with the
 tolerance BASELINE.json states (1e-3 at 1e8 samples)."""
+import importlib.util
 import math
 import os
 
@@ -11,6 +12,7 @@ import pytest
 from scipy.stats import norm
 
 pytestmark = pytest.mark.gpu
+FUZZ_SEED = 2026
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 W, H = 4.07, 1.74
 
@@ -285,3 +287,18 @@ def test_mc_poly_scenes_argument_errors(eng, pkg, wl):
     with pytest.raises(pkg.C2DError):
         eng.mc_poly_scenes(sc["robot"], d_p, 4, d_s, 4, d_sc, 8, **dict(ok, max_samples=0))
     assert eng.mc_poly_scenes(sc["robot"], d_p, 4, d_s, 4, d_sc, 0, **ok) == (0, 0)  # nothing to do
+
+
+def test_fuzzer_configurations_at_a_fixed_seed(eng, oracle):   # (`oracle`: sizes the OpenMP team to the box's CPU share)
+    """tests/tools/mc_poly_fuzz.py at a fixed seed, each configuration from its own stream (seed, index): sixteen configurations, among
+    them scenes whose estimate is neither 0 nor 1"""
+    spec = importlib.util.spec_from_file_location("mc_poly_fuzz", os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "mc_poly_fuzz.py"))
+    fz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fz)
+    samples, mixed = 0, 0
+    for i in range(16):
+        ok, n = fz.one(eng, np.random.default_rng([FUZZ_SEED, i]), i)
+        assert ok, f"configuration {i}"
+        samples += n
+        mixed += int(((fz.LAST["hits"] > 0) & (fz.LAST["hits"] < fz.LAST["samples"])).sum())
+    assert samples > 100_000 and mixed > 0

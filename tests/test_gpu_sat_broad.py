@@ -1,7 +1,9 @@
 """GPU tests of the broad-phase rectangle pair search (c2d_sat_rect_broad_pairs): on every input its list and count must equal
 c2d_sat_rect_cross_pairs' (row_base = col_base = 0), bit for bit — the cross list is itself checked against the pairwise path
 by test_gpu_sat_cross.py.  Up to a few million pairs the CPU oracle is checked directly as well."""
+import importlib.util
 import os
+import re
 import subprocess
 import sys
 
@@ -12,6 +14,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_PAIRS = 3_000_000
 SENTINEL = np.uint64(0xA5A5A5A5A5A5A5A5)
+FUZZ_SEED = 2026
 
 
 def rect_set(oracle, wl, n, seed, extent):
@@ -272,3 +275,21 @@ def test_graph_capture():
     out = subprocess.run([sys.executable, os.path.join(HERE, "broad_graph_check.py")], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-1500:]
     assert "broad graph ok" in out.stdout
+
+
+def test_fuzzer_configurations_at_a_fixed_seed(eng, oracle):
+    """tests/tools/broad_fuzz.py at a fixed seed, each configuration from its own stream (seed, index): sixteen configurations, chosen so
+    that they hold what the tool is for — a pile whose rows pass 512 hits, wild objects, self mode"""
+    spec = importlib.util.spec_from_file_location("broad_fuzz", os.path.join(HERE, "tools", "broad_fuzz.py"))
+    fz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fz)
+    seen, compared = [], 0
+    for i in range(16):
+        ok, (desc, n) = fz.one(eng, np.random.default_rng([FUZZ_SEED, i]), i, None, oracle)
+        assert ok, desc
+        seen.append(desc)
+        compared += n
+    assert any(int(m) > 512 for d in seen for m in re.findall(r"pile (\d+)", d)), seen
+    assert any(re.search(r"wild [1-9]", d) for d in seen) and any("self mode" in d for d in seen), seen
+    assert compared > 1000
+    eng.check_async()

@@ -2,7 +2,9 @@
 boolean of the pairwise path on (A_i, B_j), bit for bit.  The reference materialises the pairs (np.repeat / np.tile) and
 runs the CPU oracle on them up to a few million pairs; above that the same pairs go through the pairwise bit-mask kernel
 (c2d_sat_rect_pairs_verts_mask, itself checked against the oracle by test_gpu_sat.py) in chunks."""
+import importlib.util
 import os
+import re
 import subprocess
 import sys
 
@@ -14,6 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_PAIRS = 4_000_000       # above this the reference is the pairwise GPU kernel
 SIZES = [1, 63, 64, 65, 255, 256, 257, 1000, 4099]
 SENTINEL = np.uint64(0xA5A5A5A5A5A5A5A5)
+FUZZ_SEED = 2026
 
 
 def rect_set(oracle, wl, n, seed, extent=8.0):
@@ -352,3 +355,24 @@ def test_mask_form_graph_capture():
     out = subprocess.run([sys.executable, os.path.join(HERE, "cross_graph_check.py")], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     assert "cross graph ok" in out.stdout
+
+
+def test_fuzzer_configurations_at_a_fixed_seed(eng, oracle):
+    """tests/tools/cross_fuzz.py at a fixed seed, each configuration from its own stream (seed, index): sixteen configurations, chosen so
+    that they hold what the tool is for — the upper triangle with unequal bases, a list capacity below the total, a count-only call,
+    A and B the same memory, a set with non-finite coordinates, ld_words beyond the row's words"""
+    spec = importlib.util.spec_from_file_location("cross_fuzz", os.path.join(HERE, "tools", "cross_fuzz.py"))
+    fz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fz)
+    seen, compared = [], 0
+    for i in range(16):
+        ok, (desc, n) = fz.one(eng, np.random.default_rng([FUZZ_SEED, i]), i, None, oracle)
+        assert ok, desc
+        seen.append(desc)
+        compared += n
+    assert any(re.search(r"upper True, bases \d+, \d+ \(unequal\)", d) for d in seen), seen           # a shifted diagonal
+    assert any("below the total" in d for d in seen) and any("count-only list call" in d for d in seen), seen
+    assert any("the same memory" in d for d in seen) and any("non-finite" in d for d in seen), seen
+    assert any(re.search(r"ld_words \d+ > words", d) for d in seen), seen
+    assert compared > 1000
+    eng.check_async()

@@ -4,7 +4,9 @@ the pairwise polygon path on (A_i, B_j), bit for bit.  The reference materialise
 (c2d_sat_poly_pairs_rows, itself pinned to the oracle by test_gpu_sat.py) in chunks.  Never the code under test.  Every mask and
 list buffer handed to the library sits between guard rows that are checked afterwards."""
 import ctypes as C
+import importlib.util
 import os
+import re
 import subprocess
 import sys
 
@@ -18,6 +20,7 @@ ORACLE_PAIRS = 4_000_000       # above this the reference is the pairwise GPU ke
 CHUNK = 1_000_000              # materialised pairs per reference chunk (about 260 MB of host memory at 16 rows)
 SIZES = [1, 63, 64, 65, 255, 256, 257, 1000, 4099]
 SENTINEL = np.uint64(0xA5A5A5A5A5A5A5A5)
+FUZZ_SEED = 2026
 
 
 def padded(s, rows):
@@ -541,3 +544,25 @@ def test_mask_form_graph_capture():
     out = subprocess.run([sys.executable, os.path.join(HERE, "poly_cross_graph_check.py")], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     assert "poly cross graph ok" in out.stdout
+
+
+def test_fuzzer_configurations_at_a_fixed_seed(eng, oracle):
+    """tests/tools/poly_cross_fuzz.py at a fixed seed, each configuration from its own stream (seed, index): sixteen configurations, chosen
+    so that they hold what the tool is for — the upper triangle with unequal bases, a list capacity below the total, a count-only call,
+    A and B the same memory, non-finite real vertices, ld_words beyond the row's words, a vertex count out of range, d_k == NULL"""
+    spec = importlib.util.spec_from_file_location("poly_cross_fuzz", os.path.join(HERE, "tools", "poly_cross_fuzz.py"))
+    fz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fz)
+    seen, compared = [], 0
+    for i in range(16):
+        ok, (desc, n) = fz.one(eng, np.random.default_rng([FUZZ_SEED, i]), i, None, oracle)
+        assert ok, desc
+        seen.append(desc)
+        compared += n
+    assert any(re.search(r"upper True, bases \d+, \d+ \(unequal\)", d) for d in seen), seen           # a shifted diagonal
+    assert any("below the total" in d for d in seen) and any("count-only list call" in d for d in seen), seen
+    assert any("the same memory" in d for d in seen) and any("non-finite" in d for d in seen), seen
+    assert any(re.search(r"ld_words \d+ > words", d) for d in seen), seen
+    assert any(re.search(r"bad count in (A|B|both)", d) for d in seen) and any(re.search(r"d_k (NULL /|\w+ / NULL)", d) for d in seen), seen
+    assert compared > 1000
+    eng.check_async()

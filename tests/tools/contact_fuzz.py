@@ -37,6 +37,9 @@ pbf = _tool("poly_broad_fuzz")      # its random sets and its upload
 fuzz_seed = _tool("fuzz_seed")
 
 
+LAST = {}   # hits / misses of the last configuration, for the exploring leg's "not vacuous" check
+
+
 def random_list(rng, n_a, n_b, length):
     """row-major, as a list call emits it, with a few entries out of their set"""
     flat = np.sort(rng.integers(0, n_a * n_b, length))
@@ -120,6 +123,7 @@ def one(eng, rng, idx, announce=None):
     got = raw[1:1 + bound]
     untouched = (np.delete(raw.view(np.uint8).reshape(-1, 16), np.arange(1, 1 + bound), axis=0) == 0xA5).all()
     ok = bool(ref.same(got, want).all()) and bool(untouched) and reported == bool((want["flags"] & ref.BAD_PAIR).any())
+    LAST.update(hits=int((want["hit"] != 0).sum()), misses=int((want["hit"] == 0).sum()))
     if not ok:
         print(f"MISMATCH {desc}: {int((~ref.same(got, want)).sum())} contacts differ, untouched {bool(untouched)}, error reported {reported}")
     return ok, (desc, bound)

@@ -36,6 +36,9 @@ contact_fuzz = _tool("contact_fuzz")      # its random list
 fuzz_seed = _tool("fuzz_seed")
 
 
+LAST = {}   # hits / misses of the last configuration, for the exploring leg's "not vacuous" check
+
+
 def random_quads(rng, n):
     q = (rng.uniform(-3, 3, (1, n)) + rng.uniform(-2, 2, (8, n))).astype(np.float32)
     if rng.random() < 0.33:
@@ -96,6 +99,7 @@ def one(eng, rng, idx, announce=None):
     got = raw[1:1 + bound]
     untouched = (np.delete(raw.view(np.uint8).reshape(-1, 32), np.arange(1, 1 + bound), axis=0) == 0xA5).all()
     ok = bool(ref.same(got, want).all()) and bool(untouched) and reported == bool((want["flags"] & ref.BAD_PAIR).any())
+    LAST.update(hits=int((want["hit"] != 0).sum()), misses=int((want["hit"] == 0).sum()))
     if not ok:
         print(f"MISMATCH {desc}: {int((~ref.same(got, want)).sum())} records differ, untouched {bool(untouched)}, error reported {reported}")
     return ok, (desc, bound)

@@ -18,7 +18,11 @@ wl = importlib.import_module("c2d_amd.workloads")
 from oracle import cpu as oracle  # noqa: E402
 
 
-def one(eng, rng, idx):
+LAST = {}   # per-scene hits and samples of the last configuration, for the exploring leg's "not vacuous" check
+
+
+def one(eng, rng, idx, announce=None):
+    """One configuration; `announce(text)` is called with its description BEFORE any GPU work."""
     nrng = np.random.Generator(np.random.Philox(int(rng.integers(1 << 40))))
     ntab = int(rng.integers(1, 120))
     kmin = int(rng.choice([1, 2, 3, 3, 3]))
@@ -57,6 +61,8 @@ def one(eng, rng, idx):
     nb = int(rng.integers(2, 6))
     bins = np.concatenate([[0.0], np.sort(rng.uniform(0.001, 0.9, nb - 2)), [1.0]]).astype(np.float32)
     acc = np.sort(rng.uniform(5e-4, 5e-2, nb - 1)).astype(np.float32)
+    if announce is not None:
+        announce(f"config {idx}: scenes {ns} tables {ntab} ka {ka} k {kmin}..{kmax} scale {scale} schedule {schedule} max_samples {max_samples} seed {seed} base {base}")
     h_ref, u_ref, rows_ref, tot_ref = oracle.mc_poly_scenes(robot, poses, sds, scenes, bins, acc, max_samples, seed, base, schedule=schedule)
     d_p, d_s, d_sc = eng.to_device(poses), eng.to_device(sds), eng.to_device(scenes)
     d_h, d_u, d_r = eng.zeros(ns, np.uint32), eng.zeros(ns, np.uint32), eng.empty(ns, pkg.ROW_DT)
@@ -76,6 +82,7 @@ def one(eng, rng, idx):
     ok = ok and int(d_hits.get()[0]) == oracle.mc_poly_pair(robot, pos, theta, obstacle, sd, seed, base + j, begin, count)
     for a in (d_p, d_s, d_sc, d_h, d_u, d_r, d_hits):
         a.free()
+    LAST.update(hits=h_ref, samples=u_ref)
     if not ok:
         print(f"MISMATCH config {idx}: scenes {ns} tables {ntab} ka {ka} k {kmin}..{kmax} scale {scale} schedule {schedule} max_samples {max_samples}")
     return ok, tot_ref + count

@@ -18,6 +18,9 @@ pkg = load_package()
 wl = importlib.import_module("c2d_amd.workloads")
 
 
+LAST = {}   # hits / misses of the last configuration, for the exploring leg's "not vacuous" check
+
+
 def random_set(rng, n, rows):
     kmax = int(rng.integers(1, rows + 1))
     kmin = int(rng.integers(1, kmax + 1))
@@ -85,6 +88,7 @@ def one(eng, rng, idx, announce=None):
     for x in list(keep) + [d_cnt, d_want, d_got]:
         x.free()
     ok = want_n == got_n and np.array_equal(want, got)
+    LAST.update(hits=want_n, misses=(n_a * sb.n if not upper else sum(max(0, sb.n - 1 - i) for i in range(n_a))) - want_n)
     if not ok:
         print(f"MISMATCH {desc}: cross counts {want_n}, broad {got_n}; {int((want != got).any(1).sum())} list entries differ")
     return ok, (desc, want_n)

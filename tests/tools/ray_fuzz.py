@@ -36,6 +36,9 @@ pbf = _tool("poly_broad_fuzz")      # its random sets and its upload
 fuzz_seed = _tool("fuzz_seed")
 
 
+LAST = {}   # hits / misses of the last configuration, for the exploring leg's "not vacuous" check
+
+
 def random_rays(rng, n, b):
     """n rays around the set b: a third start anywhere, the others on a vertex, on the middle of an edge or at a vertex mean"""
     vx, vy, k = b
@@ -119,6 +122,7 @@ def one(eng, rng, idx, announce=None):
     got = raw[1:1 + n_rays]
     untouched = (np.delete(raw.view(np.uint8).reshape(-1, 16), np.arange(1, 1 + n_rays), axis=0) == 0xA5).all()
     ok = bool(ref.same(got, want).all()) and bool(untouched) and reported == bool(bad)
+    LAST.update(hits=int((want["hit"] != 0).sum()), misses=int((want["hit"] == 0).sum()))
     if not ok:
         print(f"MISMATCH {desc}: {int((~ref.same(got, want)).sum())} records differ, untouched {bool(untouched)}, error reported {reported}")
     return ok, (desc, n_rays)
