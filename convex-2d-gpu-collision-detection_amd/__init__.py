@@ -36,6 +36,9 @@ from .binding import (  # noqa: F401
     DISTANCE_BAD_PAIR,
     RAY_HIT_DT,
     RAY_START_INSIDE,
+    SWEEP_DT,
+    SWEEP_START_OVERLAP,
+    SWEEP_BAD_PAIR,
     make_polygon,
     library_path,
     load_library,

@@ -45,6 +45,10 @@ DISTANCE_EDGE_ON_B, DISTANCE_INTERIOR, DISTANCE_NO_CANDIDATE, DISTANCE_BAD_PAIR 
 RAY_HIT_DT = np.dtype([("poly", "<u4"), ("t", "<f4"), ("u", "<f4"), ("edge", "<u2"), ("hit", "u1"), ("flags", "u1")])   # c2d_ray_hit
 RAY_START_INSIDE = 1
 
+# swept queries (include/c2d.h, "swept queries: time of impact for listed pairs in linear motion")
+SWEEP_DT = np.dtype([("toi", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("axis", "<u2"), ("hit", "u1"), ("flags", "u1")])   # c2d_sweep
+SWEEP_START_OVERLAP, SWEEP_BAD_PAIR = 1, 2
+
 
 class C2DError(RuntimeError):
     def __init__(self, status: int, what: str, detail: str = ""):
@@ -185,6 +189,10 @@ _SIGNATURES = {
     "c2d_rect_pair_distances": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                           C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_ray_casts": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(_PolySet), C.c_size_t, C.c_void_p, C.c_void_p]),
+    "c2d_poly_pair_sweeps": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "c2d_rect_pair_sweeps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_bins_create": (C.c_int, [C.c_void_p, C.POINTER(_PolyBin), C.c_size_t, C.POINTER(C.c_void_p)]),
     "c2d_poly_bins_from_padded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "c2d_poly_bins_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -805,6 +813,38 @@ class Engine:
             raise ValueError("need a poly_set() description")
         planes = (C.c_void_p * 4)(*[_ptr_of(p) for p in rays])
         self._check(self.lib.c2d_poly_ray_casts(self.h, planes, n_rays, C.byref(b), col_base, _ptr_of(out), C.c_void_p(stream)), "c2d_poly_ray_casts")
+
+    # -- swept queries (include/c2d.h "swept queries: time of impact for listed pairs in linear motion") -----------------
+    @staticmethod
+    def _motion(motion, which: str):
+        """a set's motion -> its two plane pointers: None (the set stands still) or the pair (dx, dy) of device f32[n] planes"""
+        if motion is None:
+            return None, None
+        if isinstance(motion, (str, bytes)) or not hasattr(motion, "__len__") or len(motion) != 2 or motion[0] is None or motion[1] is None:
+            raise ValueError(f"{which}_motion is None or the two planes (dx, dy)")
+        return _ptr_of(motion[0]), _ptr_of(motion[1])
+
+    def poly_pair_sweeps(self, a: _PolySet, b: _PolySet, pairs, n_pairs: int, out, a_motion=None, b_motion=None, n_pairs_dev=None, row_base: int = 0,
+                         col_base: int = 0, stream: int = 0):
+        """c2d_poly_pair_sweeps: out[p] (SWEEP_DT[n_pairs], 16-byte aligned) = whether the two polygons of list entry p touch while
+        both translate over the step t = 0 .. 1, the first time they do and the normal from A to B there; a_motion / b_motion: the
+        pair (dx, dy) of device planes f32[n] of a set's displacements, or None for a set that stands still; the list, n_pairs_dev
+        and the bases as for poly_pair_contacts"""
+        if not isinstance(a, _PolySet) or not isinstance(b, _PolySet):
+            raise ValueError("need two poly_set() descriptions")
+        adx, ady = self._motion(a_motion, "a")
+        bdx, bdy = self._motion(b_motion, "b")
+        self._check(self.lib.c2d_poly_pair_sweeps(self.h, C.byref(a), C.byref(b), adx, ady, bdx, bdy, _ptr_of(pairs), n_pairs, _ptr_of(n_pairs_dev), row_base,
+                                                  col_base, _ptr_of(out), C.c_void_p(stream)), "c2d_poly_pair_sweeps")
+
+    def rect_pair_sweeps(self, a_planes: Sequence, n_a: int, b_planes: Sequence, n_b: int, pairs, n_pairs: int, out, a_motion=None, b_motion=None,
+                         n_pairs_dev=None, row_base: int = 0, col_base: int = 0, stream: int = 0):
+        """c2d_rect_pair_sweeps: poly_pair_sweeps for two rectangle sets given as 8 vertex planes each"""
+        a, b = self._cross_planes(a_planes, b_planes)
+        adx, ady = self._motion(a_motion, "a")
+        bdx, bdy = self._motion(b_motion, "b")
+        self._check(self.lib.c2d_rect_pair_sweeps(self.h, a, n_a, b, n_b, adx, ady, bdx, bdy, _ptr_of(pairs), n_pairs, _ptr_of(n_pairs_dev), row_base,
+                                                  col_base, _ptr_of(out), C.c_void_p(stream)), "c2d_rect_pair_sweeps")
 
     def _contacts_of_list(self, name: str, arrays: Sequence, list_call, contacts_call, check_async: bool = False, manifolds: bool = False):
         """The one shape of the *_contacts_host functions: a count-only list call sizes the buffers, then the list call and the

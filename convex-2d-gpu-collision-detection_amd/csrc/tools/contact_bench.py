@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Developer tool: the contact queries (c2d_poly_pair_contacts / c2d_rect_pair_contacts, and c2d_poly_pair_manifolds) and the distance queries
-(c2d_poly_pair_distances / c2d_rect_pair_distances) next to the list calls that feed them, one JSON line per configuration.  GPU only, no oracle (tests/test_gpu_contacts.py checks the values).
+"""Developer tool: the contact queries (c2d_poly_pair_contacts / c2d_rect_pair_contacts, and c2d_poly_pair_manifolds), the distance queries
+(c2d_poly_pair_distances / c2d_rect_pair_distances) and the swept queries (c2d_poly_pair_sweeps / c2d_rect_pair_sweeps) next to the list calls that feed them, one JSON line per configuration.  GPU only, no oracle (tests/test_gpu_contacts.py checks the values).
 
 Scenes: the sparse self-collision scenes of poly_broad_bench.py (K ~ U{3..16}, extent 200 * sqrt(N / 32768)) and broad_bench.py
 (rectangles of random_obb_pose_planes at the same density), C2D_CROSS_UPPER with B = A; and one dense polygon list of about 1e7
@@ -15,8 +15,13 @@ median of --reps (>= 7) after a warm-up:
   distances_ms    the distances call alone on the same list in the same run; distances_over_contacts its ratio to contacts_ms,
                   distances_per_s listed pairs / distances_ms, separated_share the share of the list that is not hit (a wave of
                   hit pairs skips the candidate loops: the broad lists are all hit, the dense list is mostly separated)
+  sweeps_ms       the sweeps call alone on the same list in the same run, both sets moving by up to +---motion per component (seeded);
+                  sweeps_over_contacts its ratio to contacts_ms, sweeps_per_s listed pairs / sweeps_ms, start_share / moving_hit_share
+                  the shares of the list that start in overlap / first touch during the step (a wave of start-overlap pairs skips
+                  the axis walk: the broad lists are all start overlap); sweeps_still_ms the same call with no motion planes (every
+                  wave skips the walk: the pairwise test, the gather and the store alone)
 The kernels' own times come from a separate run under `rocprofv3 --kernel-trace --stats -- python3 contact_bench.py --once`.
-usage: contact_bench.py [--n 131072] [--dense-n 3163] [--reps 7] [--once]"""
+usage: contact_bench.py [--n 131072] [--dense-n 3163] [--reps 7] [--motion 2.0] [--once]"""
 import argparse
 import importlib
 import json
@@ -39,6 +44,7 @@ def main():
     ap.add_argument("--n", type=int, default=131072)
     ap.add_argument("--dense-n", type=int, default=3163)
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--motion", type=float, default=2.0)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     reps = max(7, args.reps)
@@ -61,7 +67,14 @@ def main():
             ms.append(e0.elapsed_time(e1))
         return float(np.median(ms))
 
-    def report(config, n, list_call, contacts_call, total, extra=None, manifolds_call=None, distances_call=None, distances_out=None):
+    def motion_planes(count, seed):
+        """dx, dy f32[count] of one set, uniform in +-args.motion -> the two tensors (kept alive by the caller) and their pointers"""
+        rng = np.random.default_rng(seed)
+        m = [torch.from_numpy(rng.uniform(-args.motion, args.motion, count).astype(np.float32)).to(dev) for _ in range(2)]
+        return m, (m[0].data_ptr(), m[1].data_ptr())
+
+    def report(config, n, list_call, contacts_call, total, extra=None, manifolds_call=None, distances_call=None, distances_out=None, sweeps_call=None,
+               sweeps_still_call=None, sweeps_out=None):
         def both():
             if list_call is not None:
                 list_call()
@@ -73,6 +86,9 @@ def main():
                 manifolds_call()
             if distances_call is not None:
                 distances_call()
+            if sweeps_call is not None:
+                sweeps_call()
+                sweeps_still_call()
             stream.synchronize()
             return
         out = {"config": config, "n": n, "hits": total, "reps": reps}
@@ -91,6 +107,16 @@ def main():
             out["distances_per_s"] = round(total / (out["distances_ms"] * 1e-3), 0)
             if total:     # byte 24 of a record is `hit`
                 out["separated_share"] = round(1.0 - float(distances_out[:total, 24].float().mean().item()), 4)
+        if sweeps_call is not None:
+            out["sweeps_ms"] = round(timed(sweeps_call), 4)
+            out["sweeps_over_contacts"] = round(out["sweeps_ms"] / out["contacts_ms"], 3)
+            out["sweeps_per_s"] = round(total / (out["sweeps_ms"] * 1e-3), 0)
+            if total:     # byte 14 of a record is `hit`, byte 15 `flags` (1: START_OVERLAP)
+                start = sweeps_out[:total, 15] == 1
+                out["start_share"] = round(float(start.float().mean().item()), 4)
+                out["moving_hit_share"] = round(float(((sweeps_out[:total, 14] == 1) & ~start).float().mean().item()), 4)
+            out["sweeps_still_ms"] = round(timed(sweeps_still_call), 4)
+            out["motion"] = args.motion
         out.update(extra or {})
         print(json.dumps(out), flush=True)
 
@@ -124,11 +150,21 @@ def main():
     def poly_distances():
         eng.poly_pair_distances(s, s, pairs.data_ptr(), total, dist.data_ptr(), n_pairs_dev=cnt.data_ptr(), stream=sh)
 
+    swp = torch.empty((max(total, 1), 16), dtype=torch.uint8, device=dev)
+    keep_m, mot = motion_planes(n, 0xC50A)
+
+    def poly_sweeps():
+        eng.poly_pair_sweeps(s, s, pairs.data_ptr(), total, swp.data_ptr(), a_motion=mot, b_motion=mot, n_pairs_dev=cnt.data_ptr(), stream=sh)
+
+    def poly_sweeps_still():
+        eng.poly_pair_sweeps(s, s, pairs.data_ptr(), total, swp.data_ptr(), n_pairs_dev=cnt.data_ptr(), stream=sh)
+
     poly_list()
-    report("sparse_polygons_self_upper", n, poly_list, poly_contacts, total, {"extent": round(float(extent), 2)}, poly_manifolds, poly_distances, dist)
+    report("sparse_polygons_self_upper", n, poly_list, poly_contacts, total, {"extent": round(float(extent), 2)}, poly_manifolds, poly_distances, dist,
+           poly_sweeps, poly_sweeps_still, swp)
     hit_share = float((out.view(torch.int32)[:total, 3] >> 16 & 1).float().mean().item()) if total and not args.once else None
     assert hit_share in (None, 1.0), "a listed pair without `hit`"
-    del pairs, out, man, dist
+    del pairs, out, man, dist, swp
 
     # -- sparse rectangles, self-collision -------------------------------------------------------------------------------
     poses = wl.random_obb_pose_planes(n, seed=0xB0AD, extent=extent)
@@ -155,9 +191,18 @@ def main():
     def rect_distances():
         eng.rect_pair_distances(pp, n, pp, n, rpairs.data_ptr(), rtotal, rdist.data_ptr(), n_pairs_dev=cnt.data_ptr(), stream=sh)
 
+    rswp = torch.empty((max(rtotal, 1), 16), dtype=torch.uint8, device=dev)
+
+    def rect_sweeps():
+        eng.rect_pair_sweeps(pp, n, pp, n, rpairs.data_ptr(), rtotal, rswp.data_ptr(), a_motion=mot, b_motion=mot, n_pairs_dev=cnt.data_ptr(), stream=sh)
+
+    def rect_sweeps_still():
+        eng.rect_pair_sweeps(pp, n, pp, n, rpairs.data_ptr(), rtotal, rswp.data_ptr(), n_pairs_dev=cnt.data_ptr(), stream=sh)
+
     rect_list()
-    report("sparse_rectangles_self_upper", n, rect_list, rect_contacts, rtotal, {"extent": round(float(extent), 2)}, None, rect_distances, rdist)
-    del rpairs, rout, rdist
+    report("sparse_rectangles_self_upper", n, rect_list, rect_contacts, rtotal, {"extent": round(float(extent), 2)}, None, rect_distances, rdist,
+           rect_sweeps, rect_sweeps_still, rswp)
+    del rpairs, rout, rdist, rswp
 
     # -- one dense polygon list: every pair of two sets ------------------------------------------------------------------
     m = args.dense_n
@@ -180,7 +225,17 @@ def main():
     def dense_distances():      # (into the manifolds' buffer: the same 32 bytes per entry, and the manifolds leg is over by then)
         eng.poly_pair_distances(sa, sb, dense.data_ptr(), m * m, dman.data_ptr(), stream=sh)
 
-    report("dense_polygon_list", m, None, dense_contacts, m * m, None, dense_manifolds, dense_distances, dman)
+    dswp = torch.empty((m * m, 16), dtype=torch.uint8, device=dev)
+    keep_a, mot_a = motion_planes(m, 0xC50B)
+    keep_b, mot_b = motion_planes(m, 0xC50C)
+
+    def dense_sweeps():
+        eng.poly_pair_sweeps(sa, sb, dense.data_ptr(), m * m, dswp.data_ptr(), a_motion=mot_a, b_motion=mot_b, stream=sh)
+
+    def dense_sweeps_still():
+        eng.poly_pair_sweeps(sa, sb, dense.data_ptr(), m * m, dswp.data_ptr(), stream=sh)
+
+    report("dense_polygon_list", m, None, dense_contacts, m * m, None, dense_manifolds, dense_distances, dman, dense_sweeps, dense_sweeps_still, dswp)
     eng.check_async()
     eng.close()
 

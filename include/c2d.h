@@ -632,6 +632,73 @@ typedef struct c2d_ray_hit {     /* 16 bytes, 16-byte aligned output */
 int c2d_poly_ray_casts(c2d_ctx* ctx, const float* const d_rays[4] /* ox, oy, dx, dy: f32[n_rays] each */, size_t n_rays,
                        const c2d_poly_set* b, size_t col_base, c2d_ray_hit* d_out, c2d_stream stream);
 
+/* ---- swept queries: time of impact for listed pairs in linear motion ------------
+ * Additions to 0.6 (c2d_version() stays 6), found by symbol lookup like the calls above.
+ *
+ * c2d_poly_pair_sweeps / c2d_rect_pair_sweeps: for each pair of a list, with BOTH shapes translating over the step t = 0 .. 1,
+ * whether they touch during the step, the first time at which they do, and the unit normal from A towards B at that touch with the
+ * axis it came from.  (Testing sampled instants tunnels: a grazing pass falls between two samples.)  The sets, d_pairs, d_n_pairs,
+ * the bases, the records at or beyond min(n_pairs, *d_n_pairs) (untouched), bad pairs, the asynchronous error word, n_pairs == 0
+ * (a no-op), the refused arguments, "no ctx scratch", the single launch, `stream` and graph capture are those of
+ * c2d_poly_pair_distances / c2d_rect_pair_distances, that is, of the contact queries above.
+ *   d_a_dx, d_a_dy : f32[n_a] each, 4-byte aligned: the displacement of object i of A over the step.  The index is LOCAL, like the
+ *                    vertex planes': a shard passes the motion planes offset by the same amount as its vertices.
+ *   d_b_dx, d_b_dy : the same for B.
+ *                    A set whose two planes are both NULL stands still.  Exactly one NULL plane of a set is refused
+ *                    (C2D_ERR_INVALID_ARG), before the other checks.
+ *   d_out          : c2d_sweep[n_pairs], 16-byte aligned; entry p is the record of list entry p.
+ *
+ * Arithmetic contract.  Everything is IEEE binary32, round to nearest, subnormals kept, nothing contracted in any
+ * build; division and square root are correctly rounded.
+ *   hit0        the pairwise boolean itself (c2d_sat_poly_pairs_rows / c2d_sat_rect_pairs_verts of the same build on the pair as it
+ *               stands at t = 0): exactly the `hit` of the contact calls.  When hit0: toi = 0, normal (0, 0), axis = 0xFFFF, hit = 1,
+ *               flags = C2D_SWEEP_START_OVERLAP (how deep and along which normal is the contact calls' business).
+ *   motion      rx = b_dx[j] - a_dx[i], ry = b_dy[j] - a_dy[i]: the displacement of B relative to A.  A set that stands still
+ *               contributes +0.
+ *   axes        the axes, their order and the intervals [minA, maxA], [minB, maxB] are those of the contact contract: for polygons
+ *               the true normals (-ey, ex) of A's live edges (axis e), then B's (axis ka + e); for rectangles the eight edge
+ *               vectors; min / max the running fmin / fmax of nx * x + ny * y over the live vertices.
+ *               o1 = maxA - minB,  o2 = maxB - minA,  v = nx * rx + ny * ry (each product first, then the sum).
+ *   per live axis, in axis order:
+ *               v > 0:  lo = (-o2) / v,  hi = o1 / v.       v < 0:  lo = o1 / v,  hi = (-o2) / v.
+ *               v == 0: the axis bounds nothing, unless o1 < 0 || o2 < 0: then `never` is set (it separates for the whole step).
+ *               v NaN:  the axis is ignored.
+ *   the pick    t_in starts at +0 with no axis, t_out at 1.  lo > t_in replaces t_in and records the axis and the sign of v;
+ *               hi < t_out replaces t_out (compare and select, not fmax: a NaN bound fails the compare and is ignored, and among
+ *               equal lo the first axis wins).
+ *   the record  hit = !never && t_in <= t_out.  On a hit: toi = t_in, axis = the recorded one, (nx, ny) = s * (nx / len, ny / len)
+ *               of that axis with len = sqrt(nx * nx + ny * ny), s = +1 when v < 0 and -1 when v > 0 (the unit normal from A
+ *               towards B at the touch), flags = 0.  A hit whose t_in kept its start (every lo underflowed to 0 or below) has
+ *               normal (0, 0) and axis = 0xFFFF, and C2D_SWEEP_START_OVERLAP stays clear: that flag means hit0 and nothing else.
+ *               On a miss: toi = +inf, normal (0, 0), axis = 0xFFFF, hit = 0, flags = 0.  A bad pair (as for the contact calls):
+ *               everything 0, axis = 0xFFFF, flags = C2D_SWEEP_BAD_PAIR.
+ * A zero-length live edge has v = o1 = o2 = 0 and bounds nothing, so len is never 0 for a winner.  +0 and -0 compare equal in the
+ * three floats.  For convex polygons in translation the rule is exact: the closed shapes first touch at the largest lo, and they
+ * have parted again once a hi is passed.  For non-convex input only the bits are promised.  t_out, the time of separation, is not
+ * returned, and rotation during the step is out of scope. */
+#define C2D_SWEEP_START_OVERLAP 1u  /* the pair is hit at t = 0 (hit0): toi = 0, normal (0, 0), axis = 0xFFFF */
+#define C2D_SWEEP_BAD_PAIR      2u  /* as C2D_CONTACT_BAD_PAIR */
+
+typedef struct c2d_sweep {      /* 16 bytes, 16-byte aligned output */
+    float    toi;               /*  0: first time of touch in 0 .. 1; +inf: none during the step */
+    float    nx, ny;            /*  4: unit normal from A towards B at the touch; (0, 0) when there is no axis */
+    uint16_t axis;              /* 12: 0..ka-1: edge of A, ka..ka+kb-1: edge of B (rectangles: 0..3, 4..7); 0xFFFF: none */
+    uint8_t  hit;               /* 14: the shapes touch at some t in 0 .. 1 */
+    uint8_t  flags;             /* 15: C2D_SWEEP_START_OVERLAP, C2D_SWEEP_BAD_PAIR */
+} c2d_sweep;
+
+int c2d_poly_pair_sweeps(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b,
+                         const float* d_a_dx, const float* d_a_dy, const float* d_b_dx, const float* d_b_dy,
+                         const uint32_t* d_pairs, size_t n_pairs, const unsigned long long* d_n_pairs,
+                         size_t row_base, size_t col_base,
+                         c2d_sweep* d_out, c2d_stream stream);
+
+int c2d_rect_pair_sweeps(c2d_ctx* ctx, const float* const d_a[8], size_t n_a, const float* const d_b[8], size_t n_b,
+                         const float* d_a_dx, const float* d_a_dy, const float* d_b_dx, const float* d_b_dy,
+                         const uint32_t* d_pairs, size_t n_pairs, const unsigned long long* d_n_pairs,
+                         size_t row_base, size_t col_base,
+                         c2d_sweep* d_out, c2d_stream stream);
+
 /* ---- binned polygon batches ---------------------------------------------------
  * The padded layout above moves 16 vertex rows per polygon whatever the polygons are: with
  * K ~ U{3..16} that is 259 bytes per pair for 155 bytes of real vertices, and no kernel can
