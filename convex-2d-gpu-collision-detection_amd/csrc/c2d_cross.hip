@@ -30,9 +30,8 @@ constexpr int kCrossBlock = 256;      // rows of A per block: one per lane
 constexpr int kCrossCols = 256;       // columns of B per block: four mask words
 constexpr int kSideVecs = 6;          // one rectangle's hoisted quantities: 24 floats, six 16-byte LDS reads
 
-// The quantities of convex_collide that depend on one rectangle only.  Every field is computed by the same IEEE operations,
-// in the same order, as rect_collide_certified (c2d_math.hpp) computes it inside a pair, so the pair test below sees the
-// same bits as the pairwise path.
+// The quantities of convex_collide and of the parallel-axis certificates (c2d_math.hpp) that depend on one rectangle only.
+// Every projection is computed by the same IEEE operations, in the same order, as rect_collide computes it inside a pair.
 struct RectSide {
     float v[8];              // the vertices x0,y0,...,x3,y3
     float ax[2], ay[2];      // edge axes 0 and 1
@@ -98,13 +97,11 @@ C2D_DEV void side_unpack(const f32x4 (&o)[kSideVecs], RectSide& q)
     q.s2[0] = o[5][0]; q.s2[1] = o[5][1]; q.cmax = o[5][2];
 }
 
-// rect_collide_certified(A.v, B.v) (c2d_math.hpp) from hoisted sides: the same four axes, the same projections, the same
-// certificate.  The certificate's bound C is the pair's own max |coordinate|: fmax(A.cmax, B.cmax) is the value of the pairwise
-// path's fmax chain over the sixteen coordinates (max is associative on numbers, |x| has no -0, and both forms drop a NaN unless
-// every operand is one), so c2, c3 and `need` are bit-equal to the pairwise path's, and so are `sep` and `thin` — except that a
-// pair with a rectangle outside the certificate's domain (a |coordinate| of 2^61 or more, see rect_side) always reads thin.  The
-// soundness argument is otherwise the one written at rect_collide_certified; `sep` needs none (it is rect_collide's own test on
-// four of its eight axes).
+// Axes 0, 1 of both rectangles from hoisted sides, axes 2, 3 by the parallel-axis certificates (c2d_math.hpp, where the
+// soundness argument is written).  The certificate's bound C is the pair's own max |coordinate|: fmax(A.cmax, B.cmax) is the
+// value of an fmax chain over the sixteen coordinates (max is associative on numbers, |x| has no -0, and both forms drop a NaN
+// unless every operand is one).  A pair with a rectangle outside the certificate's domain (a |coordinate| of 2^61 or more, see
+// rect_side) always reads thin.  `sep` needs no argument (it is rect_collide's own test on four of its eight axes).
 C2D_DEV bool cross_collide_certified(const RectSide& A, const RectSide& B, bool& thin)
 {
     const float cmax = __builtin_fmaxf(A.cmax, B.cmax);

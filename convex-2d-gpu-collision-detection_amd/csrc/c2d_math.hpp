@@ -283,50 +283,90 @@ C2D_DEV bool rect_collide(const float (&r1)[8], const float (&r2)[8])
     return !sep;
 }
 
-// ---- convex_collide with certificates for the second axis of each parallel pair -----------------------------------------
+// ---- the parallel-axis certificates (N x M kernels: cross_collide_certified, c2d_cross.hip; Monte-Carlo kernels, c2d_mc.hip) ----
 // A rectangle's edge axes 2, 3 are the negatives of its axes 0, 1 up to rounding: b = -a + d with |d| a few ulps of the
 // coordinates.  For every vertex v the COMPUTED projections satisfy |p_b(v) + p_a(v)| <= eta,
 //     eta = |d|_1 C (1 + 3u) + 4u (1 + u) |a|_1 C,      u = 2^-24, C >= every |coordinate| of the pair
 // (d.v plus the roundings of the two dot products), so max1_b >= -min1_a - eta, min2_b <= -max2_a + eta and likewise with 1, 2
 // exchanged: when both overlaps on axis a, max2_a - min1_a and max1_a - min2_a, are at least 2 eta, NEITHER comparison of
-// utils.cu:178 can hold on axis b.  This evaluates axes 0, 1 of both rectangles, takes d from the floats (a + b) and C from
-// the sixteen coordinates, and reports `thin` when the pair is not separated by those four axes and some overlap is below its
-// certificate (or not a number: the comparisons are written so that a NaN anywhere reads "thin") — the caller then evaluates
-// the pair in full (rect_collide).  The thresholds carry 2^-8 relative and 1e-36 absolute slack for their own rounding and
-// for underflow.  The Monte-Carlo kernels use the same certificates with scene-level constants (c2d_mc.hip).
-// The bound is a rounding bound and holds while no product or difference overflows: with a coordinate of 3e38 or inf an infinite
-// overlap passes an infinite `need` and the pair was certified "collide" while an axis of edge 2 or 3 separates it.  So the
-// certificate is kept to its domain, as rect_side (c2d_cross.hip) keeps it: with every |coordinate| below 2^61, |axis| <= 2^62,
-// |projection| <= 2^124 and every overlap stays below 2^126; a pair beyond that (or all NaN) reads thin.  One compare per pair.
-C2D_DEV bool rect_collide_certified(const float (&r1)[8], const float (&r2)[8], bool& thin)
+// utils.cu:178 can hold on axis b.  A kernel that evaluates axes 0, 1 of both rectangles, takes d from the floats (a + b) and C
+// from the sixteen coordinates may therefore skip axes 2, 3 unless the pair is not separated by those four axes and some overlap
+// is below its certificate (or not a number) — such a pair is `thin` and is evaluated in full (rect_collide).  The thresholds carry
+// 2^-8 relative and 1e-36 absolute slack for their own rounding and for underflow, and the certificate is kept to |coordinate| <
+// 2^61, where no product or difference overflows (rect_side, c2d_cross.hip).  The pairwise kernels used this form until the
+// centre-gap form below replaced it (profiles/notes_r16_rect_gap.md).
+
+// ---- convex_collide decided by the centre-gap form of two parallelograms, with a proven margin --------------------------------
+// A rectangle, and any parallelogram, is a centre and two half axes, and its interval on a direction d is centre.d -+ (|a.d| +
+// |b.d|) / 2 with a = v1 - v0, b = v3 - v0.  So for the pair's four directions d (a, b of quad 1; a, b of quad 2) the sign of
+//     G_d = |d . D| - (|d . a1| + |d . b1|) - (|d . a2| + |d . b2|),     D = (w0 + w2) - (v0 + v2)  (doubled centres)
+// is the sign both comparisons of utils.cu:178 must have on edge d and on the opposite edge, whenever |G_d| exceeds what rounding
+// and the quad's distance from a parallelogram can move.  This is a certificate, not reference arithmetic: it is free to use fma
+// in every build, and a pair it cannot decide is `thin` — the caller then evaluates it with rect_collide.
+//
+// The margin.  u = 2^-24; C >= every |coordinate| of the pair; the vertices are the floats themselves, a, b, D and the defect
+// delta = (v0 + v2) - (v1 + v3) of each quad their exact real values; A = |d|_1; e_q = |delta_q|_1.  The quad's real edges are
+// a, b + delta, -a - delta, -b: the reference's axes n^ = fl(v_k+1 - v_k) are +-d + eps, eps in {0, +-delta}, each rounded once.
+//   (1) a reference projection fl(fl(n^x x) + fl(n^y y)) is within E_n = 3.01u |n|_1 C of n . v (two products, their sum, the
+//       axis difference; the fused forms of C2D_FMAD = 1, 2 round less).  min / max are monotone, so each interval end moves by
+//       at most E_n and each overlap of utils.cu:178 by at most 2 E_n; |n|_1 <= A + e_q.
+//   (2) n . (x - y) = +-d . (x - y) + eps . (x - y) and |eps . v| <= e_q C for every vertex: the overlaps on n are within 2 C e_q
+//       of those on d.  This term scales with the coordinates, NOT with |d|: a small quad far from the origin pays it in full.
+//   (3) the quad differs from its model parallelogram (v0, v1, v1 + v3 - v0, v3) in v2 alone, by delta: its interval ends on d
+//       move by at most |d . delta_q|; the doubled centre v0 + v2 is the model's plus delta_q.  With m_d the smaller overlap of
+//       the real quads on d:  |2 m_d + G_d| <= 3 (|d . delta_1| + |d . delta_2|) <= 3 A (e_1 + e_2).
+//       A quad that is no parallelogram has a large e_q and comes out thin through (2) and (3) unless it is decided anyway.
+//   (4) the evaluation below: edges and sums carry one rounding (u relative; |edge| <= 2C, |v0 + v2| <= 2C, |D^| <= 4C(1 + 2u),
+//       |D^ - D| <= 8.01uC), a dot fma(px, qx, fl(py qy)) two.  |d^ . D^ - d . D| <= (8.05 + 4.01 + 8.01) uAC; each of the four
+//       edge products is within 8.06uAC; their three additions (<= 4AC, 6AC, 8AC) add 18.1uAC, the final difference 12.1uAC:
+//       |G^_d - G_d| <= 82.6 uAC.
+//   (5) the defect as computed, e^_q = |fl(s^ - t^)|_1 with s^ = fl(v0 + v2), t^ = fl(v1 + v3): |delta| <= (1 + u) |delta^| + 4uC per
+//       component, so e_q <= (1 + u) e^_q + 8uC.
+// In units of G (twice an overlap): 4 E_n + 4 C e_q + 3 A (e_1 + e_2) + 82.6 uAC
+//     <= A (94.7 uC + 3 (e_1 + e_2)) + (4 + 12.04u) C e_q  <=  A (118.7 uC + 3.0001 (e^_1 + e^_2)) + 4.0001 C e^_q + 32.1 u C^2,
+// and the margin below is   M_d = A^ (120 uC + 3.02 (e^_1 + e^_2)) + 4.02 C e^_q + 33 u C^2 + 1e-36:  at least 2^-8 above the bound for
+// the roundings of A^ and of its own few operations, and 1e-36 absolute for products that underflow (each off by <= 2^-126 even
+// with subnormals flushed; an all-subnormal pair has every |G| below it and reads thin).  G^_d > M_d for one d proves that the
+// reference finds a separating axis; G^_d < -M_d for all four proves that neither comparison holds on any of its eight axes.
+// tests/test_rect_gap_cpu.py restates this in numpy, checks every decision against the oracle and (1) .. (5) in float64.
+//
+// Domain.  The bounds are rounding bounds and hold while nothing overflows: with every |coordinate| below 2^61 (the limit
+// rect_side, c2d_cross.hip, keeps), |edge| <= 2^62, |D^| <= 2^63, every product <= 2^126 and every G finite; a margin that
+// overflows is +inf and reads thin.  A pair beyond that reads thin by one compare.  Every coordinate enters every G^_d (v0, v1,
+// v3 through a or b, v2 through D^), so a NaN makes all four NaN: the max instructions below drop ONE NaN operand but return NaN
+// for two, both comparisons are false and the pair is thin.
+C2D_DEV float dotf(float px, float py, float qx, float qy) { return fma_(px, qx, py * qy); }
+
+C2D_DEV bool rect_gap_certified(const float (&r1)[8], const float (&r2)[8], bool& thin)
 {
-    float cmax = __builtin_fabsf(r1[0]);
+    const float a1x = r1[2] - r1[0], a1y = r1[3] - r1[1], b1x = r1[6] - r1[0], b1y = r1[7] - r1[1];
+    const float a2x = r2[2] - r2[0], a2y = r2[3] - r2[1], b2x = r2[6] - r2[0], b2y = r2[7] - r2[1];
+    const float s1x = r1[0] + r1[4], s1y = r1[1] + r1[5], s2x = r2[0] + r2[4], s2y = r2[1] + r2[5];
+    const float e1 = __builtin_fabsf(s1x - (r1[2] + r1[6])) + __builtin_fabsf(s1y - (r1[3] + r1[7]));
+    const float e2 = __builtin_fabsf(s2x - (r2[2] + r2[6])) + __builtin_fabsf(s2y - (r2[3] + r2[7]));
+    const float dx = s2x - s1x, dy = s2y - s1y;
+    float C = __builtin_fabsf(r1[0]);
 #pragma unroll
-    for (int k = 1; k < 8; k++) cmax = __builtin_fmaxf(cmax, __builtin_fabsf(r1[k]));
+    for (int k = 1; k < 8; k++) C = __builtin_fmaxf(C, __builtin_fabsf(r1[k]));
 #pragma unroll
-    for (int k = 0; k < 8; k++) cmax = __builtin_fmaxf(cmax, __builtin_fabsf(r2[k]));
-    const float c2 = (2.0f + 0x1p-7f) * cmax, c3 = (8.0f + 0x1p-5f) * 0x1p-24f * cmax;
-    bool sep = false, uneasy = !(cmax < 0x1p61f);
-#pragma unroll
-    for (int which = 0; which < 2; which++) {
-        const float (&r)[8] = which == 0 ? r1 : r2;
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const float ax = r[2 * i + 2] - r[2 * i], ay = r[2 * i + 3] - r[2 * i + 1];
-            const float bx = r[(2 * i + 6) & 7] - r[2 * i + 4], by = r[(2 * i + 7) & 7] - r[2 * i + 5];  // edge i + 2
-            const float p10 = dot2(ax, r1[0], ay, r1[1]), p11 = dot2(ax, r1[2], ay, r1[3]);
-            const float p12 = dot2(ax, r1[4], ay, r1[5]), p13 = dot2(ax, r1[6], ay, r1[7]);
-            const float p20 = dot2(ax, r2[0], ay, r2[1]), p21 = dot2(ax, r2[2], ay, r2[3]);
-            const float p22 = dot2(ax, r2[4], ay, r2[5]), p23 = dot2(ax, r2[6], ay, r2[7]);
-            const float min1 = min4(p10, p11, p12, p13), max1 = max4(p10, p11, p12, p13);
-            const float min2 = min4(p20, p21, p22, p23), max2 = max4(p20, p21, p22, p23);
-            sep |= ((max1 < min2) || (max2 < min1)) && first_projections_ordered(p10, p20);
-            const float need = fma_(__builtin_fabsf(ax) + __builtin_fabsf(ay), c3, (__builtin_fabsf(ax + bx) + __builtin_fabsf(ay + by)) * c2) + 1e-36f;
-            uneasy |= !((max2 - min1 >= need) && (max1 - min2 >= need));
-        }
-    }
-    thin = !sep && uneasy;
-    return !sep;
+    for (int k = 0; k < 8; k++) C = __builtin_fmaxf(C, __builtin_fabsf(r2[k]));
+    const float a1b1 = __builtin_fabsf(dotf(a1x, a1y, b1x, b1y)), a2b2 = __builtin_fabsf(dotf(a2x, a2y, b2x, b2y));
+    const float a1a2 = __builtin_fabsf(dotf(a1x, a1y, a2x, a2y)), a1b2 = __builtin_fabsf(dotf(a1x, a1y, b2x, b2y));
+    const float b1a2 = __builtin_fabsf(dotf(b1x, b1y, a2x, a2y)), b1b2 = __builtin_fabsf(dotf(b1x, b1y, b2x, b2y));
+    const float g1 = __builtin_fabsf(dotf(a1x, a1y, dx, dy)) - ((dotf(a1x, a1y, a1x, a1y) + a1b1) + (a1a2 + a1b2));
+    const float g2 = __builtin_fabsf(dotf(b1x, b1y, dx, dy)) - ((dotf(b1x, b1y, b1x, b1y) + a1b1) + (b1a2 + b1b2));
+    const float g3 = __builtin_fabsf(dotf(a2x, a2y, dx, dy)) - ((dotf(a2x, a2y, a2x, a2y) + a2b2) + (a1a2 + b1a2));
+    const float g4 = __builtin_fabsf(dotf(b2x, b2y, dx, dy)) - ((dotf(b2x, b2y, b2x, b2y) + a2b2) + (a1b2 + b1b2));
+    const float m0 = fma_(3.02f, e1 + e2, (120.0f * 0x1p-24f) * C);
+    const float c4 = 4.02f * C, cc = fma_((33.0f * 0x1p-24f) * C, C, 1e-36f);
+    const float n1 = fma_(c4, e1, cc), n2 = fma_(c4, e2, cc);
+    const float m1 = fma_(__builtin_fabsf(a1x) + __builtin_fabsf(a1y), m0, n1), m2 = fma_(__builtin_fabsf(b1x) + __builtin_fabsf(b1y), m0, n1);
+    const float m3 = fma_(__builtin_fabsf(a2x) + __builtin_fabsf(a2y), m0, n2), m4 = fma_(__builtin_fabsf(b2x) + __builtin_fabsf(b2y), m0, n2);
+    const float over = __builtin_fmaxf(__builtin_fmaxf(g1 - m1, g2 - m2), __builtin_fmaxf(g3 - m3, g4 - m4));   // > 0: some direction separates
+    const float under = __builtin_fmaxf(__builtin_fmaxf(g1 + m1, g2 + m2), __builtin_fmaxf(g3 + m3, g4 + m4));  // < 0: every direction overlaps
+    const bool col = under < 0.0f;
+    thin = !((C < 0x1p61f) & ((over > 0.0f) | col));
+    return col;
 }
 
 }  // namespace c2d

@@ -24,14 +24,14 @@ constexpr int kBlock = 256;
 constexpr int kWideBlock = 64;          // the 4-pairs-per-lane kernel runs one wave per block
 constexpr int kMaxBlocks = kMaxGrid;     // beyond this a launch falls back to its grid-stride loop
 
-// ---- the pairs of one lane: certified fast path, wave-wide fall-back ----------------------------------------------------
-// rect_collide_certified (c2d_math.hpp) evaluates four of the eight axes and certifies the other four from the overlaps it
-// saw; a pair whose certificate fails is "thin".  Thin pairs are rare (config 2: a wave in a few thousand), so the wave votes:
-// if any lane holds one, every lane evaluates its pairs again with all eight axes (rect_collide) — straight-line code, no
+// ---- the pairs of one lane: two tiers, certified fast path and wave-wide fall-back -----------------------------------------
+// Tier 1, rect_gap_certified (c2d_math.hpp), projects no vertex: it decides a pair from the centre-gap form of two
+// parallelograms (fourteen small dot products) whenever the gap exceeds a proven rounding margin; a pair it cannot decide is
+// "thin".  Thin pairs are rare (config 2: one pair in 10^5, a wave in a few hundred), so the wave votes: if any lane holds one,
+// every lane evaluates its pairs again with tier 2, the reference's own eight axes (rect_collide) — straight-line code, no
 // divergence.  `build(e, launder, r1, r2)` fills pair e of the lane; in the fall-back it is asked to launder its inputs through
-// an empty asm (launder, c2d_wave.hpp), otherwise the compiler keeps every projection of the fast path alive for reuse there
-// (172 spilled dwords).
-// Returns bit e = pair e collides.  Headline kernel 104.5 -> 103.3 us, pose format 85.9 -> 74.9 us per 1e7 pairs.
+// an empty asm (launder, c2d_wave.hpp), otherwise the compiler keeps values of the fast path alive for reuse there.
+// Returns bit e = pair e collides.  DESIGN.md §5.1, profiles/notes_r16_rect_gap.md.
 
 template <int PAIRS, class Build>
 C2D_DEV uint32_t collide_pairs(Build build)
@@ -43,7 +43,7 @@ C2D_DEV uint32_t collide_pairs(Build build)
         float r1[8], r2[8];
         build(e, Plain{}, r1, r2);
         bool thin;
-        bits |= (rect_collide_certified(r1, r2, thin) ? 1u : 0u) << e;
+        bits |= (rect_gap_certified(r1, r2, thin) ? 1u : 0u) << e;
         any_thin |= thin;
     }
     if (__ballot(any_thin) != 0ull) {
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(64) void sat_rect_aos_kernel(const float* __restric
 // fixes the reference's comparisons on the two edges along e.  One separating direction decides "no collision", four
 // overlapping ones decide "collision"; anything else — about one pair in 10^4 on the bench workload, and every pair with a
 // non-finite or out-of-range parameter — is thin, and the wave evaluates that pair slot with the vertex arithmetic
-// (collide_pairs).  Per-direction margins (not one margin from the smallest extent) keep a sliver's large margin on its own axis.
+// (rect_collide).  Per-direction margins (not one margin from the smallest extent) keep a sliver's large margin on its own axis.
 C2D_DEV bool pose_pair_closed_form(const float (&v)[10], bool& thin)
 {
     float s1, c1, s2, c2;
@@ -313,13 +313,11 @@ __global__ __launch_bounds__(BLOCK, (VEC == 4 ? 5 : 1)) void sat_rect_pose_kerne
                 for (int k = 0; k < 10; k++) v[k] = q[k][e];
                 bool thin;
                 uint32_t hit = pose_pair_closed_form(v, thin) ? 1u : 0u;
-                if (__ballot(thin) != 0ull) {  // this pair slot with the vertex arithmetic, for the whole wave
-                    hit = collide_pairs<1>([&q, e](int, auto, float (&r1)[8], float (&r2)[8]) {
-                        float w[10];
+                if (__ballot(thin) != 0ull) {  // this pair slot with the vertex arithmetic, for the whole wave: all eight axes at
+                    float w[10];               // once, since what the closed form leaves open rect_gap_certified leaves open too
 #pragma unroll
-                        for (int k = 0; k < 10; k++) w[k] = launder(q[k][e], Laundered{});
-                        pose_pair_rects(w, r1, r2);
-                    });
+                    for (int k = 0; k < 10; k++) w[k] = launder(q[k][e], Laundered{});
+                    hit = pose_pair_collides(w);
                 }
                 bits |= hit << e;
             }

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Developer tool: c2d_sat_rect_pairs_verts on the config-2 workload, with and without the colliding count, for one or several
-builds of libc2d.so in ONE process (interleaved, repeated): HIP events around 200 back-to-back calls after a pre-warm.
-usage: rect_bench.py [lib.so ...]"""
+builds of libc2d.so in ONE process (interleaved, repeated): HIP events around 200 back-to-back calls after a pre-warm.  Each round times every build
+once, in the order given; the last lines give each build's median and, for two builds, in how many rounds the second was faster.
+usage: rect_bench.py [--rounds N] [lib.so ...]"""
 import os
 import sys
 import time
@@ -17,7 +18,11 @@ pkg = load_package()
 
 
 def main():
-    libs = sys.argv[1:] or [pkg.library_path()]
+    args = sys.argv[1:]
+    rounds = 3
+    if args[:1] == ["--rounds"]:
+        rounds, args = int(args[1]), args[2:]
+    libs = args or [pkg.library_path()]
     dev = torch.device("cuda", 0)
     n = 10_000_000
     gen = torch.Generator(device=dev)
@@ -56,11 +61,19 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / reps * 1e3
 
-    for rep in range(3):
-        for p, e in zip(libs, engs):
+    times = [[] for _ in libs]
+    for rep in range(rounds):
+        for k, (p, e) in enumerate(zip(libs, engs)):
             a = timed(lambda: e.sat_rect_pairs_verts(ptrs, n, out.data_ptr(), cnt.data_ptr(), stream=sh))
             b = timed(lambda: e.sat_rect_pairs_verts(ptrs, n, out.data_ptr(), None, stream=sh))
+            times[k].append((a, b))
             print(f"{os.path.basename(p):28s} with count {a:7.2f} us ({65 * n / a / 1e3:5.0f} GB/s)   without {b:7.2f} us ({65 * n / b / 1e3:5.0f} GB/s)", flush=True)
+    for p, t in zip(libs, times):
+        print(f"{os.path.basename(p):28s} median of {rounds} rounds: with count {np.median([a for a, _ in t]):7.2f} us   without {np.median([b for _, b in t]):7.2f} us")
+    if len(libs) == 2:
+        for j, what in enumerate(("with count", "without")):
+            wins = sum(t1[j] < t0[j] for t0, t1 in zip(*times))
+            print(f"{os.path.basename(libs[1])} faster than {os.path.basename(libs[0])} {what} in {wins} of {rounds} rounds")
 
 
 if __name__ == "__main__":
