@@ -189,6 +189,8 @@ _SIGNATURES = {
     "c2d_rect_pair_distances": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                           C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_ray_casts": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(_PolySet), C.c_size_t, C.c_void_p, C.c_void_p]),
+    "c2d_poly_ray_casts_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(_PolySet), C.c_size_t, C.c_void_p, C.c_void_p]),
+    "c2d_poly_ray_casts_grid_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "c2d_poly_pair_sweeps": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_rect_pair_sweeps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -813,6 +815,24 @@ class Engine:
             raise ValueError("need a poly_set() description")
         planes = (C.c_void_p * 4)(*[_ptr_of(p) for p in rays])
         self._check(self.lib.c2d_poly_ray_casts(self.h, planes, n_rays, C.byref(b), col_base, _ptr_of(out), C.c_void_p(stream)), "c2d_poly_ray_casts")
+
+    def poly_ray_casts_grid(self, rays: Sequence, n_rays: int, b: _PolySet, out, col_base: int = 0, stream: int = 0):
+        """c2d_poly_ray_casts_grid: poly_ray_casts through a uniform grid over b, for many polygons and short segments; per ray the
+        pick of poly_ray_casts among the polygons whose vertex box the ray meets (include/c2d.h "ray queries through a grid").
+        Uses the ctx scratch."""
+        if rays is None or len(rays) != 4:
+            raise ValueError("need the four ray planes ox, oy, dx, dy")
+        if not isinstance(b, _PolySet):
+            raise ValueError("need a poly_set() description")
+        planes = (C.c_void_p * 4)(*[_ptr_of(p) for p in rays])
+        self._check(self.lib.c2d_poly_ray_casts_grid(self.h, planes, n_rays, C.byref(b), col_base, _ptr_of(out), C.c_void_p(stream)),
+                    "c2d_poly_ray_casts_grid")
+
+    def poly_ray_casts_grid_stats(self) -> dict:
+        """c2d_poly_ray_casts_grid_stats: the counters of the last poly_ray_casts_grid call with polygons (synchronise first)"""
+        out = (C.c_ulonglong * 4)()
+        self._check(self.lib.c2d_poly_ray_casts_grid_stats(self.h, out), "c2d_poly_ray_casts_grid_stats")
+        return {"listed": int(out[0]), "visited": int(out[1]), "candidates": int(out[2]), "outliers": int(out[3])}
 
     # -- swept queries (include/c2d.h "swept queries: time of impact for listed pairs in linear motion") -----------------
     @staticmethod

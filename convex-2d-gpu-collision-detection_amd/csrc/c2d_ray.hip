@@ -22,9 +22,7 @@
 //                           row tile meet in an atomic minimum on those eight bytes, which does not depend on who arrives first.
 //   3. ray_finalise_kernel  one lane per ray: re-evaluates the winning polygon alone (at most 16 edges) by the rule's own sequence
 //                           and writes the whole record with one 16-byte store.
-#include "c2d_cross.hpp"
-#include "c2d_math.hpp"
-#include "c2d_poly_pair.hpp"   // PolySetDev, poly_set_check, poly_count
+#include "c2d_ray_rule.hpp"
 #include "c2d_ray_strips.hpp"
 
 namespace c2d {
@@ -33,41 +31,7 @@ static_assert(sizeof(c2d_ray_hit) == 16 && offsetof(c2d_ray_hit, poly) == 0 && o
                   offsetof(c2d_ray_hit, edge) == 12 && offsetof(c2d_ray_hit, hit) == 14 && offsetof(c2d_ray_hit, flags) == 15,
               "the kernels treat a ray hit as four dwords, (poly, t) being the 64-bit key");
 
-constexpr int kRayBlock = 256;   // rays per block: one per lane
 constexpr int kRayCols = 64;     // polygons of B per staged tile
-constexpr int kRayK = C2D_POLY_KMAX;
-constexpr unsigned long long kRayNoKey = ~0ull;
-constexpr uint32_t kRayNone16 = 0xFFFFu;
-
-struct RayPlanes {
-    const float* ox;
-    const float* oy;
-    const float* dx;
-    const float* dy;
-};
-
-// the three cross products of one (ray, edge)
-struct RayEdge {
-    float den, tn, un;
-};
-
-C2D_DEV RayEdge ray_edge(float ox, float oy, float dx, float dy, float x0, float y0, float ex, float ey)
-{
-    const float wx = x0 - ox, wy = y0 - oy;
-    return RayEdge{dx * ey - dy * ex, wx * ey - wy * ex, wx * dy - wy * dx};
-}
-
-// The rule's two cases folded into one by den's sign bit: with tn, un and den flipped where den is negative the second case reads as
-// the first (a zero of either sign passes both "<= 0" and ">= 0", before and after the flip; a NaN fails either way; |den| > 0 fails
-// for a den of +-0 or NaN).  Compares only, joined without branches: the boolean is the rule's for every bit pattern.
-C2D_DEV bool ray_edge_usable(const RayEdge& c)
-{
-    const uint32_t sgn = __float_as_uint(c.den) & 0x80000000u;
-    const float den = __uint_as_float(__float_as_uint(c.den) ^ sgn), tn = __uint_as_float(__float_as_uint(c.tn) ^ sgn),
-                un = __uint_as_float(__float_as_uint(c.un) ^ sgn);
-    return (int)(den > 0.0f) & (int)(tn >= 0.0f) & (int)(tn <= den) & (int)(un >= 0.0f) & (int)(un <= den);
-}
-
 __global__ __launch_bounds__(kRayBlock) void ray_init_kernel(size_t n_rays, c2d_ray_hit* __restrict__ out)
 {
     const size_t step = (size_t)gridDim.x * kRayBlock;
@@ -196,6 +160,39 @@ __global__ __launch_bounds__(kRayBlock) void ray_finalise_kernel(RayPlanes R, si
     }
 }
 
+int ray_launch_init(c2d_ctx* ctx, hipStream_t s, size_t n_rays, c2d_ray_hit* d_out)
+{
+    hipLaunchKernelGGL(ray_init_kernel, dim3(grid_for(n_rays, kRayBlock, 1 << 16)), dim3(kRayBlock), 0, s, n_rays, d_out);
+    C2D_LAUNCH_CHECK(ctx);
+    return C2D_OK;
+}
+
+int ray_launch_finalise(c2d_ctx* ctx, hipStream_t s, const RayPlanes& R, size_t n_rays, const PolySetDev& B, uint32_t col_base, c2d_ray_hit* d_out)
+{
+    hipLaunchKernelGGL(ray_finalise_kernel, dim3(grid_for(n_rays, kRayBlock, 1 << 16)), dim3(kRayBlock), 0, s, R, n_rays, B, col_base, d_out);
+    C2D_LAUNCH_CHECK(ctx);
+    return C2D_OK;
+}
+
+int ray_check_args(c2d_ctx* ctx, const char* what, const float* const d_rays[4], size_t n_rays, const c2d_poly_set* b, size_t col_base,
+                   c2d_ray_hit* d_out, PolySetDev& B)
+{
+    B = PolySetDev{nullptr, nullptr, nullptr, 0, 0, (int)b->rows};
+    if (b->n == 0) {   // (no plane is read: only `rows` is looked at)
+        if (b->rows < 1 || b->rows > (uint32_t)C2D_POLY_KMAX) return cross_fail(ctx, what, "set b: rows must be 1..C2D_POLY_KMAX");
+    } else if (int rc = poly_set_check(ctx, what, "b", b, B)) {
+        return rc;
+    }
+    for (int p = 0; p < 4; p++) {
+        if (!d_rays[p]) return cross_fail(ctx, what, "NULL ray plane");
+        if (reinterpret_cast<uintptr_t>(d_rays[p]) & 3u) return cross_fail(ctx, what, "ray planes must be 4-byte aligned");
+    }
+    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return cross_fail(ctx, what, "the output must be 16-byte aligned");
+    if (B.n > kIndexLimit || col_base > kIndexLimit - B.n) return cross_fail(ctx, what, "col_base + n_b must not exceed 2^32");
+    if (n_rays > kIndexLimit) return cross_fail(ctx, what, "n_rays must not exceed 2^32");
+    return C2D_OK;
+}
+
 }  // namespace c2d
 
 using namespace c2d;
@@ -209,26 +206,13 @@ int c2d_poly_ray_casts(c2d_ctx* ctx, const float* const d_rays[4], size_t n_rays
     if (!ctx) return C2D_ERR_INVALID_ARG;
     if (!d_rays || !b || !d_out) return cross_fail(ctx, what, "NULL argument");
     if (n_rays == 0) return C2D_OK;
-    PolySetDev B{nullptr, nullptr, nullptr, 0, 0, (int)b->rows};
-    if (b->n == 0) {   // (no plane is read: only `rows` is looked at)
-        if (b->rows < 1 || b->rows > (uint32_t)C2D_POLY_KMAX) return cross_fail(ctx, what, "set b: rows must be 1..C2D_POLY_KMAX");
-    } else if (int rc = poly_set_check(ctx, what, "b", b, B)) {
-        return rc;
-    }
-    for (int p = 0; p < 4; p++) {
-        if (!d_rays[p]) return cross_fail(ctx, what, "NULL ray plane");
-        if (reinterpret_cast<uintptr_t>(d_rays[p]) & 3u) return cross_fail(ctx, what, "ray planes must be 4-byte aligned");
-    }
-    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return cross_fail(ctx, what, "the output must be 16-byte aligned");
-    if (B.n > kIndexLimit || col_base > kIndexLimit - B.n) return cross_fail(ctx, what, "col_base + n_b must not exceed 2^32");
-    if (n_rays > kIndexLimit) return cross_fail(ctx, what, "n_rays must not exceed 2^32");
+    PolySetDev B;
+    if (int rc = ray_check_args(ctx, what, d_rays, n_rays, b, col_base, d_out, B)) return rc;
 
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     const RayPlanes R{d_rays[0], d_rays[1], d_rays[2], d_rays[3]};
-    const int flat_grid = grid_for(n_rays, kRayBlock, 1 << 16);
-    hipLaunchKernelGGL(ray_init_kernel, dim3(flat_grid), dim3(kRayBlock), 0, s, n_rays, d_out);
-    C2D_LAUNCH_CHECK(ctx);
+    if (int rc = ray_launch_init(ctx, s, n_rays, d_out)) return rc;
     if (B.n != 0) {
         const size_t row_tiles = (n_rays + kRayBlock - 1) / kRayBlock, col_tiles = (B.n + kRayCols - 1) / kRayCols;
         const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 1;
@@ -238,9 +222,7 @@ int c2d_poly_ray_casts(c2d_ctx* ctx, const float* const d_rays[4], size_t n_rays
                            (uint32_t)strips, d_out, ctx->d_async_err);
         C2D_LAUNCH_CHECK(ctx);
     }
-    hipLaunchKernelGGL(ray_finalise_kernel, dim3(flat_grid), dim3(kRayBlock), 0, s, R, n_rays, B, (uint32_t)col_base, d_out);
-    C2D_LAUNCH_CHECK(ctx);
-    return C2D_OK;
+    return ray_launch_finalise(ctx, s, R, n_rays, B, (uint32_t)col_base, d_out);
 }
 
 }  // extern "C"

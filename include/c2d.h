@@ -632,6 +632,50 @@ typedef struct c2d_ray_hit {     /* 16 bytes, 16-byte aligned output */
 int c2d_poly_ray_casts(c2d_ctx* ctx, const float* const d_rays[4] /* ox, oy, dx, dy: f32[n_rays] each */, size_t n_rays,
                        const c2d_poly_set* b, size_t col_base, c2d_ray_hit* d_out, c2d_stream stream);
 
+/* ---- ray queries through a grid ----------------------------------------------------
+ * An addition to 0.6 (c2d_version() stays 6), found by symbol lookup like the calls above.
+ *
+ * c2d_poly_ray_casts_grid: the ray query for many polygons and short segments.  It walks a uniform grid over B along each segment
+ * instead of visiting every edge of every polygon.  The arguments, the record, the refused arguments, the vertex count outside
+ * 1..rows (in no hit, C2D_ASYNC_ERR_POLY_K), n_rays == 0 (a no-op), n_b == 0 (the no-hit record for every ray) and the untouched
+ * records at or beyond n_rays are those of c2d_poly_ray_casts.  It has a contract of its own:
+ *
+ *   the box of polygon j (count in 1..rows): xl, xh, yl, yh are the binary32 minimum / maximum of its live vertices' x and y.  A
+ *               polygon with a NaN live coordinate is UNBOXED and is a candidate of every ray.
+ *   meets(r, j) in binary64, unfused, in the written order, from the float inputs:
+ *               bx = ox + dx, by = oy + dy;
+ *               C  = the largest magnitude among ox, oy, bx, by, xl, xh, yl, yh (NaN when one of them is);
+ *               m  = 2^-20 * C;
+ *               sx = min(ox, bx) > xh + m || max(ox, bx) < xl - m,  and sy likewise with oy, by, yl, yh;
+ *               cx = 0.5 * xl + 0.5 * xh,  hx = (0.5 * xh - 0.5 * xl) + m,  and cy, hy likewise;
+ *               sn = |dx * (cy - oy) - dy * (cx - ox)| > hx * |dy| + hy * |dx|;
+ *               meets = !(sx || sy || sn).
+ *               A NaN fails every compare, so a non-finite ray or an infinite box meets.
+ *   the result  for ray r: the pick of c2d_poly_ray_casts restricted to { j : unboxed(j) || meets(r, j) }: the per-polygon rule,
+ *               the order, the ties and the record are unchanged.  It is deterministic (two runs give the same bytes) and does not
+ *               depend on how the grid is traversed.
+ *
+ * Relation to c2d_poly_ray_casts.  Wherever the segment really touches a polygon, meets holds, and the two calls agree byte for
+ * byte: on the project's ray scenes, their copies scaled by 1e-30 .. 1e30 and every hand case, no touched pair fails meets
+ * (tests/test_ray_grid_ref_cpu.py).  They are NOT equal for every bit pattern, and cannot be: the brute-force rule's booleans are not
+ * bounded by any box.  With a ray nearly collinear with an edge, den, tn and un are rounding noise, and c2d_poly_ray_casts then reports
+ * hits on polygons hundreds of units away from the segment (about 0.75 % of such rays against a square or a triangle, 13 % against a
+ * 2-gon).  The grid call reports no hit there.
+ *
+ * Unlike c2d_poly_ray_casts it uses the ctx scratch, as c2d_sat_poly_broad_pairs does: the workspace guard applies (one stream at a time
+ * per ctx), the scratch grows on demand (about 48 bytes per polygon and 36 per ray), and graph capture works after an eager call of
+ * the same or a larger n_rays and n_b; a capture that would have to grow the scratch is refused (C2D_ERR_INVALID_ARG) before anything
+ * is enqueued.  Use it from a few thousand polygons on; below that c2d_poly_ray_casts is the faster call. */
+int c2d_poly_ray_casts_grid(c2d_ctx* ctx, const float* const d_rays[4] /* ox, oy, dx, dy: f32[n_rays] each */, size_t n_rays,
+                            const c2d_poly_set* b, size_t col_base, c2d_ray_hit* d_out, c2d_stream stream);
+
+/* Diagnostics of the last c2d_poly_ray_casts_grid call with n_b > 0 on this ctx, read back with a blocking copy; call it after that
+ * call's stream has been synchronised and before any other call that uses the ctx scratch (otherwise C2D_ERR_INVALID_ARG, or the
+ * counters of a call in flight).  out[0] = rays that left the walk for the one-ray-per-wave route (non-finite, C >= 2^60, or more than
+ * 1024 sorted entries to visit), out[1] = sorted entries the walks visited, out[2] = of those, the ones that passed meets,
+ * out[3] = regular polygons tested against every ray because their box may lie outside the grid's bounds. */
+int c2d_poly_ray_casts_grid_stats(c2d_ctx* ctx, unsigned long long out[4]);
+
 /* ---- swept queries: time of impact for listed pairs in linear motion ------------
  * Additions to 0.6 (c2d_version() stays 6), found by symbol lookup like the calls above.
  *
