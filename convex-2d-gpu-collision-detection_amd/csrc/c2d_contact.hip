@@ -10,8 +10,10 @@
 //     depth = d, normal = +-n / sqrt(len2) with + when o1 <= o2.
 // One pair per lane; the lanes of a wave hold unrelated pairs, so every loop runs over all vertex slots with compile-time indices
 // (c2d_poly_pair.hpp).  The pair list is row-major: the lanes of a wave mostly share their row, so A is loaded through one
-// wave-uniform index when they all do; B is a gather (listed_pairs, c2d_pair_list.hpp, which the distance queries share).  Each
-// contact leaves as one 16-byte store.
+// wave-uniform index when they all do; B is a gather (listed_pairs, c2d_pair_list.hpp, which the distance and swept queries share).
+// The walk over the axes, with the pairwise boolean it returns, is that header's too (S::axes of its list shapes; the swept queries
+// run the same walk), and so is the kernel: this file keeps the two picks, the manifold and the query.  Each contact leaves as one
+// 16-byte store.
 //
 // One square root and one division per PAIR instead of one per axis (DESIGN.md §5.11 has the proof).  A first pass estimates every
 // axis's d as q = o * v_rsq_f32(len2) and keeps the smallest and the second smallest estimate.  With len2 in [2^-100, 2^100] and
@@ -102,65 +104,6 @@ struct FastPick {
     }
 };
 
-// ---- the shapes: every axis of the pairwise test, with its two intervals, to a pick; returns the pairwise boolean ------------
-
-// poly_collide (c2d_poly_pair.hpp) with the intervals kept: axes 0 .. ka - 1 are A's edges, ka .. ka + kb - 1 are B's.
-template <class Pick>
-C2D_DEV bool poly_contact_axes(const PolyObj& A, const PolyObj& B, Pick& pick)
-{
-    const float inf = __builtin_inff();
-    PolyObj P = A, Q = B;
-    bool sep = false;
-#pragma unroll 1
-    for (int side = 0; side < 2; side++) {
-        const uint32_t base = side ? (uint32_t)A.k : 0u;
-#pragma unroll
-        for (int a = 0; a < C2D_POLY_KMAX; a++) {
-            if (a < P.k) {   // axes >= P.k are zero vectors: they never separate and are never usable
-                const int a1 = (a + 1) & (C2D_POLY_KMAX - 1);
-                const float nx = -(P.y[a1] - P.y[a]), ny = P.x[a1] - P.x[a];
-                float mnp = inf, mxp = -inf, mnq = inf, mxq = -inf;
-#pragma unroll
-                for (int r = 0; r < C2D_POLY_KMAX; r++) {
-                    poly_minmax(nx, ny, P.x[r], P.y[r], mnp, mxp);
-                    poly_minmax(nx, ny, Q.x[r], Q.y[r], mnq, mxq);
-                }
-                sep |= ((mxp < mnq) || (mxq < mnp)) && first_projections_ordered(nx * P.x[0] + ny * P.y[0], nx * Q.x[0] + ny * Q.y[0]);
-                const float u = mxp - mnq, v = mxq - mnp;   // side 0: P is A, so u = maxA - minB; side 1: P is B, so v is
-                pick.add(base + (uint32_t)a, nx, ny, side ? v : u, side ? u : v);
-            }
-        }
-        const PolyObj t = P;
-        P = Q;
-        Q = t;
-    }
-    return !sep;
-}
-
-// rect_collide (c2d_math.hpp) with the intervals kept: axes 0 .. 3 are the edge vectors of rectangle 1, 4 .. 7 those of rectangle 2.
-template <class Pick>
-C2D_DEV bool rect_contact_axes(const float (&r1)[8], const float (&r2)[8], Pick& pick)
-{
-    bool sep = false;
-#pragma unroll
-    for (int which = 0; which < 2; which++) {
-        const float (&r)[8] = which == 0 ? r1 : r2;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const float ax = r[(2 * i + 2) & 7] - r[2 * i], ay = r[(2 * i + 3) & 7] - r[2 * i + 1];
-            const float p10 = dot2(ax, r1[0], ay, r1[1]), p11 = dot2(ax, r1[2], ay, r1[3]);
-            const float p12 = dot2(ax, r1[4], ay, r1[5]), p13 = dot2(ax, r1[6], ay, r1[7]);
-            const float p20 = dot2(ax, r2[0], ay, r2[1]), p21 = dot2(ax, r2[2], ay, r2[3]);
-            const float p22 = dot2(ax, r2[4], ay, r2[5]), p23 = dot2(ax, r2[6], ay, r2[7]);
-            const float min1 = min4(p10, p11, p12, p13), max1 = max4(p10, p11, p12, p13);
-            const float min2 = min4(p20, p21, p22, p23), max2 = max4(p20, p21, p22, p23);
-            sep |= ((max1 < min2) || (max2 < min1)) && first_projections_ordered(p10, p20);
-            pick.add((uint32_t)(4 * which + i), ax, ay, max1 - min2, max2 - min1);
-        }
-    }
-    return !sep;
-}
-
 // ---- the manifold of one polygon pair on its winning axis (include/c2d.h "contact manifolds") ---------------------
 // e, (nx, ny), len = sqrt(len2) and pos = (o1 <= o2) are the winning axis as the contact rule saw it.  Every vertex index is a
 // compile-time slot: the deepest vertex, its two neighbours and the reference edge are carried through selects.  Slots >= k repeat
@@ -241,20 +184,9 @@ C2D_DEV void poly_manifold(const PolyObj& A, const PolyObj& B, uint32_t e, float
     m1 = make_uint4(two ? __float_as_uint(y1) : 0u, two ? __float_as_uint(d1) : 0u, (single ? 0u : feature) | (two ? 2u << 16 : 1u << 16) | (flags << 24), 0u);
 }
 
-// The shapes of c2d_pair_list.hpp with what the contact kernels add:
-//   S::axes(a, b, pick)    the axes of the pairwise test of (a, b) to `pick`; returns the pairwise boolean
-struct PolyContactShape : PolyListShape {
-    template <class Pick>
-    static C2D_DEV bool axes(const Obj& a, const Obj& b, Pick& pick) { return poly_contact_axes(a, b, pick); }
-};
-
-struct RectContactShape : RectListShape {
-    template <class Pick>
-    static C2D_DEV bool axes(const Obj& a, const Obj& b, Pick& pick) { return rect_contact_axes(a.r, b.r, pick); }
-};
-
-// The query of listed_pairs (c2d_pair_list.hpp): the contact of one pair per lane.  kManifold (polygons): the manifold of the pair
-// goes to man[p] as well, as two more 16-byte stores; without it the routine is the contact kernel as it was.
+// The query of listed_pairs (c2d_pair_list.hpp; the W of its pair_list_kernel): the contact of one pair per lane.  kManifold
+// (polygons): the manifold of the pair goes to man[p] as well, as two more 16-byte stores; without it the kernel has no such
+// argument and the routine is the contact kernel as it was.
 template <class S, bool kManifold>
 struct ContactWork {
     uint4 word = make_uint4(0u, 0u, 0u, kContactNoAxis | ((uint32_t)C2D_CONTACT_BAD_PAIR << 24));   // depth 0, normal (0, 0), hit 0
@@ -290,7 +222,7 @@ struct ContactWork {
             }
         }
     }
-    C2D_DEV void store(size_t p, c2d_contact* __restrict__ out, c2d_manifold* __restrict__ man) const
+    C2D_DEV void store(size_t p, c2d_contact* __restrict__ out, c2d_manifold* __restrict__ man = nullptr) const
     {
         reinterpret_cast<uint4*>(out)[p] = word;   // d_out is 16-byte aligned (checked on the host)
         if constexpr (kManifold) {
@@ -299,22 +231,6 @@ struct ContactWork {
         }
     }
 };
-
-template <class S>
-__global__ __launch_bounds__(kPairListBlock) void contact_kernel(typename S::Set A, typename S::Set B, const uint32_t* __restrict__ pairs, size_t n_pairs,
-                                                                 const unsigned long long* __restrict__ d_n, size_t row_base, size_t col_base,
-                                                                 c2d_contact* __restrict__ out, uint32_t* __restrict__ async_err)
-{
-    listed_pairs<S, ContactWork<S, false>>(A, B, pairs, n_pairs, d_n, row_base, col_base, async_err, out, (c2d_manifold*)nullptr);
-}
-
-__global__ __launch_bounds__(kPairListBlock) void manifold_kernel(PolySetDev A, PolySetDev B, const uint32_t* __restrict__ pairs, size_t n_pairs,
-                                                                  const unsigned long long* __restrict__ d_n, size_t row_base, size_t col_base,
-                                                                  c2d_contact* __restrict__ out, c2d_manifold* __restrict__ man,
-                                                                  uint32_t* __restrict__ async_err)
-{
-    listed_pairs<PolyContactShape, ContactWork<PolyContactShape, true>>(A, B, pairs, n_pairs, d_n, row_base, col_base, async_err, out, man);
-}
 
 }  // namespace c2d
 
@@ -327,8 +243,9 @@ int c2d_poly_pair_contacts(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_s
 {
     return poly_pair_list_call(ctx, "c2d_poly_pair_contacts", a, b, d_pairs, n_pairs, d_n_pairs, row_base, col_base, {d_out},
                                [&](const PolySetDev& A, const PolySetDev& B, int grid) {
-                                   hipLaunchKernelGGL(contact_kernel<PolyContactShape>, dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs,
-                                                      n_pairs, d_n_pairs, row_base, col_base, d_out, ctx->d_async_err);
+                                   hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_list_kernel<PolyListShape, ContactWork<PolyListShape, false>, c2d_contact>),
+                                                      dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs, n_pairs, d_n_pairs,
+                                                      row_base, col_base, d_out, ctx->d_async_err);
                                });
 }
 
@@ -338,8 +255,9 @@ int c2d_poly_pair_manifolds(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_
 {
     return poly_pair_list_call(ctx, "c2d_poly_pair_manifolds", a, b, d_pairs, n_pairs, d_n_pairs, row_base, col_base, {d_contacts, d_manifolds},
                                [&](const PolySetDev& A, const PolySetDev& B, int grid) {
-                                   hipLaunchKernelGGL(manifold_kernel, dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs, n_pairs,
-                                                      d_n_pairs, row_base, col_base, d_contacts, d_manifolds, ctx->d_async_err);
+                                   hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_list_kernel<PolyListShape, ContactWork<PolyListShape, true>, c2d_contact, c2d_manifold>),
+                                                      dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs, n_pairs, d_n_pairs,
+                                                      row_base, col_base, d_contacts, d_manifolds, ctx->d_async_err);
                                });
 }
 
@@ -348,8 +266,9 @@ int c2d_rect_pair_contacts(c2d_ctx* ctx, const float* const d_a[8], size_t n_a, 
 {
     return rect_pair_list_call(ctx, "c2d_rect_pair_contacts", d_a, n_a, d_b, n_b, d_pairs, n_pairs, d_n_pairs, row_base, col_base, {d_out},
                                [&](const RectListSet& A, const RectListSet& B, int grid) {
-                                   hipLaunchKernelGGL(contact_kernel<RectContactShape>, dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs,
-                                                      n_pairs, d_n_pairs, row_base, col_base, d_out, ctx->d_async_err);
+                                   hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_list_kernel<RectListShape, ContactWork<RectListShape, false>, c2d_contact>),
+                                                      dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs, n_pairs, d_n_pairs,
+                                                      row_base, col_base, d_out, ctx->d_async_err);
                                });
 }
 

@@ -10,12 +10,14 @@
 //     d2 = (xp - cx)^2 + (yp - cy)^2; unusable when d2 is NaN.
 // In the order side, e, v the first usable candidate is the first best and a later one replaces it only under strict d2 < best.
 //
-// One pair per lane on the frame of c2d_pair_list.hpp.  The lanes of a wave hold unrelated pairs, so the vertices stay in registers
-// and every vertex index is a compile-time slot: the sweep always works on the edge from slot 0 to slot 1 of the edge polygon and
-// turns that polygon by one slot per trip, so the edge loop stays rolled (one body of K candidates instead of K * K) and the polygon
-// is back in place after K trips.  poly_load's padding repeats vertex 0, which closes the polygon for free: slot k is vertex 0, and
-// slot 16 is slot 0.  The padding is NOT neutral otherwise: a padded candidate reaches vertex 0 directly, a real one reaches the
-// same point through t, and the two d2 can differ by a rounding — so slots with e >= k or v >= k are masked out of the pick.
+// One pair per lane on the frame of c2d_pair_list.hpp, which also holds the kernel and, in its list shapes, the pairwise boolean
+// (S::collide): this file adds the candidates' record to those shapes and keeps the query.  The lanes of a wave hold unrelated pairs,
+// so the vertices stay in registers and every vertex index is a compile-time slot: the sweep always works on the edge from slot 0 to
+// slot 1 of the edge polygon and turns that polygon by one slot per trip, so the edge loop stays rolled (one body of K candidates
+// instead of K * K) and the polygon is back in place after K trips.  poly_load's padding repeats vertex 0, which closes the polygon
+// for free: slot k is vertex 0, and slot 16 is slot 0.  The padding is NOT neutral otherwise: a padded candidate reaches vertex 0
+// directly, a real one reaches the same point through t, and the two d2 can differ by a rounding — so slots with e >= k or v >= k are
+// masked out of the pick.
 #include "c2d_pair_list.hpp"
 
 namespace c2d {
@@ -96,15 +98,12 @@ C2D_DEV void distance_record(float (&ax)[K], float (&ay)[K], int ka, float (&bx)
 }
 
 // The shapes of c2d_pair_list.hpp with what the distance kernel adds:
-//   S::collide(a, b)             the pairwise boolean of the pair
 //   S::record(a, b, d0, d1)      the record of a pair that is not hit (a and b are turned and restored)
 struct PolyDistanceShape : PolyListShape {
-    static C2D_DEV bool collide(const Obj& a, const Obj& b) { return poly_collide(a, b); }
     static C2D_DEV void record(Obj& a, Obj& b, uint4& d0, uint4& d1) { distance_record<C2D_POLY_KMAX>(a.x, a.y, a.k, b.x, b.y, b.k, d0, d1); }
 };
 
 struct RectDistanceShape : RectListShape {
-    static C2D_DEV bool collide(const Obj& a, const Obj& b) { return rect_collide(a.r, b.r); }
     static C2D_DEV void record(Obj& a, Obj& b, uint4& d0, uint4& d1)
     {
         float ax[4], ay[4], bx[4], by[4];
@@ -117,7 +116,7 @@ struct RectDistanceShape : RectListShape {
     }
 };
 
-// The query of listed_pairs: starts as the BAD_PAIR record; a hit pair gets {0, (0, 0), (0, 0), 0xFFFF, 0xFFFF, 1, 0}.
+// The query of listed_pairs (the W of pair_list_kernel): starts as the BAD_PAIR record; a hit pair gets {0, (0, 0), (0, 0), 0xFFFF, 0xFFFF, 1, 0}.
 template <class S>
 struct DistanceWork {
     uint4 d0 = make_uint4(0u, 0u, 0u, 0u), d1 = make_uint4(0u, kDistanceNone, (uint32_t)C2D_DISTANCE_BAD_PAIR << 8, 0u);
@@ -146,14 +145,6 @@ struct DistanceWork {
     }
 };
 
-template <class S>
-__global__ __launch_bounds__(kPairListBlock) void distance_kernel(typename S::Set A, typename S::Set B, const uint32_t* __restrict__ pairs, size_t n_pairs,
-                                                                  const unsigned long long* __restrict__ d_n, size_t row_base, size_t col_base,
-                                                                  c2d_distance* __restrict__ out, uint32_t* __restrict__ async_err)
-{
-    listed_pairs<S, DistanceWork<S>>(A, B, pairs, n_pairs, d_n, row_base, col_base, async_err, out);
-}
-
 }  // namespace c2d
 
 using namespace c2d;
@@ -165,8 +156,9 @@ int c2d_poly_pair_distances(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_
 {
     return poly_pair_list_call(ctx, "c2d_poly_pair_distances", a, b, d_pairs, n_pairs, d_n_pairs, row_base, col_base, {d_out},
                                [&](const PolySetDev& A, const PolySetDev& B, int grid) {
-                                   hipLaunchKernelGGL(distance_kernel<PolyDistanceShape>, dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs,
-                                                      n_pairs, d_n_pairs, row_base, col_base, d_out, ctx->d_async_err);
+                                   hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_list_kernel<PolyDistanceShape, DistanceWork<PolyDistanceShape>, c2d_distance>),
+                                                      dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs, n_pairs, d_n_pairs,
+                                                      row_base, col_base, d_out, ctx->d_async_err);
                                });
 }
 
@@ -175,8 +167,9 @@ int c2d_rect_pair_distances(c2d_ctx* ctx, const float* const d_a[8], size_t n_a,
 {
     return rect_pair_list_call(ctx, "c2d_rect_pair_distances", d_a, n_a, d_b, n_b, d_pairs, n_pairs, d_n_pairs, row_base, col_base, {d_out},
                                [&](const RectListSet& A, const RectListSet& B, int grid) {
-                                   hipLaunchKernelGGL(distance_kernel<RectDistanceShape>, dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs,
-                                                      n_pairs, d_n_pairs, row_base, col_base, d_out, ctx->d_async_err);
+                                   hipLaunchKernelGGL(HIP_KERNEL_NAME(pair_list_kernel<RectDistanceShape, DistanceWork<RectDistanceShape>, c2d_distance>),
+                                                      dim3(grid), dim3(kPairListBlock), 0, (hipStream_t)stream, A, B, d_pairs, n_pairs, d_n_pairs,
+                                                      row_base, col_base, d_out, ctx->d_async_err);
                                });
 }
 

@@ -1,9 +1,11 @@
 """Graph-capture check of a list-driven query's polygon call, run as a separate process by tests/test_gpu_pair_list_contract.py:
-    python tests/pair_list_graph_check.py contacts|manifolds|distances
+    python tests/pair_list_graph_check.py contacts|manifolds|distances|sweeps
 
 torch must be imported before libc2d.so in a process that uses both (tests/graph_capture_check.py says why).  One call with
-d_n_pairs is captured on a single stream and replayed with different counts written to the device in between: after every replay
-the first min(capacity, count) records of every output equal the query's reference and every record beyond them is untouched.
+d_n_pairs (and, for the sweeps, both sets' motion planes) is captured on a single stream and replayed with different counts written
+to the device in between: after every replay the first min(capacity, count) records of every output equal the query's reference
+and every record beyond them is untouched.  The list mixes the query's classes (Query.mix: hits and misses above 0.1 each; the
+sweeps: start overlap between 0.1 and 0.9, moving hits above 0.05, misses above 0.05).
 Each stage is printed as it starts, so that a failure names its stage."""
 import importlib
 import os
@@ -38,12 +40,15 @@ def main(q):
     a, b = cases.dense_poly_sets(wl, n=64, extent=3.0)
     pairs = cases.all_pairs(64, 75)[::2]
     cap = len(pairs)
-    wants = h.outputs(q.poly_ref(a, b, *h.local(pairs)))
-    assert 0.1 < wants[0]["hit"].mean() < 0.9
+    x = q.extras(9201, 64, 75, 3.0)
+    wants = h.outputs(q.poly_ref(a, b, *h.local(pairs), *x))
+    assert q.mixed(wants, 1), "the list does not mix the query's classes"
     ta = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in a]
     tb = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in b]
     sa = eng.poly_set(ta[0].data_ptr(), ta[1].data_ptr(), ta[2].data_ptr(), 64, wl.KMAX)
     sb = eng.poly_set(tb[0].data_ptr(), tb[1].data_ptr(), tb[2].data_ptr(), 75, wl.KMAX)
+    tx = [[torch.from_numpy(plane).to(dev) for plane in m] for m in x]
+    kw = {name: tuple(t.data_ptr() for t in m) for name, m in zip(("a_motion", "b_motion"), tx)}
     t_pairs = torch.from_numpy(pairs.astype(np.int64).astype(np.int32)).to(dev)
     outs = [torch.full((cap + 2 * h.GUARD, dt.itemsize), h.BAND, dtype=torch.uint8, device=dev) for dt in q.dts]    # guard records on either side
     cnt = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -54,7 +59,7 @@ def main(q):
     with torch.cuda.graph(g, stream=side):
         sh = torch.cuda.current_stream(dev).cuda_stream
         getattr(eng, q.poly)(sa, sb, t_pairs.data_ptr(), cap, *[o.data_ptr() + dt.itemsize * h.GUARD for o, dt in zip(outs, q.dts)],
-                             n_pairs_dev=cnt.data_ptr(), stream=sh)
+                             n_pairs_dev=cnt.data_ptr(), stream=sh, **kw)
     torch.cuda.synchronize()
     assert all(bool((o == h.BAND).all()) for o in outs), "the capture itself wrote something"
     for count in (100, cap - 1, 0, 1, cap + 1000, 65):

@@ -1,7 +1,8 @@
-"""The one frame of the tests of the list-driven queries (contacts, manifolds, distances), as csrc/c2d_pair_list.hpp is the one frame
-of their kernels: the uploads, the pairwise GPU paths, run() with its guard bands, and the table QUERIES of what each query states
-of its own.  A plain module (pytest does not collect it) on numpy, pytest and the numpy references only: it never loads libc2d.so,
-so tests/pair_list_graph_check.py can import it after torch.  tests/test_pair_list_harness_cpu.py drives run() without a device."""
+"""The one frame of the tests of the list-driven queries (contacts, manifolds, distances, sweeps), as csrc/c2d_pair_list.hpp is the one
+frame of their kernels: the uploads, the pairwise GPU paths, run() with its guard bands, and the table QUERIES of what each query
+states of its own.  A plain module (pytest does not collect it) on numpy, pytest and the numpy references only: it never loads
+libc2d.so, so tests/pair_list_graph_check.py can import it after torch.  tests/test_pair_list_harness_cpu.py drives run() without a
+device."""
 import functools
 
 import numpy as np
@@ -11,6 +12,7 @@ import contact_cases
 import contact_ref
 import distance_ref
 import manifold_ref
+import sweep_ref
 
 GUARD = 4            # guard records in front of and behind every output
 BAND = 0xA5
@@ -50,6 +52,47 @@ class RectsOnDevice:
 
     def free(self):
         self.d.free()
+
+
+class Motion:
+    """The motion of a set on the device: two planes f32[n], each behind `offset` floats of NaN.  .ptrs = (dx, dy), the a_motion /
+    b_motion of the Engine methods; .sub(r0) the planes of the shard that starts at object r0.  apart: each plane is an exact
+    allocation of its own (nothing behind its last element)."""
+
+    def __init__(self, eng, m, offset=0, apart=False):
+        host = np.full((2, len(m[0]) + offset), np.nan, np.float32)
+        host[0, offset:], host[1, offset:] = m[0], m[1]
+        self.d = [eng.to_device(host[0]), eng.to_device(host[1])] if apart else [eng.to_device(host)]
+        self.ptrs = tuple(p + 4 * offset for p in ((self.d[0].ptr, self.d[1].ptr) if apart else (self.d[0].row(0), self.d[0].row(1))))
+
+    def sub(self, r0):
+        return self.ptrs[0] + 4 * r0, self.ptrs[1] + 4 * r0
+
+    def free(self):
+        for d in self.d:
+            d.free()
+
+
+def motions(seed, n_a, n_b, scale=4.0):
+    """-> (ma, mb), each (dx, dy) f32[n] of up to +-scale per component"""
+    rng = np.random.default_rng(seed)
+    return tuple(tuple((rng.uniform(-1, 1, n) * scale).astype(np.float32) for _ in range(2)) for n in (n_a, n_b))
+
+
+class Extras:
+    """What the two sets of one call carry besides their vertices, on the device, from its host form x = Query.extras(...): nothing
+    for most queries, each set's motion for the sweeps (None: that set stands still).  .kw: the keywords of poly_call / rect_call;
+    .raw: the same pointers as the C call takes them behind the two sets."""
+
+    def __init__(self, eng, x, apart=False):
+        self.d = [None if m is None else Motion(eng, m, apart=apart) for m in x]
+        self.kw = {name: d.ptrs for name, d in zip(("a_motion", "b_motion"), self.d) if d is not None}
+        self.raw = [p for d in self.d for p in (d.ptrs if d is not None else (None, None))]
+
+    def free(self):
+        for d in self.d:
+            if d is not None:
+                d.free()
 
 
 def local(pairs):
@@ -139,24 +182,42 @@ def outputs(records):
     return records if isinstance(records, tuple) else (records,)
 
 
+def hit_or_miss(want):
+    return want["hit"] == 1, want["hit"] == 0
+
+
+def sweep_classes(want):
+    """start overlap, moving hit, miss"""
+    start = (want["flags"] & sweep_ref.START_OVERLAP) != 0
+    return start, (want["hit"] == 1) & ~start, want["hit"] == 0
+
+
 class Query:
     """What one list-driven query states of its own.  dts / sames / nouns: per output, the record, its comparison and its word in a
     message; poly / rect: the Engine method of the polygon / rectangle call (the C symbol is "c2d_" + that), taking the outputs in
-    order behind n_pairs; poly_ref / rect_ref(a, b, i, j): the numpy reference on local indices; bad_pair: the flag a refused
+    order behind n_pairs; poly_ref / rect_ref(a, b, i, j, *x): the numpy reference on local indices; bad_pair: the flag a refused
     entry carries in the first output; every / count_cut: which of the dense sets' pairs dense() takes, and which 300 of those
     test_device_count_bounds_the_work lists; with_contacts: every polygon run() also queues c2d_poly_pair_contacts on the same
-    arguments and compares it, byte for byte, with the first output."""
+    arguments and compares it, byte for byte, with the first output; extras(seed, n_a, n_b, scale) -> x: what the two sets carry
+    besides their vertices, as the reference takes it (Extras uploads it for the call); classes(first output) -> the kinds of record a
+    list has to mix, and mix = (dense, graph): the share of each that dense() and the graph check ask for at least."""
 
-    def __init__(self, name, dts, sames, nouns, bad_pair, poly, poly_ref, rect=None, rect_ref=None, every=1, count_cut=slice(5, None, 311), with_contacts=False):
+    def __init__(self, name, dts, sames, nouns, bad_pair, poly, poly_ref, rect=None, rect_ref=None, every=1, count_cut=slice(5, None, 311), with_contacts=False,
+                 extras=lambda *a, **kw: (), classes=hit_or_miss, mix=((0.1, 0.5), (0.1, 0.1))):
         self.name, self.dts, self.sames, self.nouns, self.bad_pair = name, dts, sames, nouns, bad_pair
         self.poly, self.poly_ref, self.rect, self.rect_ref = poly, poly_ref, rect, rect_ref
         self.every, self.count_cut, self.with_contacts = every, count_cut, with_contacts
+        self.extras, self.classes, self.mix = extras, classes, mix
+
+    def mixed(self, want, where):
+        """whether the records `want` of a list mix this query's classes as `where` (0: dense(), 1: the graph check) asks"""
+        return all(c.mean() > least for c, least in zip(self.classes(outputs(want)[0]), self.mix[where]))
 
     def __repr__(self):
         return self.name
 
     def poly_call(self, eng, a, b, **bases):
-        """a, b: c2d_poly_set; bases: row_base, col_base -> the queue of run(); .dts: the outputs it wants banded"""
+        """a, b: c2d_poly_set; bases: row_base, col_base and Extras.kw -> the queue of run(); .dts: the outputs it wants banded"""
         def queue(d_pairs, cap, outs, d_n):
             getattr(eng, self.poly)(a, b, d_pairs, cap, *outs[:len(self.dts)], n_pairs_dev=d_n, **bases)
             if self.with_contacts:
@@ -195,22 +256,29 @@ MANIFOLDS = Query("manifolds", (contact_ref.CONTACT_DT, manifold_ref.MANIFOLD_DT
                   contact_ref.BAD_PAIR, "poly_pair_manifolds", manifold_ref.poly_manifolds, every=17, count_cut=slice(None), with_contacts=True)
 DISTANCES = Query("distances", (distance_ref.DISTANCE_DT,), (distance_ref.same,), ("records",), distance_ref.BAD_PAIR, "poly_pair_distances",
                   distance_ref.poly_distances, "rect_pair_distances", distance_ref.rect_distances)
-QUERIES = (CONTACTS, MANIFOLDS, DISTANCES)
+SWEEPS = Query("sweeps", (sweep_ref.SWEEP_DT,), (sweep_ref.same,), ("records",), sweep_ref.BAD_PAIR, "poly_pair_sweeps", sweep_ref.poly_sweeps,
+               "rect_pair_sweeps", sweep_ref.rect_sweeps, extras=motions, classes=sweep_classes, mix=((0.1, 0.05, 0.3), (0.1, 0.05, 0.05)))
+QUERIES = (CONTACTS, MANIFOLDS, DISTANCES, SWEEPS)
 
 
 # ---- shared inputs, computed once per process ---------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def dense(wl, query):
-    """The dense sets (300 x 311 polygons in a small box) and every `query.every`-th of their pairs, colliding and separated, with the
-    query's reference of those pairs (read-only) -> a, b, pairs, want"""
+    """The dense sets (300 x 311 polygons in a small box) and every `query.every`-th of their pairs, in every class of the query, with
+    the query's reference of those pairs (read-only), the sets carrying dense_extras(query) -> a, b, pairs, want"""
     a, b = contact_cases.dense_poly_sets(wl)
     pairs = contact_cases.all_pairs(a[0].shape[1], b[0].shape[1])[::query.every]
-    want = query.poly_ref(a, b, *local(pairs))
+    want = query.poly_ref(a, b, *local(pairs), *dense_extras(query))
     for w in outputs(want):
         w.setflags(write=False)
-    share = outputs(want)[0]["hit"].mean()
-    assert len(pairs) >= 4099 and 0.1 < share < 0.5, share
+    assert len(pairs) >= 4099 and query.mixed(want, 0), [c.mean() for c in query.classes(outputs(want)[0])]
     return a, b, pairs, want
+
+
+@functools.lru_cache(maxsize=None)
+def dense_extras(query):
+    """the sweeps: both dense sets move by up to +-4 per component"""
+    return query.extras(9101, 300, 311)
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,5 +1,5 @@
 """CPU test of the judges of the differential fuzzers (compare() of tests/tools/cross_fuzz.py — shared by poly_cross_fuzz.py —
-broad_fuzz.py and manifold_fuzz.py): each is fed a correct answer, which it must accept, and then one planted fault at a time, each
+broad_fuzz.py and pair_list_fuzz.py, the one of the four list-driven tools): each is fed a correct answer, which it must accept, and then one planted fault at a time, each
 of which it must reject.  A judge that lets a fault pass would turn every leg that relies on it green for nothing."""
 import importlib.util
 import os
@@ -12,7 +12,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import contact_cases  # noqa: E402
 import contact_ref  # noqa: E402
+import distance_ref  # noqa: E402
 import manifold_ref  # noqa: E402
+import pair_list_harness as h  # noqa: E402
 
 
 def tool(name):
@@ -34,7 +36,7 @@ def bf(pkg):
 
 @pytest.fixture(scope="module")
 def mf(pkg):
-    return tool("manifold_fuzz")
+    return tool("pair_list_fuzz")
 
 
 # ---- the mask and list judge of the two cross fuzzers -------------------------------------------------------------------------------
@@ -223,7 +225,13 @@ def test_broad_judge_rejects_planted_faults(bf):
         assert bf.compare(*args) != [], plant
 
 
-# ---- the record judge of the manifold fuzzer ----------------------------------------------------------------------------------------
+# ---- the record judge of the list-driven fuzzers: on the manifolds' two outputs, then on the distances' one --------------------------
+def judge(mf, args, query=h.MANIFOLDS):
+    """compare() on args = [the buffer of each output, reported, clean, the wanted records of each output, capacity]"""
+    n = len(query.dts)
+    return mf.compare(query, args[:n], args[n], args[n + 1], args[n + 2: 2 * n + 2], args[2 * n + 2])
+
+
 @pytest.fixture(scope="module")
 def manifold_case(wl):
     """a reference answer with two-point manifolds, misses and one bad entry"""
@@ -242,7 +250,7 @@ def manifold_answer(mf, want, capacity, bound, drop_bad=False):
         bound -= 1
     bad = bool((wc["flags"] & contact_ref.BAD_PAIR).any())
     bufs = []
-    for w, dt in zip((wc, wm), mf.DTS):
+    for w, dt in zip((wc, wm), h.MANIFOLDS.dts):
         buf = np.frombuffer(bytes([mf.BAND]) * ((capacity + 2 * mf.GUARD) * dt.itemsize), dt).copy()
         buf[mf.GUARD: mf.GUARD + bound] = w
         bufs.append(buf)
@@ -253,12 +261,12 @@ def test_manifold_judge_accepts_a_correct_answer(mf, manifold_case):
     n = len(manifold_case[0])
     for capacity, bound in ((n, n), (n + 3, n), (n, n - 9), (n, 5), (n, 0)):
         args = manifold_answer(mf, manifold_case, capacity, bound)
-        assert args[2] == (bound > 5) and mf.compare(*args) == []
-    assert mf.compare(*manifold_answer(mf, manifold_case, n, n, drop_bad=True)) == []
+        assert args[2] == (bound > 5) and judge(mf, args) == []
+    assert judge(mf, manifold_answer(mf, manifold_case, n, n, drop_bad=True)) == []
     args = manifold_answer(mf, manifold_case, n, n)          # +0 and -0 are equal, a NaN equals a NaN of another payload
     q = int(np.flatnonzero(args[1]["x1"][mf.GUARD:] == 0)[0]) + mf.GUARD
     args[1]["x1"][q] = -0.0
-    assert mf.compare(*args) == []
+    assert judge(mf, args) == []
 
 
 def test_manifold_judge_rejects_planted_faults(mf, manifold_case):
@@ -294,16 +302,70 @@ def test_manifold_judge_rejects_planted_faults(mf, manifold_case):
     faults += [lambda a: a.__setitem__(2, False), lambda a: a.__setitem__(3, False)]              # a missing report; one that stays
     for plant in faults:
         args = manifold_answer(mf, manifold_case, n, n)
-        assert mf.compare(*args) == []
+        assert judge(mf, args) == []
         plant(args)
-        assert mf.compare(*args) != [], plant
+        assert judge(mf, args) != [], plant
     for k in (0, 1):                                                                              # a record at the device count's bound
         args = manifold_answer(mf, manifold_case, n, n - 9)
         byte(k, G + n - 9)(args)
-        assert mf.compare(*args) != []
+        assert judge(mf, args) != []
         args = manifold_answer(mf, manifold_case, n, n - 9)
         args[k][G + n - 10] = args[k][G + n - 11]                                                 # the last record inside it: compared
-        assert mf.compare(*args) != []
+        assert judge(mf, args) != []
     args = manifold_answer(mf, manifold_case, n, n, drop_bad=True)                                # a spurious report
     args[2] = True
-    assert mf.compare(*args) != []
+    assert judge(mf, args) != []
+
+
+@pytest.fixture(scope="module")
+def distance_case(wl):
+    """a reference answer of a query with one output: separated pairs with their closest points, hits and one bad entry"""
+    a, b = contact_cases.dense_poly_sets(wl, n=40, extent=3.0)
+    pairs = contact_cases.all_pairs(a[0].shape[1], b[0].shape[1])[::23].astype(np.int64)
+    pairs[5, 0] = a[0].shape[1] + 2            # out of its set: BAD_PAIR
+    want = distance_ref.poly_distances(a, b, pairs[:, 0], pairs[:, 1])
+    assert (want["hit"] == 0).sum() > 5 and (want["hit"] == 1).any() and ((want["flags"] & distance_ref.BAD_PAIR) != 0).sum() == 1
+    return want
+
+
+def distance_answer(mf, want, capacity, bound):
+    w = want[:bound].copy()
+    dt = h.DISTANCES.dts[0]
+    buf = np.frombuffer(bytes([mf.BAND]) * ((capacity + 2 * mf.GUARD) * dt.itemsize), dt).copy()
+    buf[mf.GUARD: mf.GUARD + bound] = w
+    return [buf, bool((w["flags"] & distance_ref.BAD_PAIR).any()), True, w, capacity]
+
+
+def test_single_output_judge_accepts_a_correct_answer(mf, distance_case):
+    n = len(distance_case)
+    for capacity, bound in ((n, n), (n + 3, n), (n, n - 9), (n, 5), (n, 0)):
+        args = distance_answer(mf, distance_case, capacity, bound)
+        assert args[1] == (bound > 5) and judge(mf, args, h.DISTANCES) == []
+
+
+def test_single_output_judge_rejects_planted_faults(mf, distance_case):
+    n, G = len(distance_case), mf.GUARD
+    far = int(np.flatnonzero((distance_case["hit"] == 0) & (distance_case["flags"] & distance_ref.BAD_PAIR == 0))[0])
+
+    def band_byte(record):
+        def plant(a):
+            a[0].view(np.uint8).reshape(len(a[0]), -1)[record, 3] = 0
+        return plant
+
+    def ulp(a):
+        v = a[0]["dist"][G + far: G + far + 1]
+        assert np.isfinite(v).all() and v[0] != 0
+        v.view(np.uint32)[0] += 1
+
+    def reserved(a):
+        a[0]["reserved1"][G + far] = 1
+
+    faults = [band_byte(r) for r in (0, G - 1, G + n, G + n + G - 1)] + [ulp, reserved, lambda a: a.__setitem__(1, False), lambda a: a.__setitem__(2, False)]
+    for plant in faults:      # a band byte on either side, a one-ulp float, a reserved field, a missing report, one that stays
+        args = distance_answer(mf, distance_case, n, n)
+        assert judge(mf, args, h.DISTANCES) == []
+        plant(args)
+        assert judge(mf, args, h.DISTANCES) != [], plant
+    args = distance_answer(mf, distance_case, n, n - 9)          # a record at the device count's bound
+    band_byte(G + n - 9)(args)
+    assert judge(mf, args, h.DISTANCES) != []

@@ -1,12 +1,11 @@
 """GPU tests of the swept queries (c2d_poly_pair_sweeps / c2d_rect_pair_sweeps): every field of every record equals
 tests/sweep_ref.py — the numpy restatement of the contract of include/c2d.h, pinned by tests/test_sweep_ref_cpu.py — floats bit for
 bit (+0 and -0 equal).  Every output buffer handed to the library sits between guard bands that are checked afterwards
-(pair_list_harness.run).  The last four tests state for sweeps what tests/test_gpu_pair_list_contract.py states for the other
-list-driven queries."""
+(pair_list_harness.run).  What every list-driven query promises of its list is tests/test_gpu_pair_list_contract.py's, for the sweeps
+as for the others; the last test here is what the sweeps alone refuse: half a motion, a misaligned plane."""
 import ctypes as C
 import importlib.util
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -17,56 +16,22 @@ sys.path.insert(0, HERE)
 import contact_cases as cases  # noqa: E402
 import sweep_ref as ref  # noqa: E402
 import pair_list_harness as h  # noqa: E402
-from pair_list_harness import BAND, RectsOnDevice, Uploaded, local, pairwise_gpu, rect_pairwise_gpu  # noqa: E402
+from pair_list_harness import BAND, Motion, RectsOnDevice, Uploaded, local, motions, pairwise_gpu, rect_pairwise_gpu  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 FUZZ_SEED = 20264
 F = np.float32
 LIST_LENGTHS = [0, 1, 63, 64, 65, 255, 256, 257, 4099]
-# the sweeps' row of pair_list_harness.QUERIES, kept here: the motions travel as keyword arguments of poly_call / rect_call
-Q = h.Query("sweeps", (ref.SWEEP_DT,), (ref.same,), ("records",), ref.BAD_PAIR, "poly_pair_sweeps", ref.poly_sweeps, "rect_pair_sweeps", ref.rect_sweeps)
-run, poly_call, rect_call, assert_same = Q.run, Q.poly_call, Q.rect_call, Q.assert_same
-
-
-class Motion:
-    """The motion of a set on the device: two planes f32[n], each behind `offset` floats of NaN.  .ptrs = (dx, dy), the a_motion /
-    b_motion of the Engine methods; .sub(r0) the planes of the shard that starts at object r0."""
-
-    def __init__(self, eng, m, offset=0):
-        host = np.full((2, len(m[0]) + offset), np.nan, F)
-        host[0, offset:], host[1, offset:] = m[0], m[1]
-        self.d = eng.to_device(host)
-        self.ptrs = (self.d.row(0) + 4 * offset, self.d.row(1) + 4 * offset)
-
-    def sub(self, r0):
-        return self.ptrs[0] + 4 * r0, self.ptrs[1] + 4 * r0
-
-    def free(self):
-        self.d.free()
-
-
-def motions(seed, n_a, n_b, scale=4.0):
-    rng = np.random.default_rng(seed)
-    return tuple(tuple((rng.uniform(-1, 1, n) * scale).astype(F) for _ in range(2)) for n in (n_a, n_b))
-
-
-def classes(want):
-    start = (want["flags"] & ref.START_OVERLAP) != 0
-    return start, (want["hit"] == 1) & ~start, want["hit"] == 0
+Q = h.SWEEPS
+run, poly_call, rect_call, assert_same, classes = Q.run, Q.poly_call, Q.rect_call, Q.assert_same, h.sweep_classes
 
 
 @pytest.fixture(scope="module")
 def dense(wl):
     """the dense sets (300 x 311 polygons), both moving by up to +-4 per component, with the reference records of ALL their pairs,
-    computed once and read-only -> a, b, pairs, ma, mb, want"""
-    a, b = cases.dense_poly_sets(wl)
-    pairs = cases.all_pairs(a[0].shape[1], b[0].shape[1])
-    ma, mb = motions(9101, a[0].shape[1], b[0].shape[1])
-    want = ref.poly_sweeps(a, b, *local(pairs), ma, mb)
-    want.setflags(write=False)
-    start, moving, miss = classes(want)
-    assert start.mean() > 0.1 and moving.mean() > 0.05 and miss.mean() > 0.3
-    return a, b, pairs, ma, mb, want
+    computed once and read-only (pair_list_harness.dense: every class of record has its share) -> a, b, pairs, ma, mb, want"""
+    a, b, pairs, want = h.dense(wl, Q)
+    return (a, b, pairs, *h.dense_extras(Q), want)
 
 
 def test_values_for_every_list_length(eng, dense):
@@ -398,127 +363,27 @@ def test_fuzzer_configurations_at_a_fixed_seed(eng):
     eng.check_async()
 
 
-# ---- the frame's contract, stated for sweeps as tests/test_gpu_pair_list_contract.py states it for the other queries -----------------
-
-def test_device_count_bounds_the_work(eng, dense):
-    """n_pairs = capacity with the count on the device: smaller (only that many records are written), equal, larger (clamped to
-    n_pairs), and no count at all.  run() checks the guard bands and every record beyond the bound."""
-    a, b, pairs, ma, mb, want = dense
-    ua, ub, da, db = Uploaded(eng, a), Uploaded(eng, b), Motion(eng, ma), Motion(eng, mb)
-    sel = np.arange(len(pairs))[5::311][:300]
-    call = poly_call(eng, ua.set, ub.set, a_motion=da.ptrs, b_motion=db.ptrs)
-    for n_dev in (0, 1, 63, 64, 137, 299, 300, 301, 1 << 40, (1 << 64) - 1, None):
-        got = run(eng, call, pairs[sel], capacity=300, n_dev=n_dev)
-        bound = 300 if n_dev is None else min(300, n_dev)
-        assert_same(got[:bound], want[sel[:bound]], f"device count {n_dev}")
-    got = run(eng, call, pairs[sel], capacity=1000, n_dev=300)
-    assert_same(got[:300], want[sel], "capacity 1000, count 300")
-    eng.check_async()
-    for x in (ua, ub, da, db):
-        x.free()
-
-
-def test_bad_pairs_read_nothing_and_are_reported_once(eng, wl):
-    """Indices equal to n, 0xFFFFFFFF and below the base, in either column, and polygons with a vertex count of 0 and 17: those
-    entries carry BAD_PAIR, every other entry is correct, and the error is reported once by the next synchronise.  The vertex planes
-    and the motion planes end where their allocations end; the frame's guard lets no such index reach a load."""
-    n_a, n_b, rb, cb = 50, 64, 1000, 5
-    a = wl.random_convex_polygon_set(n_a, seed=8001, extent=2.5)
-    b = wl.random_convex_polygon_set(n_b, seed=8002, kmax=8, extent=2.5, rows=8)
-    kb = b[2].copy()
-    kb[[3, 40]] = [0, 17]
-    b = (b[0], b[1], kb)
-    ma, mb = motions(9801, n_a, n_b, 2.5)
-    d = [eng.to_device(x) for x in (*a, *b, *ma, *mb)]        # exact allocations: nothing behind the last plane row
-    sa, sb = eng.poly_set(d[0], d[1], d[2], n_a, 16), eng.poly_set(d[3], d[4], d[5], n_b, 8)
-    good = cases.all_pairs(n_a, n_b)[::7].astype(np.int64) + (rb, cb)
-    bad = np.array([[rb + n_a, cb], [0xFFFFFFFF, cb + 1], [rb - 1, cb + 2], [rb + 1, cb + n_b], [rb + 2, 0xFFFFFFFF], [rb + 3, cb - 1],
-                    [0, 0], [0xFFFFFFFF, 0xFFFFFFFF], [rb + n_a + 70, cb + 3]], np.int64)
-    listed = good.copy()
-    at = np.array([0, 1, 63, 64, 65, 200, 255, 256, len(good) - 1])
-    listed[at] = bad
-    want = ref.poly_sweeps(a, b, listed[:, 0] - rb, listed[:, 1] - cb, ma, mb)
-    is_bad = want["flags"] == ref.BAD_PAIR
-    assert is_bad[at].all() and is_bad.sum() > len(at) and (~is_bad).sum() > 300          # (the bad counts as well)
-    eng.check_async()
-    call = poly_call(eng, sa, sb, a_motion=(d[6], d[7]), b_motion=(d[8], d[9]), row_base=rb, col_base=cb)
-    assert_same(run(eng, call, listed.astype(np.uint32), expect_error=True), want, "list with bad pairs")
-    # the same with rectangles (no absent objects there: only the indices)
-    ra = np.ascontiguousarray(np.concatenate([a[0][:4], a[1][:4]])[[0, 4, 1, 5, 2, 6, 3, 7]])
-    xa = RectsOnDevice(eng, ra)
-    want = ref.rect_sweeps(ra, ra, listed[:, 0] - rb, listed[:, 1] - cb, ma, None)
-    got = run(eng, rect_call(eng, xa, xa, a_motion=(d[6], d[7]), row_base=rb, col_base=cb), listed.astype(np.uint32), expect_error=True)
-    assert_same(got, want, "rectangle list with bad pairs")
-    xa.free()
-    # a clean call afterwards reports nothing
-    sound = good[(kb[good[:, 1] - cb] >= 1) & (kb[good[:, 1] - cb] <= 8)][:10]
-    clean = run(eng, call, sound.astype(np.uint32))
-    assert (clean["flags"] & ref.BAD_PAIR == 0).all()
-    eng.check_async()
-    for x in d:
-        x.free()
-
-
-def test_argument_errors(eng, pkg, wl):
-    """Every refused form returns -1 and writes nothing: the forms of the other list-driven queries, and a set's motion with exactly
-    one plane or a misaligned one (checked on the C call: the Python mirror refuses a half motion itself)."""
-    a = wl.random_convex_polygon_set(100, seed=5, extent=3.0)
-    ua = Uploaded(eng, a)
+def test_motion_argument_errors(eng, wl):
+    """What the sweeps refuse beyond the forms of every list-driven query (tests/test_gpu_pair_list_contract.py): a set's motion with
+    exactly one plane, or a misaligned one — on the C calls (the Python mirror refuses a half motion itself), with -1, nothing
+    written, and in front of the n_pairs == 0 no-op, which a sound motion on one set alone passes."""
+    ua = Uploaded(eng, wl.random_convex_polygon_set(100, seed=5, extent=3.0))
     S = ua.set
     d_pairs = eng.zeros((16, 2), np.uint32)
     d_out = eng.zeros(16, ref.SWEEP_DT)
-    d_n = eng.zeros(1, np.uint64)
     dm = Motion(eng, (np.ones(100, F), np.ones(100, F)))
     M = dm.ptrs
-    mk = lambda **kw: eng.poly_set(kw.get("vx", ua.px), kw.get("vy", ua.py), ua.dk, kw.get("n", 100), kw.get("rows", 16), kw.get("stride", 0))  # noqa: E731
     planes = [ua.px] * 8
     cplanes = (C.c_void_p * 8)(*planes)
     raw_poly, raw_rect = eng.lib.c2d_poly_pair_sweeps, eng.lib.c2d_rect_pair_sweeps
-    assert raw_poly(eng.h, None, C.byref(S), M[0], M[1], M[0], M[1], d_pairs.ptr, 16, None, 0, 0, d_out.ptr, None) == -1
-    assert raw_poly(eng.h, C.byref(S), None, M[0], M[1], M[0], M[1], d_pairs.ptr, 16, None, 0, 0, d_out.ptr, None) == -1
     for m4 in ((M[0], None, None, None), (None, M[1], None, None), (M[0], M[1], M[0], None), (None, None, None, M[1]),      # one NULL plane of a set
                (M[0] + 2, M[1], None, None), (None, None, M[0], M[1] + 1)):                                                  # a misaligned plane
         assert raw_poly(eng.h, C.byref(S), C.byref(S), *m4, d_pairs.ptr, 16, None, 0, 0, d_out.ptr, None) == -1, m4
         assert raw_rect(eng.h, cplanes, 100, cplanes, 100, *m4, d_pairs.ptr, 16, None, 0, 0, d_out.ptr, None) == -1, m4
         assert raw_poly(eng.h, C.byref(S), C.byref(S), *m4, None, 0, None, 0, 0, None, None) == -1, m4        # refused in front of the n_pairs == 0 no-op
-    poly, rect = eng.poly_pair_sweeps, eng.rect_pair_sweeps
-    bad = [
-        lambda: poly(mk(vx=0), S, d_pairs, 16, d_out, M, M),                           # a NULL plane
-        lambda: poly(S, mk(vy=0), d_pairs, 16, d_out, M, M),
-        lambda: poly(mk(rows=0), S, d_pairs, 16, d_out, M, M),                         # rows 0 or 17
-        lambda: poly(S, mk(rows=17), d_pairs, 16, d_out, M, M),
-        lambda: poly(mk(stride=99), S, d_pairs, 16, d_out, M, M),                      # stride < n
-        lambda: poly(mk(vx=ua.px + 2), S, d_pairs, 16, d_out, M, M),                   # a misaligned plane
-        lambda: poly(S, S, None, 16, d_out, M, M),                                     # no list
-        lambda: poly(S, S, d_pairs.ptr + 2, 15, d_out, M, M),                          # list not 4-byte aligned
-        lambda: poly(S, S, d_pairs, 16, d_out, M, M, n_pairs_dev=d_n.ptr + 4),         # count not 8-byte aligned
-        lambda: poly(S, S, d_pairs, 1 << 62 | 1, d_out, M, M),                         # n_pairs beyond 2^62
-        lambda: poly(S, S, d_pairs, 16, d_out, M, M, row_base=1 << 62),                # bases beyond 2^62
-        lambda: poly(S, S, d_pairs, 16, d_out, M, M, col_base=1 << 62),
-        lambda: poly(S, S, d_pairs, 16, None, M, M),                                   # the output missing
-        lambda: poly(S, S, d_pairs, 15, d_out.ptr + 8, M, M),                          # the output not 16-byte aligned
-        lambda: rect(planes[:7] + [0], 100, planes, 100, d_pairs, 16, d_out, M, M),
-        lambda: rect(planes, 100, planes[:7] + [0], 100, d_pairs, 16, d_out, M, M),
-        lambda: rect(planes, 100, planes, 100, None, 16, d_out, M, M),
-        lambda: rect(planes, 100, planes, 100, d_pairs, 16, None, M, M),
-        lambda: rect(planes, 100, planes, 100, d_pairs, 15, d_out.ptr + 4, M, M),
-        lambda: rect(planes, 100, planes, 100, d_pairs, 16, d_out, M, M, col_base=1 << 62),
-    ]
-    for n, call in enumerate(bad):
-        with pytest.raises(pkg.C2DError) as e:
-            call()
-        assert e.value.status == -1, n
-    poly(S, S, None, 0, None, M, None)                      # n_pairs == 0: a no-op
-    rect(planes, 100, planes, 100, None, 0, None)
+    eng.poly_pair_sweeps(S, S, None, 0, None, M, None)                      # n_pairs == 0: a no-op
+    eng.rect_pair_sweeps(planes, 100, planes, 100, None, 0, None)
     eng.synchronize()
     assert (d_out.get().view(np.uint8) == 0).all(), "a refused call wrote something"
-    for x in (d_pairs, d_n, ua, d_out, dm):
+    for x in (d_pairs, ua, d_out, dm):
         x.free()
-
-
-def test_graph_capture_follows_the_device_count():
-    """One capture of the polygon call with d_n_pairs and both motions, replayed with different counts written to the device in
-    between (tests/sweep_graph_check.py, its own process: torch has to be imported before libc2d.so)."""
-    out = subprocess.run([sys.executable, os.path.join(HERE, "sweep_graph_check.py")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    assert "sweeps graph ok" in out.stdout

@@ -1,4 +1,4 @@
-"""CPU test of tests/pair_list_harness.py itself: run(), banded() and unband() carry the guard-band coverage of all three list-driven
+"""CPU test of tests/pair_list_harness.py itself: run(), banded() and unband() carry the guard-band coverage of all four list-driven
 queries, so a silent mistake there would remove it everywhere at once.  The stand-in engine's device arrays are numpy buffers, the
 stand-in query a Python function that writes records through the pointers run() hands it."""
 import ctypes as C
@@ -75,9 +75,10 @@ def writer(dts, stray=None):
 
 @pytest.mark.parametrize("q", h.QUERIES, ids=repr)
 def test_the_table_has_the_bindings_records(pkg, q):
-    assert [dt.itemsize for dt in q.dts] == {"contacts": [16], "manifolds": [16, 32], "distances": [32]}[q.name]
-    assert q.dts == {"contacts": (pkg.CONTACT_DT,), "manifolds": (pkg.CONTACT_DT, pkg.MANIFOLD_DT), "distances": (pkg.DISTANCE_DT,)}[q.name]
-    assert pkg.CONTACT_DT.itemsize == 16 and pkg.MANIFOLD_DT.itemsize == 32 and pkg.DISTANCE_DT.itemsize == 32
+    assert [dt.itemsize for dt in q.dts] == {"contacts": [16], "manifolds": [16, 32], "distances": [32], "sweeps": [16]}[q.name]
+    assert q.dts == {"contacts": (pkg.CONTACT_DT,), "manifolds": (pkg.CONTACT_DT, pkg.MANIFOLD_DT), "distances": (pkg.DISTANCE_DT,),
+                     "sweeps": (pkg.SWEEP_DT,)}[q.name]
+    assert pkg.CONTACT_DT.itemsize == 16 and pkg.MANIFOLD_DT.itemsize == 32 and pkg.DISTANCE_DT.itemsize == 32 and pkg.SWEEP_DT.itemsize == 16
 
 
 @pytest.mark.parametrize("q", h.QUERIES, ids=repr)

@@ -3,38 +3,20 @@
 (tests/distance_ref.py, pinned by tests/test_distance_ref_cpu.py), after contact_fuzz.py: random set sizes, row layouts,
 vertex-count ranges, densities, strides and pointer offsets, bases, list lengths and device counts, clockwise polygons, points and
 segments, outliers, NaN / inf in real slots, junk in the padded slots, tied shapes (poly_broad_fuzz.py's random sets); rectangles as
-random quads, one time in three on a 1/16 grid (exact ties), some with non-finite vertices.  Prints its seed; a mismatch names its
-configuration.
+random quads, one time in three on a 1/16 grid (exact ties), some with non-finite vertices.  This file is the generator; the call
+and the judge are pair_list_fuzz.py's.  Prints its seed; a mismatch names its configuration.
 usage: distance_fuzz.py [configs] [seed]     (no seed: the commit's, tests/tools/fuzz_seed.py)"""
-import importlib
 import importlib.util
 import os
-import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(HERE))
-from __graft_entry__ import load_package  # noqa: E402
-import distance_ref as ref  # noqa: E402
-
-pkg = load_package()
-wl = importlib.import_module("c2d_amd.workloads")
-
-
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-pbf = _tool("poly_broad_fuzz")      # its random sets and its upload
-contact_fuzz = _tool("contact_fuzz")      # its random list
-fuzz_seed = _tool("fuzz_seed")
-
+spec = importlib.util.spec_from_file_location("pair_list_fuzz", os.path.join(HERE, "pair_list_fuzz.py"))
+plf = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(plf)            # the back half of every list-driven fuzz tool: run(), its judge, main(); it puts tests/ on the path
+h, wl, pbf = plf.h, plf.wl, plf.pbf
+contact_fuzz = plf.tool("contact_fuzz")      # its random list
 
 LAST = {}   # hits / misses of the last configuration, for the exploring leg's "not vacuous" check
 
@@ -46,6 +28,22 @@ def random_quads(rng, n):
     return q
 
 
+def random_sets(rng, n_a, n_b):
+    """two rectangle sets (random quads) three times in ten, else two polygon sets with where their planes go -> a, b, place (None for
+    rectangles: plf.run), their description"""
+    if rng.random() < 0.3:
+        a = random_quads(rng, n_a)
+        b = a if (n_a == n_b and rng.random() < 0.3) else random_quads(rng, n_b)
+        if rng.random() < 0.3:
+            a = wl.inject_non_finite(a, seed=int(rng.integers(1 << 30)), frac=0.1)
+        return a, b, None, f"rectangles {n_a} x {n_b}"
+    a, da = pbf.random_set(rng, n_a, int(rng.integers(1, 17)))
+    same = bool(rng.random() < 0.3)
+    b, db = (a, da) if same else pbf.random_set(rng, n_b, int(rng.integers(1, 17)))
+    place = [(int(rng.integers(0, 4)), int(rng.integers(0, 9))) for _ in range(1 if same else 2)]      # (offset, stride - n) of a set's planes
+    return a, b, place, f"polygons {n_a} x {b[0].shape[1]}, A {da}, B {'= A' if same else db}"
+
+
 def one(eng, rng, idx, announce=None):
     """One configuration; `announce(text)` is called with its description BEFORE any GPU work.  Returns (ok, (description, records))."""
     n_a, n_b = (int(rng.choice([1, 2, 63, 64, 65, 257, int(rng.integers(1, 600))])) for _ in range(2))
@@ -53,75 +51,15 @@ def one(eng, rng, idx, announce=None):
     rb, cb = (int(rng.choice([0, 0, 7, 1 << 20, (1 << 32) - 700])) for _ in range(2))
     cap = length + int(rng.choice([0, 0, 1, 100]))
     n_dev = rng.choice([None, length, max(length - 1, 0), length // 2, cap + 5])
-    rects = bool(rng.random() < 0.3)
-    if rects:
-        a = random_quads(rng, n_a)
-        b = a if (n_a == n_b and rng.random() < 0.3) else random_quads(rng, n_b)
-        if rng.random() < 0.3:
-            a = wl.inject_non_finite(a, seed=int(rng.integers(1 << 30)), frac=0.1)
-        desc = f"config {idx}: rectangles {n_a} x {n_b}, list {length} in {cap}, count {n_dev}, bases {rb}, {cb}"
-        keep = [eng.to_device(a), eng.to_device(b)]
-        pa, pb = [keep[0].row(k) for k in range(8)], [keep[1].row(k) for k in range(8)]
-    else:
-        a, da = pbf.random_set(rng, n_a, int(rng.integers(1, 17)))
-        same = bool(rng.random() < 0.3)
-        b, db = (a, da) if same else pbf.random_set(rng, n_b, int(rng.integers(1, 17)))
-        n_b = b[0].shape[1]
-        sa, keep = pbf.upload(eng, a, int(rng.integers(0, 4)), n_a + int(rng.integers(0, 9)))
-        sb, keep_b = (sa, ()) if same else pbf.upload(eng, b, int(rng.integers(0, 4)), n_b + int(rng.integers(0, 9)))
-        keep = list(keep) + list(keep_b)
-        desc = f"config {idx}: polygons {n_a} x {n_b}, A {da}, B {'= A' if same else db}, list {length} in {cap}, count {n_dev}, bases {rb}, {cb}"
+    a, b, place, what = random_sets(rng, n_a, n_b)
+    desc = f"config {idx}: {what}, list {length} in {cap}, count {n_dev}, bases {rb}, {cb}"
     if announce is not None:
         announce(desc)
-    pairs = contact_fuzz.random_list(rng, n_a, n_b, length)
-    listed = np.full((cap, 2), 0xFFFFFFFF, np.uint32)
-    listed[:length] = ((pairs + (rb, cb)) & 0xFFFFFFFF).astype(np.uint32)
-    # what the call sees is the u32 list minus the bases: an entry that wrapped is judged as the call judges it
-    li, lj = listed[:, 0].astype(np.int64) - rb, listed[:, 1].astype(np.int64) - cb
-    bound = cap if n_dev is None else min(cap, int(n_dev))
-    want = (ref.rect_distances(a, b, li[:bound], lj[:bound]) if rects else ref.poly_distances(a, b, li[:bound], lj[:bound]))
-    d_pairs = eng.to_device(listed)
-    d_out = eng.empty(cap + 2, ref.DISTANCE_DT)
-    eng.memset(d_out, 0xA5, d_out.nbytes)
-    d_n = None if n_dev is None else eng.to_device(np.array([int(n_dev)], np.uint64))
-    if rects:
-        eng.rect_pair_distances(pa, n_a, pb, n_b, d_pairs, cap, d_out.ptr + 32, n_pairs_dev=d_n, row_base=rb, col_base=cb)
-    else:
-        eng.poly_pair_distances(sa, sb, d_pairs, cap, d_out.ptr + 32, n_pairs_dev=d_n, row_base=rb, col_base=cb)
-    try:
-        eng.synchronize()
-        reported = False
-    except pkg.C2DError:
-        reported = True
-    raw = d_out.get()
-    for x in keep + [d_pairs, d_out] + ([d_n] if d_n is not None else []):
-        x.free()
-    got = raw[1:1 + bound]
-    untouched = (np.delete(raw.view(np.uint8).reshape(-1, 32), np.arange(1, 1 + bound), axis=0) == 0xA5).all()
-    ok = bool(ref.same(got, want).all()) and bool(untouched) and reported == bool((want["flags"] & ref.BAD_PAIR).any())
-    LAST.update(hits=int((want["hit"] != 0).sum()), misses=int((want["hit"] == 0).sum()))
-    if not ok:
-        print(f"MISMATCH {desc}: {int((~ref.same(got, want)).sum())} records differ, untouched {bool(untouched)}, error reported {reported}")
-    return ok, (desc, bound)
-
-
-def main():
-    configs = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-    seed, origin = (int(sys.argv[2]), "the command line") if len(sys.argv) > 2 else fuzz_seed.commit_seed()
-    print(f"distance_fuzz: {configs} configurations, seed {seed} ({origin})", flush=True)
-    rng = np.random.default_rng(seed)
-    eng = pkg.Engine(0)
-    fails = total = 0
-    for i in range(configs):
-        ok, info = one(eng, rng, i)
-        fails += not ok
-        total += info[-1]
-        if (i + 1) % 50 == 0:
-            print(f"  {i + 1} / {configs} configurations, {fails} failures so far", flush=True)
-    print(f"{configs} configurations, {fails} failures; {total} records compared")
-    eng.close()
-    sys.exit(1 if fails else 0)
+    pairs = contact_fuzz.random_list(rng, n_a, (b.shape if place is None else b[0].shape)[1], length)
+    ok, info, wants = plf.run(eng, h.DISTANCES, desc, a, b, pairs, cap, n_dev, rb, cb, place)
+    LAST.update(plf.hits_and_misses(wants))
+    return ok, info
 
 
 if __name__ == "__main__":
-    main()
+    plf.main("distance_fuzz", one, "records")
