@@ -7,9 +7,9 @@ HIPCC    ?= /opt/rocm/bin/hipcc
 # -fno-slp-vectorize: hipcc otherwise packs scalar f32 ops into v_pk_mul/add_f32, measured 2 % slower here.
 HIPFLAGS := -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -fPIC -Wall -Wextra -Wno-unused-parameter -Iinclude
 
-SRCS := $(CSRC)/c2d_api.hip $(CSRC)/c2d_host.hip $(CSRC)/c2d_sat.hip $(CSRC)/c2d_poly.hip $(CSRC)/c2d_poly_binned.hip $(CSRC)/c2d_mc.hip $(CSRC)/c2d_mc_poly.hip $(CSRC)/c2d_tables.hip $(CSRC)/c2d_dist.hip $(CSRC)/c2d_cross.hip $(CSRC)/c2d_broad.hip $(CSRC)/c2d_poly_cross.hip $(CSRC)/c2d_poly_broad.hip $(CSRC)/c2d_contact.hip $(CSRC)/c2d_distance.hip $(CSRC)/c2d_ray.hip $(CSRC)/c2d_ray_grid.hip $(CSRC)/c2d_sweep.hip
+SRCS := $(CSRC)/c2d_api.hip $(CSRC)/c2d_host.hip $(CSRC)/c2d_sat.hip $(CSRC)/c2d_poly.hip $(CSRC)/c2d_poly_binned.hip $(CSRC)/c2d_mc.hip $(CSRC)/c2d_mc_poly.hip $(CSRC)/c2d_tables.hip $(CSRC)/c2d_dist.hip $(CSRC)/c2d_cross.hip $(CSRC)/c2d_broad.hip $(CSRC)/c2d_poly_cross.hip $(CSRC)/c2d_poly_broad.hip $(CSRC)/c2d_contact.hip $(CSRC)/c2d_distance.hip $(CSRC)/c2d_ray.hip $(CSRC)/c2d_ray_grid.hip $(CSRC)/c2d_sweep.hip $(CSRC)/c2d_clearance.hip
 OBJS := $(SRCS:.hip=.o)
-HDRS := $(CSRC)/c2d_math.hpp $(CSRC)/c2d_mc_core.hpp $(CSRC)/c2d_count.hpp $(CSRC)/c2d_internal.hpp $(CSRC)/c2d_broad.hpp $(CSRC)/c2d_poly_pair.hpp $(CSRC)/c2d_cross.hpp $(CSRC)/c2d_cross_tiles.hpp $(CSRC)/c2d_pair_list.hpp $(CSRC)/c2d_ray_strips.hpp $(CSRC)/c2d_ray_rule.hpp $(CSRC)/c2d_ray_walk.hpp $(CSRC)/c2d_wave.hpp include/c2d.h include/utils.h
+HDRS := $(CSRC)/c2d_math.hpp $(CSRC)/c2d_mc_core.hpp $(CSRC)/c2d_count.hpp $(CSRC)/c2d_internal.hpp $(CSRC)/c2d_broad.hpp $(CSRC)/c2d_poly_pair.hpp $(CSRC)/c2d_cross.hpp $(CSRC)/c2d_cross_tiles.hpp $(CSRC)/c2d_pair_list.hpp $(CSRC)/c2d_ray_strips.hpp $(CSRC)/c2d_ray_rule.hpp $(CSRC)/c2d_ray_walk.hpp $(CSRC)/c2d_distance_rule.hpp $(CSRC)/c2d_clearance_bound.hpp $(CSRC)/c2d_wave.hpp include/c2d.h include/utils.h
 
 all: lib oracle drivers lib-fmad lib-nopretest lib-rehearsal lib-movecheck lib-splitcheck
 
@@ -38,7 +38,7 @@ clean:
 	rm -f $(OBJS) $(LIBDIR)/libc2d.so $(BINDIR)/generate_dataset $(BINDIR)/compute_collision_probability $(BINDIR)/ztest
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib oracle drivers tools clean lib-fmad lib-nopretest lib-rehearsal lib-mcstats lib-mcclock lib-ab-stamps lib-movecheck lib-splitcheck
+.PHONY: all lib oracle drivers tools clean lib-fmad lib-nopretest lib-rehearsal lib-mcstats lib-mcclock lib-ab-stamps lib-ab-clearance lib-movecheck lib-splitcheck
 
 # developer tools (not shipped in libc2d.so)
 TOOLS := $(CSRC)/tools/sat_tune $(CSRC)/tools/pose_probe $(CSRC)/tools/clock_probe $(CSRC)/tools/instr_probe $(CSRC)/tools/store_pattern_probe $(CSRC)/tools/stream_lifetime_probe $(CSRC)/tools/load_policy_probe
@@ -120,3 +120,11 @@ $(LIBDIR)/libc2d_stamp%.so: $(SRCS) $(HDRS)
 	@mkdir -p $(LIBDIR) build/stamp$*
 	for f in $(SRCS); do $(HIPCC) $(HIPFLAGS) -DC2D_WS_STAMP_MODE=$* -c $$f -o build/stamp$*/$$(basename $$f .hip).o || exit 1; done
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ build/stamp$*/*.o -ldl
+
+# measurement build (developer tool, not part of `all`): the clearance kernel without its certified skip (C2D_CLEARANCE_NO_SKIP in
+# c2d_clearance.hip), compared with the product library in one process by csrc/tools/clearance_bench.py (profiles/notes_r18_clearances.md)
+lib-ab-clearance: $(LIBDIR)/libc2d_clr_noskip.so
+$(CSRC)/c2d_clearance_noskip.o: $(CSRC)/c2d_clearance.hip $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -DC2D_CLEARANCE_NO_SKIP -c $< -o $@
+$(LIBDIR)/libc2d_clr_noskip.so: $(OBJS) $(CSRC)/c2d_clearance_noskip.o
+	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $(filter-out $(CSRC)/c2d_clearance.o,$(OBJS)) $(CSRC)/c2d_clearance_noskip.o -ldl

@@ -36,6 +36,9 @@ from .binding import (  # noqa: F401
     DISTANCE_BAD_PAIR,
     RAY_HIT_DT,
     RAY_START_INSIDE,
+    CLEARANCE_DT,
+    CLEARANCE_SKIP_SELF,
+    CLEARANCE_NONE,
     SWEEP_DT,
     SWEEP_START_OVERLAP,
     SWEEP_BAD_PAIR,

@@ -45,6 +45,11 @@ DISTANCE_EDGE_ON_B, DISTANCE_INTERIOR, DISTANCE_NO_CANDIDATE, DISTANCE_BAD_PAIR 
 RAY_HIT_DT = np.dtype([("poly", "<u4"), ("t", "<f4"), ("u", "<f4"), ("edge", "<u2"), ("hit", "u1"), ("flags", "u1")])   # c2d_ray_hit
 RAY_START_INSIDE = 1
 
+# clearance queries (include/c2d.h, "clearance queries: the nearest polygon of a set for every query polygon")
+CLEARANCE_DT = np.dtype([("poly", "<u4"), ("dist", "<f4"), ("ax", "<f4"), ("ay", "<f4"), ("bx", "<f4"), ("by", "<f4"), ("edge", "<u2"), ("vert", "<u2"),
+                         ("hit", "u1"), ("flags", "u1"), ("reserved0", "<u2")])   # c2d_clearance
+CLEARANCE_SKIP_SELF, CLEARANCE_NONE = 1, 16
+
 # swept queries (include/c2d.h, "swept queries: time of impact for listed pairs in linear motion")
 SWEEP_DT = np.dtype([("toi", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("axis", "<u2"), ("hit", "u1"), ("flags", "u1")])   # c2d_sweep
 SWEEP_START_OVERLAP, SWEEP_BAD_PAIR = 1, 2
@@ -191,6 +196,7 @@ _SIGNATURES = {
     "c2d_poly_ray_casts": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(_PolySet), C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_ray_casts_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(_PolySet), C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_ray_casts_grid_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
+    "c2d_poly_set_clearances": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "c2d_poly_pair_sweeps": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_rect_pair_sweeps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -833,6 +839,22 @@ class Engine:
         out = (C.c_ulonglong * 4)()
         self._check(self.lib.c2d_poly_ray_casts_grid_stats(self.h, out), "c2d_poly_ray_casts_grid_stats")
         return {"listed": int(out[0]), "visited": int(out[1]), "candidates": int(out[2]), "outliers": int(out[3])}
+
+    # -- clearance queries (include/c2d.h "clearance queries: the nearest polygon of a set for every query polygon") -----------------
+    def poly_set_clearances(self, a_set: _PolySet, b_set: _PolySet, d_out, row_base: int = 0, col_base: int = 0, flags: int = 0, stream: int = 0):
+        """c2d_poly_set_clearances: d_out[i] (CLEARANCE_DT[n_a], 16-byte aligned) = the polygon of b_set nearest to polygon i of a_set by
+        the distance contract, as col_base + j, with that pair's distance record; a_set, b_set from poly_set() (they may describe the
+        same memory); flags: 0 or CLEARANCE_SKIP_SELF (the pair with row_base + i == col_base + j is not considered)"""
+        if not isinstance(a_set, _PolySet) or not isinstance(b_set, _PolySet):
+            raise ValueError("need two poly_set() descriptions")
+        if d_out is None:
+            raise ValueError("need an output of CLEARANCE_DT[n_a]")
+        if isinstance(d_out, DeviceArray) and d_out.nbytes < CLEARANCE_DT.itemsize * a_set.n:
+            raise ValueError("the output holds fewer than n_a records")
+        if row_base < 0 or col_base < 0 or flags & ~CLEARANCE_SKIP_SELF:
+            raise ValueError("bases are not negative, and flags is 0 or CLEARANCE_SKIP_SELF")
+        self._check(self.lib.c2d_poly_set_clearances(self.h, C.byref(a_set), C.byref(b_set), row_base, col_base, flags, _ptr_of(d_out), C.c_void_p(stream)),
+                    "c2d_poly_set_clearances")
 
     # -- swept queries (include/c2d.h "swept queries: time of impact for listed pairs in linear motion") -----------------
     @staticmethod

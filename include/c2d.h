@@ -676,6 +676,60 @@ int c2d_poly_ray_casts_grid(c2d_ctx* ctx, const float* const d_rays[4] /* ox, oy
  * out[3] = regular polygons tested against every ray because their box may lie outside the grid's bounds. */
 int c2d_poly_ray_casts_grid_stats(c2d_ctx* ctx, unsigned long long out[4]);
 
+/* ---- clearance queries: the nearest polygon of a set for every query polygon ------
+ * An addition to 0.6 (c2d_version() stays 6), found by symbol lookup like the calls above.
+ *
+ * c2d_poly_set_clearances: for each polygon A_i of the set a — a robot link, a footprint along a path — WHICH polygon of the set b is
+ * nearest to it, HOW far it is and WHERE the two closest points lie.  An N x M reduction over the distance contract above: nothing of
+ * size n_a x n_b is written, and no row is left for the caller to reduce.  (The broad-phase lists hold only pairs whose boxes
+ * overlap: they cannot answer this.)
+ *   a, b       : the polygon sets, as for the cross forms: rows, stride, d_k == NULL (every polygon has `rows` vertices), shards by
+ *                pointer offset; a and b may be the same memory.  Rectangles go in as 4-gons with rows = 4.  Padded vertex slots are
+ *                never interpreted.
+ *   row_base   : the global index of A_0;  col_base: the global index of B_0: a record reports col_base + j.
+ *   flags      : 0 or C2D_CLEARANCE_SKIP_SELF (self-clearance of one set: a == b, row_base == col_base).
+ *   d_out      : c2d_clearance[n_a], 16-byte aligned; entry i is the record of A_i.  Records at or beyond n_a are never touched.
+ *
+ * The contract, stated through the distance contract.
+ *   per-pair records   for query i, D(i, j) is the c2d_distance record that c2d_poly_pair_distances defines for the pair (A_i, B_j).
+ *   considered         polygon j is considered when its vertex count is within 1..rows and it is not the self pair; with
+ *                      C2D_CLEARANCE_SKIP_SELF the self pair is the one with row_base + i == col_base + j, without the flag there is none.
+ *   the pick           the winner j* is the considered polygon with the smallest key (bits of D(i, j).dist, col_base + j).  dist is
+ *                      never NaN and never -0 and a hit pair has dist = +0, so the order of the bits is the order of the values;
+ *                      equal distances fall to the smaller index.  Ties are real: duplicated obstacles, two obstacles equally far, a
+ *                      hit and a separated pair whose d2 underflowed to 0.  A C2D_DISTANCE_NO_CANDIDATE pair has dist = +inf: it
+ *                      wins only when nothing nearer is considered.
+ *   the record         a winner exists: poly = col_base + j*, and dist, ax, ay, bx, by, edge, vert, hit and flags are the same-named
+ *                      fields of D(i, j*), bit for bit (+0 and -0 compare equal in the five floats); reserved0 = 0.
+ *                      Nothing considered (n_b == 0, only bad polygons, only the self pair): poly = 0xFFFFFFFF, dist = +inf, both
+ *                      points (0, 0), edge = vert = 0xFFFF, hit = 0, flags = C2D_CLEARANCE_NONE.
+ *                      A query with a vertex count outside 1..rows: poly = 0xFFFFFFFF, everything else 0, edge = vert = 0xFFFF,
+ *                      flags = C2D_DISTANCE_BAD_PAIR.
+ * A vertex count outside 1..rows in a or b is reported by the next c2d_stream_synchronize / c2d_ctx_check_async
+ * (C2D_ASYNC_ERR_POLY_K), as for the ray call.  The implementation evaluates polygons in parallel and may skip the candidates of a
+ * pair that a certified bound proves no nearer than the best so far; its results equal the rule above.
+ *
+ * n_a == 0 is a no-op.  NULL arguments, `rows` out of range, misaligned planes or a misaligned d_out, stride < n, unknown flag bits and
+ * row_base + n_a or col_base + n_b above 2^32 are refused (C2D_ERR_INVALID_ARG) before a device is touched.  The call is asynchronous
+ * on `stream` with no host synchronisation, and deterministic: two runs give the same bytes.  It uses no ctx scratch (the workspace
+ * guard is not involved) and is graph-capturable (a chain of kernel nodes). */
+#define C2D_CLEARANCE_SKIP_SELF 1   /* call flag: the pair with row_base + i == col_base + j is not considered */
+#define C2D_CLEARANCE_NONE 16       /* record flag: no polygon of B was considered */
+
+typedef struct c2d_clearance {  /* 32 bytes, 16-byte aligned output */
+    uint32_t poly;              /*  0: col_base + j of the winner; 0xFFFFFFFF: none */
+    float    dist;              /*  4 */
+    float    ax, ay;            /*  8: closest point on A_i */
+    float    bx, by;            /* 16: closest point on the winner */
+    uint16_t edge, vert;        /* 24, 26 */
+    uint8_t  hit, flags;        /* 28, 29: flags = the C2D_DISTANCE_* bits of the winning pair, or C2D_CLEARANCE_NONE */
+    uint16_t reserved0;         /* 30: written as 0 */
+} c2d_clearance;
+
+int c2d_poly_set_clearances(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b,
+                            size_t row_base, size_t col_base, int flags,
+                            c2d_clearance* d_out, c2d_stream stream);
+
 /* ---- swept queries: time of impact for listed pairs in linear motion ------------
  * Additions to 0.6 (c2d_version() stays 6), found by symbol lookup like the calls above.
  *
