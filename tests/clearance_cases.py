@@ -1,7 +1,14 @@
 """Inputs shared by the tests of the clearance query (test_clearance_ref_cpu.py, test_clearance_bound_cpu.py, test_gpu_clearances.py,
 clearance_graph_check.py, tools/clearance_fuzz.py): hand cases that are exact in binary32 with what the contract says of them, the
-sparse clearance scene, the adversarial set of the certified bound, and the numpy statement of a polygon's vertex box.  numpy only."""
+sparse clearance scene, the adversarial set of the certified bound, the numpy statement of a polygon's vertex box, and two
+constructions that make the main kernel's own decisions visible in `poly`: the hard input classes of contact_cases.py beside a witness
+(witness_batches) and obstacles that tie within a few ulp of dist (slid_near_ties); tests/test_clearance_cases_cpu.py holds what they
+promise on the reference alone.  numpy only."""
+import functools
+
 import numpy as np
+
+import contact_cases
 
 F = np.float32
 INF, NAN = float("inf"), float("nan")
@@ -158,3 +165,74 @@ def adversarial_bound_sets():
     for s in (a, b):      # every coordinate is a float as written
         assert np.isfinite(s[0]).all()
     return a, b
+
+
+# ---- a witness beside every obstacle: the boolean of every single pair shows in `poly` ----------------------------------------------
+WITNESS_LAYOUTS = {"one_tile": 1, "two_tiles": 64}      # name -> copies of B_j in front of the witness: [B_j, W] and [B_j x 64, W]
+FLT_MAX = float(np.finfo(F).max)
+
+
+def witness_half_side(a, b):
+    """S = four times the largest finite |coordinate| of the batch, clamped to what float32 holds"""
+    c = np.abs(np.concatenate([x.ravel() for x in (a[0], a[1], b[0], b[1])]).astype(np.float64))
+    return float(F(min(4.0 * c[np.isfinite(c)].max(), FLT_MAX)))
+
+
+@functools.lru_cache(maxsize=None)
+def witness_batches(wl):
+    """name -> (a, b, w, layouts) for every batch of contact_cases.hard_poly_batches: its sets a and b, the witness w (a set of one
+    polygon: the axis-parallel box of half side witness_half_side(a, b) about the origin, in b's rows), and layouts[name of
+    WITNESS_LAYOUTS] = (set, width): for every obstacle j the `width` polygons [B_j x (width - 1), W], laid out one behind the
+    other, so that the shard of obstacle j is the polygons width * j .. width * (j + 1) - 1.  By the contract the winner of query i
+    in the shard of j is the shard's index 0 exactly when D(i, j) is a hit or has dist == +0, as long as W is a hit for every query
+    (then W's key is (+0, width - 1), and only a B_j at +0 comes before it)."""
+    out = {}
+    for name, (a, b, _, _) in contact_cases.hard_poly_batches(wl).items():
+        S = witness_half_side(a, b)
+        rows, n_b = b[0].shape
+        w = polys([(-S, -S), (S, -S), (S, S), (-S, S)], rows=rows)
+        layouts = {}
+        for layout, copies in WITNESS_LAYOUTS.items():
+            width = copies + 1
+            idx = np.repeat(np.arange(n_b), width)
+            is_w = np.tile(np.arange(width) == copies, n_b)
+            layouts[layout] = (tuple(np.ascontiguousarray(np.where(is_w, w[p][..., :1], b[p][..., idx])) for p in range(3)), width)
+        for s in (a, b, w) + tuple(l[0] for l in layouts.values()):
+            for x in s:
+                x.setflags(write=False)
+        out[name] = (a, b, w, layouts)
+    return out
+
+
+# ---- obstacles within a few ulp of the best: where the main kernel's d2min must be the contract's to the last bit ----------------------
+SLAB = [(-30.0, -1.0), (30.0, -1.0), (30.0, 0.0), (-30.0, 0.0)]                      # 60 x 1, its top edge on the local x axis
+PENTAGON = [(0.0, 0.75), (0.6, 1.1), (0.4, 1.9), (-0.5, 1.8), (-0.7, 1.2)]           # its lowest vertex 0.75 above that edge
+NEAR_TIE_THETAS = (0.37, 1.1, 2.9, 4.0)
+NEAR_TIE_OFFSETS = ((0.0, 0.0), (100.0, -50.0))      # at the second the ulp of a coordinate is much larger than the ulp of dist
+
+
+def slid_near_ties(theta, offset, seed=9401, n_a=64, n_b=130):
+    """-> a, b: n_a copies of SLAB, each slid along its long direction by up to +-3, and n_b copies of PENTAGON, each slid along the
+    same direction by up to +-20 (its lowest vertex stays over the inside of every slab's top edge); everything rotated by theta
+    and moved by offset in float64 and rounded to float32 last.  In exact arithmetic every pair is 0.75 apart; in float32 the
+    obstacles of a query differ by rounding alone."""
+    rng = np.random.default_rng(seed)
+    c, s = np.cos(theta), np.sin(theta)
+
+    def place(shape, slide):
+        local = np.array(shape, np.float64)[None, :, :] + np.stack([slide, np.zeros_like(slide)], axis=-1)[:, None, :]     # [n][k][2]
+        x, y = c * local[..., 0] - s * local[..., 1] + offset[0], s * local[..., 0] + c * local[..., 1] + offset[1]
+        vx, vy = np.zeros((16, len(slide)), F), np.zeros((16, len(slide)), F)
+        vx[:len(shape)], vy[:len(shape)] = x.T.astype(F), y.T.astype(F)
+        return vx, vy, np.full(len(slide), len(shape), np.uint8)
+
+    return place(SLAB, rng.uniform(-3.0, 3.0, n_a)), place(PENTAGON, rng.uniform(-20.0, 20.0, n_b))
+
+
+def near_tie_shares(dist):
+    """dist f32 [n_a][n_b] (> 0) -> the share of the queries whose runner-up is 1..4 ulp of dist behind the winner, the share
+    whose best is exactly tied with another obstacle, and the share whose winner (the smallest index at the best) is beyond tile 0"""
+    bits = np.ascontiguousarray(dist).view(np.uint32).astype(np.int64)
+    low = np.sort(bits, axis=1)[:, :2]
+    gap = low[:, 1] - low[:, 0]
+    return float(((gap >= 1) & (gap <= 4)).mean()), float((gap == 0).mean()), float((bits.argmin(axis=1) >= 64).mean())

@@ -1,21 +1,29 @@
 """What the GPU tests of the clearance query share (test_gpu_clearances.py, tools/clearance_fuzz.py): the call between guard bands, the
 reference of a scene whose polygons repeat (computed on the distinct polygons and indexed), and the comparison with its message.
-A plain module on numpy and the numpy references: it never loads libc2d.so."""
+The per-pair records of the constructions of clearance_cases.py (witness_batches, slid_near_ties) are computed once per process here, for
+test_clearance_cases_cpu.py and the GPU tests alike.  A plain module on numpy and the numpy references: it never loads libc2d.so."""
+import functools
+
 import numpy as np
 import pytest
 
+import clearance_cases as cases
 import clearance_ref as ref
 import pair_list_harness as h
 
 DT = ref.CLEARANCE_DT
 
 
-def call(eng, a_set, b_set, n_a, capacity=None, expect_error=False, **kw):
+def call(eng, a_set, b_set, n_a, capacity=None, expect_error=False, band=None, **kw):
     """c2d_poly_set_clearances into a buffer between guard bands -> the n_a records; the bands and every record at or beyond n_a
-    must be untouched; under expect_error the next synchronise reports status -1, once"""
+    must be untouched; under expect_error the next synchronise reports status -1, once.  band: a buffer of h.banded(eng, cap, DT) to
+    use again (many small calls: it is filled with the band's byte first and stays the caller's)"""
     cap = max(n_a, 4) if capacity is None else capacity
-    d = h.banded(eng, cap, DT)
+    d = h.banded(eng, cap, DT) if band is None else band
     try:
+        if band is not None:
+            assert d.nbytes == (cap + 2 * h.GUARD) * DT.itemsize
+            eng.memset(d, h.BAND, d.nbytes)
         eng.poly_set_clearances(a_set, b_set, d.ptr + DT.itemsize * h.GUARD, **kw)
         if expect_error:
             with pytest.raises(Exception) as e:
@@ -27,7 +35,8 @@ def call(eng, a_set, b_set, n_a, capacity=None, expect_error=False, **kw):
             eng.synchronize()
         return h.unband(d, cap, n_a, DT)[:n_a].copy()
     finally:
-        d.free()
+        if band is None:
+            d.free()
 
 
 def twice(eng, a_set, b_set, n_a, what, **kw):
@@ -43,13 +52,30 @@ def take(s, idx):
     return np.ascontiguousarray(s[0][:, idx]), np.ascontiguousarray(s[1][:, idx]), None if s[2] is None else np.ascontiguousarray(s[2][idx])
 
 
-def indexed_reference(a, ia, b, ib, **kw):
-    """the reference of (take(a, ia), take(b, ib)): the per-pair records are computed for the distinct polygons once and indexed"""
+def indexed_reference(a, ia, b, ib, D=None, by_query=None, **kw):
+    """the reference of (take(a, ia), take(b, ib)): the per-pair records are computed for the distinct polygons once (or handed in
+    as D) and indexed.  by_query (the default beyond 2^22 pairs): the pick is made once per DISTINCT query against take(b, ib) and
+    indexed by ia, so that the cost does not grow with len(ia); the self pair of SKIP_SELF depends on the query's own place, and
+    matters only where it is the winner: those queries are reduced one by one."""
     ia, ib = np.asarray(ia, np.int64), np.asarray(ib, np.int64)
     if len(ia) == 0:
         return np.zeros(0, DT)
-    D = ref.pair_records(a, b) if b[0].shape[1] else np.zeros((a[0].shape[1], 0), ref.dref.DISTANCE_DT)
-    return ref.reduce(D[np.ix_(ia, ib)], ref.bad_counts(a)[ia], ref.bad_counts(b)[ib], **kw)
+    if D is None:
+        D = ref.pair_records(a, b) if b[0].shape[1] else np.zeros((a[0].shape[1], 0), ref.dref.DISTANCE_DT)
+    bad_a, bad_b = ref.bad_counts(a), ref.bad_counts(b)[ib]
+    if by_query is None:
+        by_query = len(ia) * len(ib) > 1 << 22
+    if not by_query:
+        return ref.reduce(D[np.ix_(ia, ib)], bad_a[ia], bad_b, **kw)
+    rb, cb, flags = kw.get("row_base", 0), kw.get("col_base", 0), kw.get("flags", 0)
+    Db = D[:, ib]
+    out = ref.reduce(Db, bad_a, bad_b, col_base=cb)[ia]
+    if flags & ref.SKIP_SELF:
+        j_self = rb + np.arange(len(ia), dtype=np.int64) - cb
+        own = (j_self >= 0) & (j_self < len(ib)) & (out["poly"].astype(np.int64) == cb + j_self)
+        for q in np.flatnonzero(own):
+            out[q] = ref.reduce(Db[ia[q]:ia[q] + 1], bad_a[ia[q]:ia[q] + 1], bad_b, row_base=rb + int(q), col_base=cb, flags=flags)[0]
+    return out
 
 
 def assert_same(got, want, what):
@@ -57,3 +83,33 @@ def assert_same(got, want, what):
     if not ok.all():
         q = int(np.flatnonzero(~ok)[0])
         raise AssertionError(f"{what}: {int((~ok).sum())} of {len(want)} records differ; first at {q}: got {got[q]}, want {want[q]}")
+
+
+@functools.lru_cache(maxsize=None)
+def witness_records(wl, name):
+    """-> D [n_a][n_b], DW [n_a][1]: the per-pair records of batch `name` of cases.witness_batches and of its queries against the
+    witness (read-only)"""
+    a, b, w, _ = cases.witness_batches(wl)[name]
+    D, DW = ref.pair_records(a, b), ref.pair_records(a, w)
+    D.setflags(write=False)
+    DW.setflags(write=False)
+    return D, DW
+
+
+def witness_reference(wl, name, layout, j):
+    """the reference of batch `name`'s queries against the shard of obstacle j in `layout`, col_base being the shard's offset"""
+    a, b, w, layouts = cases.witness_batches(wl)[name]
+    D, DW = witness_records(wl, name)
+    width = layouts[layout][1]
+    records = np.concatenate([np.repeat(D[:, j:j + 1], width - 1, axis=1), DW], axis=1)
+    bad_b = np.concatenate([np.repeat(ref.bad_counts(b)[j:j + 1], width - 1), ref.bad_counts(w)])
+    return ref.reduce(records, ref.bad_counts(a), bad_b, col_base=width * j)
+
+
+@functools.lru_cache(maxsize=None)
+def near_tie_records(theta, offset):
+    """-> a, b, D: cases.slid_near_ties(theta, offset) and its per-pair records [64][130] (read-only)"""
+    a, b = cases.slid_near_ties(theta, offset)
+    D = ref.pair_records(a, b)
+    D.setflags(write=False)
+    return a, b, D

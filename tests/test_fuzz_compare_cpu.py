@@ -1,5 +1,5 @@
 """CPU test of the judges of the differential fuzzers (compare() of tests/tools/cross_fuzz.py — shared by poly_cross_fuzz.py —
-broad_fuzz.py and pair_list_fuzz.py, the one of the four list-driven tools): each is fed a correct answer, which it must accept, and then one planted fault at a time, each
+broad_fuzz.py and pair_list_fuzz.py, the one of the four list-driven tools; and clearance_ref.same, the judge of clearance_fuzz.py): each is fed a correct answer, which it must accept, and then one planted fault at a time, each
 of which it must reject.  A judge that lets a fault pass would turn every leg that relies on it green for nothing."""
 import importlib.util
 import os
@@ -10,6 +10,8 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import clearance_cases  # noqa: E402
+import clearance_ref  # noqa: E402
 import contact_cases  # noqa: E402
 import contact_ref  # noqa: E402
 import distance_ref  # noqa: E402
@@ -369,3 +371,65 @@ def test_single_output_judge_rejects_planted_faults(mf, distance_case):
     args = distance_answer(mf, distance_case, n, n - 9)          # a record at the device count's bound
     band_byte(G + n - 9)(args)
     assert judge(mf, args, h.DISTANCES) != []
+
+
+# ---- the record judge of the clearance fuzzer: clearance_ref.same -------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def clearance_case(wl):
+    """a reference answer with separated winners and their closest points, hits, a query with a bad count and one with nothing to consider"""
+    a, b = clearance_cases.scene(wl, n_a=60, n_b=40, extent=12.0)
+    a = tuple(x.copy() for x in a)
+    a[2][7] = 0
+    want = clearance_ref.clearances(a, b, row_base=3, col_base=5)
+    want[11] = clearance_ref.clearances(a, clearance_cases.empty())[11]
+    assert (want["hit"] == 1).sum() > 5 and ((want["hit"] == 0) & (want["poly"] != clearance_ref.NO_POLY)).sum() > 5
+    assert want["flags"][7] == distance_ref.BAD_PAIR and want["flags"][11] == clearance_ref.NONE_FLAG
+    want.setflags(write=False)
+    return want
+
+
+def test_clearance_judge_accepts_a_correct_answer(clearance_case):
+    want = clearance_case
+    assert clearance_ref.same(want.copy(), want).all() and len(clearance_ref.same(want[:0].copy(), want[:0])) == 0
+    got = want.copy()                      # +0 and -0 are equal in every float, a hit's zeros and a separated winner's alike
+    for f in clearance_ref.FLOATS:
+        zero = np.flatnonzero(got[f] == 0)
+        assert len(zero) > 0
+        got[f][zero] = -0.0
+        assert np.signbit(got[f][zero]).all() and not np.signbit(want[f][zero]).any()
+    assert clearance_ref.same(got, want).all() and clearance_ref.same(want, got).all()
+
+
+def test_clearance_judge_rejects_planted_faults(clearance_case):
+    want = clearance_case
+    far = int(np.flatnonzero((want["hit"] == 0) & (want["poly"] != clearance_ref.NO_POLY) & (want["ax"] != 0) & (want["ay"] != 0) & (want["bx"] != 0) & (want["by"] != 0))[0])
+    hit = int(np.flatnonzero(want["hit"] == 1)[0])
+
+    def ulp(f, step):
+        def plant(g):
+            v = g[f][far: far + 1]
+            assert np.isfinite(v).all() and v[0] != 0
+            v.view(np.int32)[0] += step
+        return plant
+
+    def field(name, q, value):
+        def plant(g):
+            assert g[name][q] != value
+            g[name][q] = value
+        return plant
+
+    faults = [ulp(f, step) for f in clearance_ref.FLOATS for step in (1, -1)]
+    faults += [field("poly", far, int(want["poly"][far]) + 1), field("poly", hit, int(want["poly"][hit]) - 1), field("poly", 11, 0), field("poly", 7, 5)]
+    faults += [field("edge", far, int(want["edge"][far]) ^ 1), field("vert", far, int(want["vert"][far]) ^ 1), field("edge", hit, 0), field("vert", hit, 0)]
+    faults += [field("hit", far, 1), field("hit", hit, 0), field("flags", far, int(want["flags"][far]) ^ distance_ref.INTERIOR),
+               field("flags", far, int(want["flags"][far]) ^ distance_ref.EDGE_ON_B), field("flags", 7, 0), field("flags", 11, 0)]
+    faults += [field("reserved0", far, 1), field("reserved0", hit, 0x8000), field("dist", hit, np.float32(1e-45)), field("dist", 11, np.float32(3e38))]
+    for plant in faults:
+        got = want.copy()
+        assert clearance_ref.same(got, want).all()
+        plant(got)
+        ok = clearance_ref.same(got, want)
+        assert (~ok).sum() == 1, plant      # the planted record, and no other
+    got = want.copy()                       # a NaN where a number belongs is a difference
+    got["dist"][far] = np.nan
+    assert not clearance_ref.same(got, want)[far]

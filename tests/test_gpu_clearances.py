@@ -2,7 +2,17 @@
 restatement of the contract of include/c2d.h, the reduction over tests/distance_ref.py, pinned by tests/test_clearance_ref_cpu.py —
 the five floats bit for bit (+0 and -0 equal); each record also equals what c2d_poly_pair_distances gives for the pair (i, winner)
 on the GPU, and `hit` the OR of the row of c2d_sat_poly_cross_mask.  Every output buffer handed to the library sits between guard
-bands that are checked afterwards.  No test case asks the numpy reference for more than 1e5 pairs."""
+bands that are checked afterwards.  No test case asks the numpy reference for more than 1e5 pairs.
+
+The finalise pass recomputes the winner's record, so what the main kernel's own copy of the pairwise test and its own d2min got wrong
+shows only in WHO wins.  Four tests make that visible (their inputs are proved on the reference alone in test_clearance_cases_cpu.py):
+test_hard_batches_whole                       the hard input classes of contact_cases.py, each batch's A against its whole B
+test_every_pairs_boolean_through_a_witness    every pair of those batches alone beside a witness that hits every query, in one tile
+                                              and across two strips: `poly` says what the main kernel's walk decided, and it must be
+                                              what c2d_sat_poly_pairs_rows decides on the GPU in the same run
+test_near_ties_between_obstacles              130 different obstacles within a few ulp of dist of each other, and exactly tied, as
+                                              built, reversed and spread over 17 strips
+test_between_one_strip_and_one_per_tile       1 < strips < column tiles, an uneven split, many row tiles"""
 import ctypes as C
 import importlib.util
 import os
@@ -54,6 +64,104 @@ def many_queries(wl):
     want.setflags(write=False)
     assert 0.05 < (want["hit"] == 1).mean() < 0.8 and (want["hit"] == 0).mean() > 0.2
     return a, b, want
+
+
+HARD_NAMES = ["clockwise", "clockwise_both", "repeated_vertices", "k1_k2", "touching", "equal_shapes", "equal_boxes", "scale_1e30", "scale_1e-30",
+              "scale_1e-42", "scale_1e18", "scale_1e-18", "non_finite_vertex0", "non_finite_later_vertex", "overflowing_len2"]
+
+
+@pytest.mark.parametrize("name", HARD_NAMES)
+def test_hard_batches_whole(eng, wl, name):
+    """one small batch per class of tests/contact_cases.py, the batch's queries against all of its obstacles, twice (the same bytes):
+    where masking the padding, the closing edge, k = 1 / 2, exact ties, overflow, underflow and the two NaN rules go wrong in the
+    main kernel's own walk of the axes"""
+    assert sorted(contact_cases.hard_poly_batches(wl)) == sorted(HARD_NAMES), "a batch of hard_poly_batches is not run"
+    a, b, _, _ = cases.witness_batches(wl)[name]
+    D, _ = ch.witness_records(wl, name)
+    ua, ub = Uploaded(eng, a), Uploaded(eng, b)
+    got = ch.twice(eng, ua.set, ub.set, a[0].shape[1], name)
+    ch.assert_same(got, ref.reduce(D, ref.bad_counts(a), ref.bad_counts(b)), name)
+    eng.check_async()
+    ua.free()
+    ub.free()
+
+
+@pytest.mark.parametrize("name", HARD_NAMES)
+def test_every_pairs_boolean_through_a_witness(eng, wl, name):
+    """Every obstacle j of a hard batch alone with a witness W that hits every query: [B_j, W] in one staged tile, and [B_j x 64, W]
+    with W alone in tile 1 (one row tile: another strip, so the atomic minimum decides).  One call per obstacle on a pointer shard,
+    col_base the shard's offset.  The winner is the shard's index 0 exactly when the pair (A_i, B_j) is a hit (or at dist +0), else
+    W: every boolean of the main kernel's walk is in `poly`, and must be c2d_sat_poly_pairs_rows' boolean of the pair, computed on
+    the GPU here."""
+    a, b, w, layouts = cases.witness_batches(wl)[name]
+    D, _ = ch.witness_records(wl, name)
+    n_a, n_b = a[0].shape[1], b[0].shape[1]
+    pairwise = h.pairwise_gpu(eng, a, b, contact_cases.all_pairs(n_a, n_b)).reshape(n_a, n_b) != 0
+    first = pairwise | (D["dist"] == 0)
+    ua = Uploaded(eng, a)
+    band = h.banded(eng, n_a, ch.DT)
+    for layout, (s, width) in layouts.items():
+        ub = Uploaded(eng, s)
+        assert strips_of(eng, n_a, width) == -(-width // TILE_COLS)
+        for j in range(n_b):
+            what = f"{name}, {layout}, obstacle {j}"
+            got = ch.call(eng, ua.set, ub.sub(width * j, width * (j + 1)), n_a, band=band, col_base=width * j)
+            ch.assert_same(got, ch.witness_reference(wl, name, layout, j), what)
+            wrong = np.flatnonzero((got["poly"] == width * j) != first[:, j])
+            assert len(wrong) == 0, f"{what}: the main kernel and c2d_sat_poly_pairs_rows disagree on the pairs of queries {wrong[:8]}"
+            assert np.isin(got["poly"], [width * j, width * j + width - 1]).all(), what
+        ub.free()
+    eng.check_async()
+    band.free()
+    ua.free()
+
+
+def test_near_ties_between_obstacles(eng):
+    """tests/clearance_cases.py slid_near_ties: 64 slabs against 130 pentagons that are all 0.75 away in exact arithmetic.  At the
+    origin the runner-up is 1..4 ulp of dist behind the winner for a quarter of the queries and more; at (100, -50) most queries
+    have their best exactly tied between different obstacles.  The main kernel's d2min must be the contract's to the last bit, its
+    comparison strict and its ties the smallest index: as built and reversed (each twice, the same bytes), and at the origin
+    tiled to 1 025 obstacles, the near-tied ones in 17 different strips"""
+    for theta in cases.NEAR_TIE_THETAS:
+        for offset in cases.NEAR_TIE_OFFSETS:
+            a, b, D = ch.near_tie_records(theta, offset)
+            ia = np.arange(a[0].shape[1])
+            orders = {"as built": np.arange(130), "reversed": np.arange(130)[::-1]}
+            if offset == cases.NEAR_TIE_OFFSETS[0]:
+                orders["tiled to 1025"] = np.resize(np.arange(130), 1025)
+            ua = Uploaded(eng, a)
+            for order, ib in orders.items():
+                what = f"theta {theta}, offset {offset}, {order}"
+                ub = Uploaded(eng, ch.take(b, ib))
+                got = ch.twice(eng, ua.set, ub.set, 64, what)
+                ch.assert_same(got, ch.indexed_reference(a, ia, b, ib, D=D), what)
+                assert strips_of(eng, 64, len(ib)) == -(-len(ib) // TILE_COLS)
+                ub.free()
+            ua.free()
+    eng.check_async()
+
+
+@pytest.mark.parametrize("s", [2, 4])
+def test_between_one_strip_and_one_per_tile(eng, sparse, s):
+    """8 * cus / s row tiles (the last one of 5 queries) against 513 polygons, 9 column tiles: 1 < strips < 9 and 9 is no multiple
+    of it, so the strips hold unequal numbers of tiles (on 256 CUs: 2 strips of 5 + 4 and 4 of 3 + 2 + 2 + 2), a lane's best is
+    carried from tile to tile while the other strips race it through the atomic minimum, and blockIdx.x / strips and % strips
+    run over many row tiles.  The queries are drawn from 64 distinct polygons."""
+    a, b, D = sparse
+    cus = eng.info()["compute_units"]
+    row_tiles = 8 * cus // s
+    n = TILE_ROWS * row_tiles - 251
+    strips = strips_of(eng, n, 513) if n > 0 else 0
+    if not (1 < strips < 9 and 9 % strips != 0):
+        pytest.skip(f"{cus} compute units give {strips} strips for 8 * cus / {s} row tiles against 9 column tiles: not strictly between, unevenly split")
+    print(f"{cus} compute units, {row_tiles} row tiles, {n} queries: {strips} strips over 9 column tiles")
+    ia = np.random.default_rng(9361 + s).integers(0, 64, n)
+    ua, ub = Uploaded(eng, ch.take(a, ia)), Uploaded(eng, b)
+    got = ch.twice(eng, ua.set, ub.set, n, f"{strips} strips")
+    ch.assert_same(got, ref.reduce(D, ref.bad_counts(a), ref.bad_counts(b))[ia], f"{n} queries against 513 in {strips} strips")
+    eng.check_async()
+    ua.free()
+    ub.free()
 
 
 def test_every_number_of_queries(eng, many_queries):

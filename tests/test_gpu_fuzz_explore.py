@@ -12,13 +12,14 @@ $C2D_FUZZ_SECONDS, default 40, is the budget of each of the first five legs (sat
 sequential generator through their configurations: configuration i is a function of the seed and of every draw of configurations
 0 .. i - 1, so a failure there reproduces only by running the leg from its start.
 
-The ten legs added after them (rect_cross .. sweeps: the N x M, broad-phase, list-driven, ray and polygon Monte-Carlo entry points,
-tests/tools/cross_fuzz.py, poly_cross_fuzz.py, broad_fuzz.py, poly_broad_fuzz.py, contact_fuzz.py, manifold_fuzz.py, distance_fuzz.py,
-ray_fuzz.py, mc_poly_fuzz.py, sweep_fuzz.py) get one eighth of that budget each, 5 s by default (ten eighths in all), and draw configuration i from
+The twelve legs added after them (rect_cross .. clearances: the N x M, broad-phase, list-driven, ray, polygon Monte-Carlo, grid ray and
+clearance entry points, tests/tools/cross_fuzz.py, poly_cross_fuzz.py, broad_fuzz.py, poly_broad_fuzz.py, contact_fuzz.py, manifold_fuzz.py,
+distance_fuzz.py, ray_fuzz.py, mc_poly_fuzz.py, sweep_fuzz.py, ray_grid_fuzz.py, clearance_fuzz.py) get one eighth of that budget each, 5 s
+by default (twelve eighths in all), and draw configuration i from
 np.random.default_rng([leg seed, i]): there a configuration IS a function of (seed, index) alone, and
     C2D_FUZZ_SEED=<base seed> C2D_FUZZ_INDEX=<i> python -m pytest tests/test_gpu_fuzz_explore.py -m gpu -k <leg>
-runs exactly that one.  Over its run each of the ten must have compared a colliding and a non-colliding result (rays: a hit and a
-miss; mc_poly: a scene with 0 < hits < samples)."""
+runs exactly that one.  Over its run each of the twelve must have compared a colliding and a non-colliding result (rays and grid rays: a
+hit and a miss; clearances: a winner that is hit and one that is not; mc_poly: a scene with 0 < hits < samples)."""
 import importlib.util
 import os
 import time
@@ -31,12 +32,15 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 OLD_LEGS = ("sat_rect_pose", "sat_poly_rows", "sat_poly_binned", "mc_scenes", "sat_rect_verts")   # one sequential generator each, the whole budget
-NEW_LEGS = ("rect_cross", "poly_cross", "rect_broad", "poly_broad", "contacts", "manifolds", "distances", "rays", "mc_poly", "sweeps")   # a stream per configuration, an eighth
+NEW_LEGS = ("rect_cross", "poly_cross", "rect_broad", "poly_broad", "contacts", "manifolds", "distances", "rays", "mc_poly", "sweeps",
+            "ray_grid", "clearances")   # a stream per configuration, an eighth
 LEGS = OLD_LEGS + NEW_LEGS   # (append only: a leg's seed offset is its index)
 TOOL = {"sat_rect_verts": "verts_fuzz", "sat_rect_pose": "pose_fuzz", "sat_poly_rows": "poly_fuzz", "sat_poly_binned": "binned_fuzz", "mc_scenes": "mc_fuzz",
         "rect_cross": "cross_fuzz", "poly_cross": "poly_cross_fuzz", "rect_broad": "broad_fuzz", "poly_broad": "poly_broad_fuzz", "contacts": "contact_fuzz",
-        "manifolds": "manifold_fuzz", "distances": "distance_fuzz", "rays": "ray_fuzz", "mc_poly": "mc_poly_fuzz", "sweeps": "sweep_fuzz"}
+        "manifolds": "manifold_fuzz", "distances": "distance_fuzz", "rays": "ray_fuzz", "mc_poly": "mc_poly_fuzz", "sweeps": "sweep_fuzz",
+        "ray_grid": "ray_grid_fuzz", "clearances": "clearance_fuzz"}
 TAKES_ORACLE = ("rect_cross", "poly_cross", "rect_broad", "manifolds")   # one(eng, rng, idx, announce, oracle)
+TAKES_WL = ("clearances",)   # one(eng, wl, rng, idx, announce)
 
 
 def _tool(name):
@@ -47,7 +51,7 @@ def _tool(name):
 
 
 @pytest.mark.parametrize("leg", LEGS)
-def test_differential_fuzz_at_this_commits_seed(eng, oracle, capsys, leg):   # (`oracle`: sizes the OpenMP team to the box's CPU share)
+def test_differential_fuzz_at_this_commits_seed(eng, oracle, wl, capsys, leg):   # (`oracle`: sizes the OpenMP team to the box's CPU share)
     base, origin = _tool("fuzz_seed").commit_seed()
     seed = (base + 0x3C6EF35F * LEGS.index(leg)) & 0x7FFFFFFF   # one stream per leg
     new = leg in NEW_LEGS
@@ -86,7 +90,7 @@ def test_differential_fuzz_at_this_commits_seed(eng, oracle, capsys, leg):   # (
             elif not new:
                 ok, what = fz.one(eng, rng, i, announce)
             else:   # a stream of its own per configuration: (seed, index) alone names it
-                args = (eng, np.random.default_rng([seed, i]), i, announce) + ((oracle,) if leg in TAKES_ORACLE else ())
+                args = (eng,) + ((wl,) if leg in TAKES_WL else ()) + (np.random.default_rng([seed, i]), i, announce) + ((oracle,) if leg in TAKES_ORACLE else ())
                 ok, what = fz.one(*args)
                 if leg == "mc_poly":
                     hit = miss = hit or bool(((fz.LAST["hits"] > 0) & (fz.LAST["hits"] < fz.LAST["samples"])).any())

@@ -3,8 +3,10 @@
 tests/test_clearance_ref_cpu.py): random set sizes on both sides of the kernel's tiles, row layouts, vertex-count ranges, densities
 from crowded to sparse (where the certified skip fires), repeated polygons (ties between obstacles), scales inside and outside the
 bound's domain and in the band where d2 underflows to 0 while the exact test still separates (a hit and a separated pair then tie), NaN / inf in real slots, vertex counts out of range in both sets, strides and pointer offsets, bases, d_k == NULL,
-and one set against itself under C2D_CLEARANCE_SKIP_SELF.  The reference is computed for the distinct polygons and indexed, so a
-configuration costs a few thousand reference pairs.  Prints its seed; a mismatch names its configuration.
+one set against itself under C2D_CLEARANCE_SKIP_SELF, and (about one configuration in seven, two sets only) so many queries that the
+launch lies between one strip and one strip per column tile: several tiles per strip, split unevenly, with many row tiles.  The
+reference is computed for the distinct polygons and indexed, so a configuration costs a few thousand reference pairs however many
+queries it has.  Prints its seed; a mismatch names its configuration.
 usage: clearance_fuzz.py [configs] [seed]"""
 import os
 import sys
@@ -23,11 +25,19 @@ from pair_list_harness import Uploaded  # noqa: E402
 F = np.float32
 
 
-LAST = {}   # of the last configuration: "zero_separated" = winners with hit = 0 and dist = +0 (a separated pair whose d2 underflowed)
+LAST = {}   # of the last configuration: "zero_separated" = winners with hit = 0 and dist = +0 (a separated pair whose d2 underflowed),
+            # "hits" / "misses" = winners with hit = 1 / hit = 0
+TILE_ROWS, TILE_COLS, BLOCKS_PER_CU = 256, 64, 8      # csrc/c2d_clearance.hip and the strip rule's target (csrc/c2d_ray_strips.hpp)
 
 
-def draw(wl, rng, idx):
-    """One configuration, drawn and judged by the reference, no GPU involved -> a dict of what run() needs"""
+def strips_of(cus, n_a, n_b):
+    row_tiles, col_tiles = -(-n_a // TILE_ROWS), -(-n_b // TILE_COLS)
+    return min(col_tiles, max(1, BLOCKS_PER_CU * cus // row_tiles))
+
+
+def draw(wl, rng, idx, cus=None):
+    """One configuration, drawn and judged by the reference, no GPU involved -> a dict of what run() needs.  cus: the device's
+    number of compute units; without it the draw between the strip extremes never fires (its numbers are drawn all the same)."""
     rows_a, rows_b = (int(rng.choice([4, 8, 16])) for _ in range(2))
     da, db = int(rng.integers(1, 120)), int(rng.integers(1, 40))                  # distinct polygons
     n_a = int(rng.choice([1, 63, 64, 65, 255, 256, 257, int(rng.integers(1, 600))]))
@@ -57,24 +67,44 @@ def draw(wl, rng, idx):
     if not self_set and rng.random() < 0.3:
         ib = np.sort(ib)                                                          # runs of one obstacle
     rb, cb = (int(rng.choice([0, 0, 7, 1 << 20])) for _ in range(2))
+    top = False
     if self_set:
         cb = rb
-    elif rng.random() < 0.2:
-        rb, cb = (1 << 32) - len(ia), (1 << 32) - len(ib)                         # up to exactly 2^32
+    else:
+        top = bool(rng.random() < 0.2)                                            # up to exactly 2^32
     flags = ref.SKIP_SELF if (self_set or rng.random() < 0.2) else 0
     place = [(int(rng.integers(0, 4)), int(rng.integers(0, 9))) for _ in range(2)]
+    # the last draws of the stream (every draw above is what it was before they were added): between one strip and one strip per
+    # tile.  1 < strips < col_tiles needs three column tiles (a B of fewer is redrawn at 129 .. 700) and 8 * cus / strips row tiles.
+    fire, pick, cut, n_b_between = rng.random() < 0.15, rng.random(), int(rng.integers(0, TILE_ROWS)), int(rng.integers(129, 701))
+    between = ""
+    if fire and cus and not self_set:
+        if len(ib) <= 2 * TILE_COLS:
+            ib = rng.integers(0, b[0].shape[1], n_b_between)
+        col_tiles = -(-len(ib) // TILE_COLS)
+        want_strips = 2 + int(pick * (col_tiles - 2))                             # 2 .. col_tiles - 1
+        ia = rng.integers(0, a[0].shape[1], TILE_ROWS * (BLOCKS_PER_CU * cus // want_strips) - cut)
+        strips = strips_of(cus, len(ia), len(ib))
+        between = f", {strips} strips over {col_tiles} column tiles" if 1 < strips < col_tiles else ""
+    if top:
+        rb, cb = (1 << 32) - len(ia), (1 << 32) - len(ib)
     what = (f"config {idx}: {len(ia)} x {len(ib)} of {a[0].shape[1]} x {b[0].shape[1]} distinct, rows {rows_a} / {rows_b}, extent {extent}, scale 2^{scale}, "
             f"d_k {'NULL' if no_k else 'given'}, {'one set under SKIP_SELF' if self_set else 'two sets'}, bases {rb} / {cb}, flags {flags}, "
-            f"planes (offset, stride - n) {place}, generator seeds {seeds}")
+            f"planes (offset, stride - n) {place}, generator seeds {seeds}{between}")
     want = ch.indexed_reference(a, ia, b, ib, row_base=rb, col_base=cb, flags=flags)
     LAST["zero_separated"] = int(((want["hit"] == 0) & (want["dist"] == 0) & (want["poly"] != ref.NO_POLY)).sum())
+    LAST["hits"], LAST["misses"] = int((want["hit"] == 1).sum()), int(((want["hit"] == 0) & (want["poly"] != ref.NO_POLY)).sum())
+    LAST["between"] = bool(between)
     return dict(a=a, b=b, ia=ia, ib=ib, rb=rb, cb=cb, flags=flags, place=place, no_k=no_k, self_set=self_set, what=what, want=want)
 
 
-def one(eng, wl, rng, idx):
-    """One configuration -> (ok, description); a vertex count out of range must be reported by the synchronise, once per call."""
-    c = draw(wl, rng, idx)
+def one(eng, wl, rng, idx, announce=None):
+    """One configuration -> (ok, description); a vertex count out of range must be reported by the synchronise, once per call.
+    `announce(text)` is called with the description before any GPU work."""
+    c = draw(wl, rng, idx, eng.info()["compute_units"])
     a, b, ia, ib, place, no_k, self_set, what, want = (c[k] for k in ("a", "b", "ia", "ib", "place", "no_k", "self_set", "what", "want"))
+    if announce is not None:
+        announce(what)
     sa, sb = ch.take(a, ia), ch.take(b, ib)
     ua = Uploaded(eng, sa, offset=place[0][0], stride=len(ia) + place[0][1], with_k=not no_k)
     ub = ua if self_set else Uploaded(eng, sb, offset=place[1][0], stride=len(ib) + place[1][1], with_k=not no_k)
