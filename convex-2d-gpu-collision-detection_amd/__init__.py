@@ -42,6 +42,8 @@ from .binding import (  # noqa: F401
     SWEEP_DT,
     SWEEP_START_OVERLAP,
     SWEEP_BAD_PAIR,
+    CAST_DT,
+    CAST_SKIP_SELF,
     make_polygon,
     library_path,
     load_library,

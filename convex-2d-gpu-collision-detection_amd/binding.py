@@ -53,6 +53,9 @@ CLEARANCE_SKIP_SELF, CLEARANCE_NONE = 1, 16
 # swept queries (include/c2d.h, "swept queries: time of impact for listed pairs in linear motion")
 SWEEP_DT = np.dtype([("toi", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("axis", "<u2"), ("hit", "u1"), ("flags", "u1")])   # c2d_sweep
 SWEEP_START_OVERLAP, SWEEP_BAD_PAIR = 1, 2
+# shape casts (include/c2d.h, "shape casts: the first touch of each moving polygon against a set")
+CAST_DT = np.dtype([("poly", "<u4"), ("toi", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("axis", "<u2"), ("hit", "u1"), ("flags", "u1"), ("reserved0", "<u4")])   # c2d_cast
+CAST_SKIP_SELF = 1
 
 
 class C2DError(RuntimeError):
@@ -201,6 +204,8 @@ _SIGNATURES = {
                                        C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_rect_pair_sweeps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "c2d_poly_set_casts": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                     C.c_int, C.c_void_p, C.c_void_p]),
     "c2d_poly_bins_create": (C.c_int, [C.c_void_p, C.POINTER(_PolyBin), C.c_size_t, C.POINTER(C.c_void_p)]),
     "c2d_poly_bins_from_padded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "c2d_poly_bins_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -887,6 +892,26 @@ class Engine:
         bdx, bdy = self._motion(b_motion, "b")
         self._check(self.lib.c2d_rect_pair_sweeps(self.h, a, n_a, b, n_b, adx, ady, bdx, bdy, _ptr_of(pairs), n_pairs, _ptr_of(n_pairs_dev), row_base,
                                                   col_base, _ptr_of(out), C.c_void_p(stream)), "c2d_rect_pair_sweeps")
+
+    # -- shape casts (include/c2d.h "shape casts: the first touch of each moving polygon against a set") -----------------
+    def poly_set_casts(self, a_set: _PolySet, b_set: _PolySet, a_motion=None, b_motion=None, row_base: int = 0, col_base: int = 0, flags: int = 0, out=None,
+                       stream: int = 0):
+        """c2d_poly_set_casts: out[i] (CAST_DT[n_a], 8-byte aligned) = the polygon of b_set that polygon i of a_set touches first while
+        both translate over the step t = 0 .. 1, as col_base + j, with that pair's sweep record; a_set, b_set from poly_set() (they
+        may describe the same memory); a_motion / b_motion as for poly_pair_sweeps: None or the pair (dx, dy) of device planes f32[n];
+        flags: 0 or CAST_SKIP_SELF (the pair with row_base + i == col_base + j is not considered)"""
+        if not isinstance(a_set, _PolySet) or not isinstance(b_set, _PolySet):
+            raise ValueError("need two poly_set() descriptions")
+        if out is None:
+            raise ValueError("need an output of CAST_DT[n_a]")
+        if isinstance(out, DeviceArray) and out.nbytes < CAST_DT.itemsize * a_set.n:
+            raise ValueError("the output holds fewer than n_a records")
+        if row_base < 0 or col_base < 0 or flags & ~CAST_SKIP_SELF:
+            raise ValueError("bases are not negative, and flags is 0 or CAST_SKIP_SELF")
+        adx, ady = self._motion(a_motion, "a")
+        bdx, bdy = self._motion(b_motion, "b")
+        self._check(self.lib.c2d_poly_set_casts(self.h, C.byref(a_set), C.byref(b_set), adx, ady, bdx, bdy, row_base, col_base, flags, _ptr_of(out),
+                                                C.c_void_p(stream)), "c2d_poly_set_casts")
 
     def _contacts_of_list(self, name: str, arrays: Sequence, list_call, contacts_call, check_async: bool = False, manifolds: bool = False):
         """The one shape of the *_contacts_host functions: a count-only list call sizes the buffers, then the list call and the

@@ -797,6 +797,60 @@ int c2d_rect_pair_sweeps(c2d_ctx* ctx, const float* const d_a[8], size_t n_a, co
                          size_t row_base, size_t col_base,
                          c2d_sweep* d_out, c2d_stream stream);
 
+/* ---- shape casts: the first touch of each moving polygon against a set -----------
+ * An addition to 0.6 (c2d_version() stays 6), found by symbol lookup like the calls above.
+ *
+ * c2d_poly_set_casts: for each polygon A_i of the set a — a footprint moving over one time step — WHICH polygon of the set b it
+ * touches first, WHEN, and with which normal.  An N x M reduction over the sweep contract above, as the clearance call is one over the
+ * distance contract: nothing of size n_a x n_b is written, and no row is left for the caller to reduce.  (The broad-phase lists hold
+ * only pairs whose boxes overlap at t = 0: they miss exactly the pairs a sweep is for.)
+ *   a, b       : the polygon sets, as for the clearance call: rows, stride, d_k == NULL, shards by pointer offset; a and b may be the
+ *                same memory.  Polygons only: rectangles go in as 4-gons with rows = 4.
+ *   d_a_dx, d_a_dy, d_b_dx, d_b_dy : the motion planes of the swept queries: f32[n] each, 4-byte aligned, LOCAL indices (a shard
+ *                passes them offset like its vertices).  A set whose two planes are both NULL stands still.  Exactly one NULL
+ *                plane of a set is refused (C2D_ERR_INVALID_ARG), before the other checks.
+ *   row_base   : the global index of A_0;  col_base: the global index of B_0: a record reports col_base + j.
+ *   flags      : 0 or C2D_CAST_SKIP_SELF (one set against itself: a == b, row_base == col_base, the same motion planes).
+ *   d_out      : c2d_cast[n_a], 8-byte aligned; entry i is the record of A_i.  Records at or beyond n_a are never touched.
+ *
+ * The contract, stated through the sweep contract.
+ *   per-pair records   for query i, S(i, j) is the c2d_sweep record that c2d_poly_pair_sweeps defines for the pair (A_i, B_j) with
+ *                      these motion planes.
+ *   considered         polygon j is considered when its vertex count is within 1..rows and it is not the self pair; with
+ *                      C2D_CAST_SKIP_SELF the self pair is the one with row_base + i == col_base + j, without the flag there is none.
+ *   the pick           among the considered j with S(i, j).hit == 1, the winner j* has the smallest key (bits of S(i, j).toi, col_base + j).
+ *                      A hit's toi is t_in: it starts at +0 and is replaced only by a larger value, so it is never NaN and never -0
+ *                      and at most 1, and the order of the bits is the order of the values; equal times fall to the smaller index.
+ *                      Ties are real: duplicated obstacles, a start overlap against a hit at +0 with no axis, symmetric scenes.
+ *   the record         a winner exists: poly = col_base + j*, and toi, nx, ny, axis, hit and flags are the same-named fields of
+ *                      S(i, j*), bit for bit (+0 and -0 compare equal in the three floats); reserved0 = 0.
+ *                      No considered polygon is hit (n_b == 0, only bad polygons, only the self pair, all misses): poly = 0xFFFFFFFF,
+ *                      toi = +inf, normal (0, 0), axis = 0xFFFF, hit = 0, flags = 0.
+ *                      A query with a vertex count outside 1..rows: poly = 0xFFFFFFFF, everything else 0, axis = 0xFFFF,
+ *                      flags = C2D_SWEEP_BAD_PAIR.
+ * A vertex count outside 1..rows in a or b is reported by the next c2d_stream_synchronize / c2d_ctx_check_async
+ * (C2D_ASYNC_ERR_POLY_K).  The implementation evaluates polygons in parallel and leaves the axes of a pair as soon as the pair can no
+ * longer win; its results equal the rule above.
+ *
+ * n_a == 0 is a no-op.  NULL arguments, `rows` out of range, misaligned planes or motion planes, a d_out that is not 8-byte aligned,
+ * stride < n, unknown flag bits, half a motion and row_base + n_a or col_base + n_b above 2^32 are refused (C2D_ERR_INVALID_ARG)
+ * before a device is touched.  The call is asynchronous on `stream` with no host synchronisation, and deterministic: two runs give
+ * the same bytes.  It uses no ctx scratch (the workspace guard is not involved) and is graph-capturable (a chain of kernel nodes). */
+#define C2D_CAST_SKIP_SELF 1   /* call flag: the pair with row_base + i == col_base + j is not considered */
+
+typedef struct c2d_cast {   /* 24 bytes, 8-byte aligned output */
+    uint32_t poly;          /*  0: col_base + j of the winner; 0xFFFFFFFF: none */
+    float    toi;           /*  4 */
+    float    nx, ny;        /*  8 */
+    uint16_t axis;          /* 16 */
+    uint8_t  hit, flags;    /* 18, 19: flags = the C2D_SWEEP_* bits of the winning pair */
+    uint32_t reserved0;     /* 20: written as 0 */
+} c2d_cast;
+
+int c2d_poly_set_casts(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b,
+                       const float* d_a_dx, const float* d_a_dy, const float* d_b_dx, const float* d_b_dy,
+                       size_t row_base, size_t col_base, int flags, c2d_cast* d_out, c2d_stream stream);
+
 /* ---- binned polygon batches ---------------------------------------------------
  * The padded layout above moves 16 vertex rows per polygon whatever the polygons are: with
  * K ~ U{3..16} that is 259 bytes per pair for 155 bytes of real vertices, and no kernel can
