@@ -206,6 +206,8 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_set_casts": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                      C.c_int, C.c_void_p, C.c_void_p]),
+    "c2d_poly_sweep_broad_pairs": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_bins_create": (C.c_int, [C.c_void_p, C.POINTER(_PolyBin), C.c_size_t, C.POINTER(C.c_void_p)]),
     "c2d_poly_bins_from_padded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "c2d_poly_bins_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -912,6 +914,62 @@ class Engine:
         bdx, bdy = self._motion(b_motion, "b")
         self._check(self.lib.c2d_poly_set_casts(self.h, C.byref(a_set), C.byref(b_set), adx, ady, bdx, bdy, row_base, col_base, flags, _ptr_of(out),
                                                 C.c_void_p(stream)), "c2d_poly_set_casts")
+
+    # -- swept broad phase (include/c2d.h "swept broad-phase pair search of two convex polygon sets") -----------------
+    def poly_sweep_broad_pairs(self, a: _PolySet, b: _PolySet, pairs, capacity: int, count, a_motion=None, b_motion=None, upper: bool = False,
+                               stream: int = 0):
+        """c2d_poly_sweep_broad_pairs: every pair (i, j) whose poly_pair_sweeps record has hit == 1 (row_base = col_base = 0), found
+        through the broad phase on swept boxes: the first `capacity` pairs in row-major order into pairs = u32[capacity][2]; count
+        (required) is incremented by the total; a, b from poly_set(); a_motion / b_motion as for poly_pair_sweeps: None or the pair
+        (dx, dy) of device planes f32[n] (the same set twice with the same planes: boxes and sort are made once)"""
+        if not isinstance(a, _PolySet) or not isinstance(b, _PolySet):
+            raise ValueError("need two poly_set() descriptions")
+        adx, ady = self._motion(a_motion, "a")
+        bdx, bdy = self._motion(b_motion, "b")
+        self._check(self.lib.c2d_poly_sweep_broad_pairs(self.h, C.byref(a), C.byref(b), adx, ady, bdx, bdy, CROSS_UPPER if upper else 0, _ptr_of(pairs),
+                                                        capacity, _ptr_of(count), C.c_void_p(stream)), "c2d_poly_sweep_broad_pairs")
+
+    @staticmethod
+    def _host_motion(motion, n: int, which: str):
+        if motion is None:
+            return None
+        if isinstance(motion, (str, bytes)) or not hasattr(motion, "__len__") or len(motion) != 2:
+            raise ValueError(f"{which}_motion is None or the two planes (dx, dy)")
+        dx, dy = np.ascontiguousarray(motion[0], np.float32), np.ascontiguousarray(motion[1], np.float32)
+        if dx.shape != (n,) or dy.shape != (n,):
+            raise ValueError(f"{which}_motion needs two planes f32[{n}]")
+        return dx, dy
+
+    def poly_sweep_broad_pairs_host(self, vx_a, vy_a, k_a, a_motion=None, vx_b=None, vy_b=None, k_b=None, b_motion=None, upper: bool = False) -> np.ndarray:
+        """Host convenience: vx, vy f32[rows][n], k u8[n] (or None) and a motion (None, or the two planes dx, dy f32[n]) per set
+        (vx_b None: the same set with the same motion, uploaded once) -> the pairs that touch during the step as u32 [total][2] in
+        row-major order.  A count-only call first, then the list sized exactly."""
+        vx_a, vy_a, k_a = self._host_poly_set(vx_a, vy_a, k_a)
+        same = vx_b is None
+        if same:
+            if vy_b is not None or k_b is not None or b_motion is not None:
+                raise ValueError("set B needs vx_b and vy_b (or none of vx_b, vy_b, k_b, b_motion: the same set)")
+        else:
+            if vy_b is None:
+                raise ValueError("set B needs vx_b and vy_b")
+            vx_b, vy_b, k_b = self._host_poly_set(vx_b, vy_b, k_b)
+        n_a = vx_a.shape[1]
+        n_b = n_a if same else vx_b.shape[1]
+        mot_a = self._host_motion(a_motion, n_a, "a")
+        mot_b = None if same else self._host_motion(b_motion, n_b, "b")
+        if n_a == 0 or n_b == 0:
+            return np.zeros((0, 2), np.uint32)
+        host = [vx_a, vy_a, k_a] + ([] if same else [vx_b, vy_b, k_b])
+        n_sets = len(host)
+        host += list(mot_a or ()) + list(mot_b or ())
+        arrays = self._to_device_all(host)
+        a = self.poly_set(*arrays[:3], n_a, vx_a.shape[0])
+        b = a if same else self.poly_set(*arrays[3:6], n_b, vx_b.shape[0])
+        d_mot_a = tuple(arrays[n_sets:n_sets + 2]) if mot_a else None
+        d_mot_b = d_mot_a if same else (tuple(arrays[-2:]) if mot_b else None)
+        return self._pairs_sized_exactly("poly_sweep_broad_pairs_host", arrays,
+                                         lambda pairs, cap, cnt: self.poly_sweep_broad_pairs(a, b, pairs, cap, cnt, d_mot_a, d_mot_b, upper=upper),
+                                         check_async=True)
 
     def _contacts_of_list(self, name: str, arrays: Sequence, list_call, contacts_call, check_async: bool = False, manifolds: bool = False):
         """The one shape of the *_contacts_host functions: a count-only list call sizes the buffers, then the list call and the

@@ -851,6 +851,57 @@ int c2d_poly_set_casts(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* 
                        const float* d_a_dx, const float* d_a_dy, const float* d_b_dx, const float* d_b_dy,
                        size_t row_base, size_t col_base, int flags, c2d_cast* d_out, c2d_stream stream);
 
+/* ---- swept broad-phase pair search of two convex polygon sets ---------------------
+ * An addition to 0.6 (c2d_version() stays 6), found by symbol lookup like the calls above.
+ *
+ * c2d_poly_sweep_broad_pairs: every pair of two polygon sets that touches during one step — the front end of the swept queries, as
+ * c2d_sat_poly_broad_pairs is the front end of the static ones (whose lists hold only pairs that overlap at t = 0).
+ *
+ * The contract, stated through the sweep contract.  S(i, j) is the c2d_sweep record that c2d_poly_pair_sweeps defines for the pair
+ * (A_i, B_j) with these motion planes and row_base = col_base = 0.  The call returns the list of all (i, j), in row-major order,
+ * with S(i, j).hit == 1 — for every input bit pattern: NaN, inf, huge and subnormal coordinates and motions, degenerate and
+ * clockwise polygons, repeated vertices, sets with different `rows`, any `stride`, d_k == NULL.  A polygon with a vertex count
+ * outside 1..rows is in no pair (its S is the BAD_PAIR record, hit = 0) and is not counted; the error is reported by the next
+ * c2d_stream_synchronize / c2d_ctx_check_async (C2D_ASYNC_ERR_POLY_K).  With C2D_CROSS_UPPER only the pairs with j > i are listed.
+ * Every pair of c2d_sat_poly_broad_pairs' list is in this one (a pair that overlaps at t = 0 is a hit with
+ * C2D_SWEEP_START_OVERLAP).
+ *
+ * The pairs are found through the broad phase of c2d_sat_poly_broad_pairs (the same grid, sort, scan, count and emit pipeline) on
+ * SWEPT conservative boxes: the hull of the polygon's box of that call, its slabs widened for the sweep rule's own roundings, at
+ * t = 0 and displaced by the polygon's motion.  DESIGN.md §5.19 proves that no pair is lost.  Polygons the argument does not cover
+ * ("wild") are tested against everything: what is wild for c2d_sat_poly_broad_pairs, a non-finite motion component, a |motion
+ * component| >= 2^60, a displaced |coordinate| >= 2^60.  A box far wider than the scene's typical one is wild too, so ONE fast
+ * outlier costs n_b exact tests (n_a + n_b when it is in both sets); a scene in which many polygons move many polygon sizes per
+ * step belongs to c2d_poly_set_casts or to shorter steps.
+ *   a, b       : as c2d_sat_poly_broad_pairs.  Polygons only: rectangles go in as 4-gons with rows = 4.  a and b may describe the
+ *                same memory (same pointers, n, stride, rows, d_k AND the same motion planes): the boxes and the sort are then
+ *                made once, and with C2D_CROSS_UPPER that is the continuous self-collision test of one set.  One set against
+ *                itself with different motion planes is two sets.
+ *   d_a_dx, d_a_dy, d_b_dx, d_b_dy : the motion planes of the swept queries: f32[n] each, 4-byte aligned.  A set whose two planes
+ *                are both NULL stands still.  Exactly one NULL plane of a set is refused (C2D_ERR_INVALID_ARG), before the other
+ *                checks.
+ *   flags      : 0, or C2D_CROSS_UPPER: only the pairs with j > i.
+ *   d_pairs, capacity, d_count : u32[capacity][2] of (i, j) in row-major order, only the first `capacity` pairs written;
+ *                d_count (required) is incremented by the TOTAL; d_pairs may be NULL when capacity is 0 (a count-only call,
+ *                which skips the emit pass).
+ * The chain.  The list and its device-side count feed the narrow phase with no host synchronisation, on one stream:
+ *     c2d_poly_sweep_broad_pairs(ctx, a, b, adx, ady, bdx, bdy, flags, d_pairs, capacity, d_count, s);     (d_count zeroed before)
+ *     c2d_poly_pair_sweeps(ctx, a, b, adx, ady, bdx, bdy, d_pairs, capacity, d_count, 0, 0, d_out, s);     (d_n_pairs = d_count)
+ * The second call processes min(capacity, *d_count) entries; every record it writes has hit == 1.
+ *
+ * n_a == 0 or n_b == 0 is a no-op.  A call with n_a or n_b above 2^32 is refused; an unknown flag, a NULL argument, `rows`
+ * outside 1..C2D_POLY_KMAX, half a motion or a misaligned motion plane is refused (C2D_ERR_INVALID_ARG) before a device is
+ * touched.  Asynchronous on `stream`, with no host synchronisation; the output is deterministic.  It works through the ctx scratch
+ * under the workspace guard, which it grows on first use and keeps; the size depends only on (n_a, n_b, same memory): 36 bytes
+ * per polygon of A plus 48.5 per polygon of B (68.5 per polygon when B is A: the boxes are shared) and a 4 KiB header.  Graph
+ * capture follows c2d_sat_poly_broad_pairs: allowed after an eager call of the same or a larger size, refused
+ * (C2D_ERR_INVALID_ARG) before anything is enqueued if the scratch would have to grow. */
+int c2d_poly_sweep_broad_pairs(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b,
+                               const float* d_a_dx, const float* d_a_dy, const float* d_b_dx, const float* d_b_dy,
+                               int flags,                               /* 0 or C2D_CROSS_UPPER (j > i only) */
+                               uint32_t* d_pairs, size_t capacity,      /* u32[capacity][2] */
+                               unsigned long long* d_count, c2d_stream stream);
+
 /* ---- binned polygon batches ---------------------------------------------------
  * The padded layout above moves 16 vertex rows per polygon whatever the polygons are: with
  * K ~ U{3..16} that is 259 bytes per pair for 155 bytes of real vertices, and no kernel can

@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""Differential fuzz of c2d_poly_sweep_broad_pairs against its reference (tests/sweep_broad_ref.py: every pair through
+tests/sweep_ref.py's poly_sweeps, pinned by tests/test_sweep_broad_ref_cpu.py): the random sets of poly_broad_fuzz.py (sizes on both
+sides of the wave, block and tile edges, row layouts, vertex-count ranges with points and segments, densities, clockwise polygons,
+outliers, huge coordinates, NaN / inf in real slots, junk in the padded slots), now and then a vertex count out of range, strides
+and pointer offsets, d_k == NULL, two sets, one set against itself with its own motion (the same memory) and with another motion
+(two sets), C2D_CROSS_UPPER, and the motions of sweep_fuzz.py per set (standing still, all zero, the scale of the scene, a
+hundredth of it, far larger, mixed scales with exact zeros and non-finite components).  draw() makes a configuration and its
+reference list without a GPU; one() runs it; the judge is sweep_broad_harness.compare.  Prints its seed; a mismatch names its
+configuration.
+usage: sweep_broad_fuzz.py [configs] [seed]"""
+import importlib.util
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+TESTS = os.path.dirname(HERE)
+for p in (TESTS, os.path.dirname(TESTS)):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+import sweep_broad_harness as sh  # noqa: E402
+import sweep_broad_ref as ref  # noqa: E402
+import sweep_ref  # noqa: E402
+
+
+def _tool(name):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+poly_broad_fuzz = _tool("poly_broad_fuzz")    # its random sets
+sweep_fuzz = _tool("sweep_fuzz")              # its motions
+
+LAST = {}   # of the last configuration: "hits" = listed pairs, "moving_hits" = those that do not overlap at t = 0, "misses" = the other pairs
+SIZES = [1, 2, 63, 64, 65, 257]
+SMALL = 300
+
+
+def _scene(s):
+    finite = np.abs(s[0][0][np.isfinite(s[0][0])])
+    return float(np.median(finite)) + 1.0 if finite.size else 1.0
+
+
+def draw(rng, idx, small=False):
+    """One configuration and the reference's list of it, no GPU involved -> a dict of what one() needs (small: no set above SMALL)"""
+    sizes = SIZES + [int(rng.integers(1, 1200)), int(rng.integers(1200, 2600))]
+    if small:
+        sizes = [min(n, SMALL) for n in sizes]
+    n_a, n_b = int(rng.choice(sizes)), int(rng.choice(sizes))
+    mode = str(rng.choice(["two", "two", "self", "self_other_motion"]))
+    upper = bool(rng.random() < 0.5)
+    a, da = poly_broad_fuzz.random_set(rng, n_a, int(rng.integers(1, 17)))
+    b, db = poly_broad_fuzz.random_set(rng, n_b, int(rng.integers(1, 17))) if mode == "two" else (a, da)
+    with np.errstate(all="ignore"):
+        ma, name_a = sweep_fuzz.random_motion(rng, n_a, _scene(a))
+        mb, name_b = (ma, name_a) if mode == "self" else sweep_fuzz.random_motion(rng, b[0].shape[1], _scene(b))
+    # The reference walks every axis of every pair it cannot drop on one axis: where most pairs are hits (motions far larger than
+    # the scene, the densest scenes) the sets stay small.
+    crowded = name_a in ("huge", "mixed") or name_b in ("huge", "mixed") or "density 16.0" in da + db
+    if crowded and max(n_a, n_b) > SMALL:
+        cut = lambda s, m, n: ((s[0][:, :n], s[1][:, :n], s[2][:n]), None if m is None else (m[0][:n], m[1][:n]))   # noqa: E731
+        a, ma = cut(a, ma, min(n_a, SMALL))
+        (b, mb) = (a, ma if mode == "self" else cut(b, mb, min(n_a, SMALL))[1]) if mode != "two" else cut(b, mb, min(n_b, SMALL))
+    n_a, n_b = a[0].shape[1], b[0].shape[1]
+    no_k = bool(rng.random() < 0.15)
+    if no_k:                                                   # d_k == NULL: every polygon has `rows` vertices, and they are all read
+        a = (np.nan_to_num(a[0], nan=1.0, posinf=2.0, neginf=-2.0), np.nan_to_num(a[1], nan=1.0, posinf=2.0, neginf=-2.0), None)
+    elif rng.random() < 0.3:                                   # a few vertex counts out of range
+        k = a[2].copy()
+        k[rng.integers(0, n_a, 1 + n_a // 50)] = rng.choice(np.array([0, a[0].shape[0] + 1, 255], np.uint8), 1 + n_a // 50)
+        a = (a[0], a[1], k)
+    if mode != "two":
+        b = a
+    what = f"sweep broad config {idx}: " + (f"{n_a} x {n_b}, A {da}, B {db}" if mode == "two" else f"{mode} n {n_a} {da}")
+    what += f", motion A {name_a}, B {name_b}, upper {upper}" + (", no count plane" if no_k else "")
+    with np.errstate(all="ignore"):
+        want = ref.pairs(a, b, ma, mb, upper=upper)
+        ii, jj = want[:, 0].astype(np.int64), want[:, 1].astype(np.int64)
+        start = int(((sweep_ref.poly_sweeps(a, b, ii, jj, ma, mb)["flags"] & sweep_ref.START_OVERLAP) != 0).sum())
+    both = ref.present(a)[:, None] & ref.present(b)[None, :]
+    considered = int(np.triu(both, 1).sum()) if upper else int(both.sum())
+    LAST.update(hits=len(want), moving_hits=len(want) - start, misses=considered - len(want))
+    place = [(int(rng.integers(0, 4)), int(rng.integers(0, 9))) for _ in range(2)]
+    return dict(a=a, b=b, ma=ma, mb=mb, mode=mode, upper=upper, no_k=no_k, what=what, want=want, place=place,
+                bad=bool((~ref.present(a)).any() or (~ref.present(b)).any()))
+
+
+def one(eng, rng, idx, announce=None):
+    """One configuration -> (ok, description); a vertex count out of range must be reported by the synchronise.
+    `announce(text)` is called with the description before any GPU work."""
+    c = draw(rng, idx)
+    what = c["what"]
+    if announce is not None:
+        announce(what)
+    a, b, place = c["a"], c["b"], c["place"]
+    A = sh.MovingSet(eng, a, c["ma"], offset=place[0][0], stride=a[0].shape[1] + place[0][1])
+    if c["mode"] == "two":
+        B = sh.MovingSet(eng, b, c["mb"], offset=place[1][0], stride=b[0].shape[1] + place[1][1])
+    elif c["mode"] == "self":
+        B = A
+    else:                                                      # the same vertex memory, other motion planes
+        B = A.with_motion(c["mb"])
+    try:
+        got, total = sh.run(eng, A, B, c["upper"], absent=c["bad"])     # (a vertex count out of range must be reported, by each call)
+    finally:
+        A.free()
+        if B is not A:
+            B.free()
+    why = sh.compare(got, total, c["want"])
+    if why is not None:
+        return False, what + ": " + why
+    return True, what + f" [{LAST['hits']} pairs, {LAST['moving_hits']} of them apart at t = 0, {LAST['misses']} misses]"
+
+
+def main():
+    from __graft_entry__ import load_package
+
+    pkg = load_package()
+    configs = int(sys.argv[1]) if len(sys.argv) > 1 else 16
+    seed = int(sys.argv[2]) if len(sys.argv) > 2 else int.from_bytes(os.urandom(4), "little")
+    print(f"sweep_broad_fuzz: seed {seed}, {configs} configurations", flush=True)
+    eng = pkg.Engine(0)
+    bad = 0
+    for idx in range(configs):
+        ok, what = one(eng, np.random.default_rng([seed, idx]), idx)
+        print(("ok   " if ok else "FAIL ") + what, flush=True)
+        bad += not ok
+    eng.close()
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
