@@ -208,6 +208,8 @@ _SIGNATURES = {
                                      C.c_int, C.c_void_p, C.c_void_p]),
     "c2d_poly_sweep_broad_pairs": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "c2d_poly_near_broad_pairs": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_float, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                            C.c_void_p]),
     "c2d_poly_bins_create": (C.c_int, [C.c_void_p, C.POINTER(_PolyBin), C.c_size_t, C.POINTER(C.c_void_p)]),
     "c2d_poly_bins_from_padded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "c2d_poly_bins_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -969,6 +971,40 @@ class Engine:
         d_mot_b = d_mot_a if same else (tuple(arrays[-2:]) if mot_b else None)
         return self._pairs_sized_exactly("poly_sweep_broad_pairs_host", arrays,
                                          lambda pairs, cap, cnt: self.poly_sweep_broad_pairs(a, b, pairs, cap, cnt, d_mot_a, d_mot_b, upper=upper),
+                                         check_async=True)
+
+    # -- proximity pair search (include/c2d.h "proximity pair search of two convex polygon sets: every pair within a distance") ---------
+    def poly_near_broad_pairs(self, a: _PolySet, b: _PolySet, max_dist: float, pairs, capacity: int, count, upper: bool = False, stream: int = 0):
+        """c2d_poly_near_broad_pairs: every pair (i, j) whose poly_pair_distances record has hit == 1 or dist <= max_dist (row_base =
+        col_base = 0), found through the broad phase on boxes that hold the margin: the first `capacity` pairs in row-major order into
+        pairs = u32[capacity][2]; count (required) is incremented by the total; a, b from poly_set() (the same set twice: boxes and
+        sort are made once); max_dist: finite, 0 <= max_dist < 2^60"""
+        if not isinstance(a, _PolySet) or not isinstance(b, _PolySet):
+            raise ValueError("need two poly_set() descriptions")
+        self._check(self.lib.c2d_poly_near_broad_pairs(self.h, C.byref(a), C.byref(b), C.c_float(max_dist), CROSS_UPPER if upper else 0, _ptr_of(pairs),
+                                                       capacity, _ptr_of(count), C.c_void_p(stream)), "c2d_poly_near_broad_pairs")
+
+    def poly_near_broad_pairs_host(self, vx_a, vy_a, k_a, max_dist: float, vx_b=None, vy_b=None, k_b=None, upper: bool = False) -> np.ndarray:
+        """Host convenience: vx, vy f32[rows][n] and k u8[n] (or None) per set (vx_b None: the same set, uploaded once) -> the pairs
+        that are hit or within max_dist as u32 [total][2] in row-major order.  A count-only call first, then the list sized exactly."""
+        vx_a, vy_a, k_a = self._host_poly_set(vx_a, vy_a, k_a)
+        same = vx_b is None
+        if same:
+            if vy_b is not None or k_b is not None:
+                raise ValueError("set B needs vx_b and vy_b (or none of vx_b, vy_b, k_b: the same set)")
+        else:
+            if vy_b is None:
+                raise ValueError("set B needs vx_b and vy_b")
+            vx_b, vy_b, k_b = self._host_poly_set(vx_b, vy_b, k_b)
+        n_a = vx_a.shape[1]
+        n_b = n_a if same else vx_b.shape[1]
+        if n_a == 0 or n_b == 0:
+            return np.zeros((0, 2), np.uint32)
+        arrays = self._to_device_all([vx_a, vy_a, k_a] + ([] if same else [vx_b, vy_b, k_b]))
+        a = self.poly_set(*arrays[:3], n_a, vx_a.shape[0])
+        b = a if same else self.poly_set(*arrays[3:], n_b, vx_b.shape[0])
+        return self._pairs_sized_exactly("poly_near_broad_pairs_host", arrays,
+                                         lambda pairs, cap, cnt: self.poly_near_broad_pairs(a, b, max_dist, pairs, cap, cnt, upper=upper),
                                          check_async=True)
 
     def _contacts_of_list(self, name: str, arrays: Sequence, list_call, contacts_call, check_async: bool = False, manifolds: bool = False):

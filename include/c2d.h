@@ -902,6 +902,59 @@ int c2d_poly_sweep_broad_pairs(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_po
                                uint32_t* d_pairs, size_t capacity,      /* u32[capacity][2] */
                                unsigned long long* d_count, c2d_stream stream);
 
+/* ---- proximity pair search of two convex polygon sets: every pair within a distance -
+ * An addition to 0.6 (c2d_version() stays 6), found by symbol lookup like the calls above.
+ *
+ * c2d_poly_near_broad_pairs: every pair of two polygon sets that is hit or no farther apart than max_dist — the front end of the
+ * distance queries (a safety margin, speculative contacts, the neighbours of a potential field), as c2d_sat_poly_broad_pairs is the
+ * front end of the static ones (whose lists hold only pairs that overlap: c2d_poly_pair_distances answers those with dist = 0).
+ *
+ * The contract, stated through the distance contract.  D(i, j) is the c2d_distance record that c2d_poly_pair_distances defines for
+ * the pair (A_i, B_j) with row_base = col_base = 0.  The call returns the list of all (i, j), in row-major order, with
+ *     D(i, j).hit == 1 || D(i, j).dist <= max_dist
+ * — a binary32 compare on the record's own dist, for every input bit pattern: NaN, inf, huge and subnormal coordinates, degenerate
+ * and clockwise polygons, repeated vertices, sets with different `rows`, any `stride`, d_k == NULL.  A pair without a usable
+ * candidate (C2D_DISTANCE_NO_CANDIDATE, dist = +inf) is listed only when it is hit.  A polygon with a vertex count outside 1..rows is
+ * in no pair (its D is the BAD_PAIR record) and is not counted; the error is reported by the next c2d_stream_synchronize /
+ * c2d_ctx_check_async (C2D_ASYNC_ERR_POLY_K).  With C2D_CROSS_UPPER only the pairs with j > i are listed.  Three consequences:
+ *   superset     for any admissible max_dist the list contains the list of c2d_sat_poly_broad_pairs on the same sets (its pairs are
+ *                the hit ones);
+ *   monotone     the list of a larger max_dist contains the list of a smaller one;
+ *   the chain    the list and its device-side count feed c2d_poly_pair_distances with no host synchronisation, on one stream:
+ *                    c2d_poly_near_broad_pairs(ctx, a, b, max_dist, flags, d_pairs, capacity, d_count, s);     (d_count zeroed before)
+ *                    c2d_poly_pair_distances(ctx, a, b, d_pairs, capacity, d_count, 0, 0, d_out, s);           (d_n_pairs = d_count)
+ *                The second call processes min(capacity, *d_count) entries; every record it writes has hit == 1 || dist <= max_dist.
+ *                The contact, manifold and sweep calls take the list the same way.
+ *
+ * The pairs are found through the broad phase of c2d_sat_poly_broad_pairs (the same grid, sort, scan, count and emit pipeline) on
+ * conservative boxes that hold the margin: the hull of the polygon's box of that call and of the box of its live vertices widened
+ * on every side by half of max_dist and by what the distance rule's roundings need.  DESIGN.md §5.20 proves that no pair is lost.
+ * Polygons the argument does not cover ("wild") are tested against everything: what is wild for c2d_sat_poly_broad_pairs (1- and
+ * 2-gons among them) and a polygon whose largest |coordinate| is below 2^-100.  A box far wider than the scene's typical one is wild
+ * too.  The cost grows with the candidates: a max_dist of many polygon sizes makes every polygon a neighbour of many.
+ *   a, b       : as c2d_sat_poly_broad_pairs.  Polygons only: rectangles go in as 4-gons with rows = 4.  a and b may describe the
+ *                same memory (same pointers, n, stride, rows and d_k): the boxes and the sort are then made once, and with
+ *                C2D_CROSS_UPPER that is the neighbour search of one set.
+ *   max_dist   : finite, 0 <= max_dist < 2^60; -0 counts as 0.  Anything else, NaN included, is refused (C2D_ERR_INVALID_ARG) before
+ *                a device is touched and before the sets are looked at.  max_dist = 0 lists the hit pairs and the separated pairs
+ *                whose d2 underflowed to 0.
+ *   flags      : 0, or C2D_CROSS_UPPER: only the pairs with j > i.
+ *   d_pairs, capacity, d_count : u32[capacity][2] of (i, j) in row-major order, only the first `capacity` pairs written;
+ *                d_count (required) is incremented by the TOTAL; d_pairs may be NULL when capacity is 0 (a count-only call,
+ *                which skips the emit pass).
+ *
+ * n_a == 0 or n_b == 0 is a no-op.  A call with n_a or n_b above 2^32 is refused; an unknown flag, a NULL argument or `rows`
+ * outside 1..C2D_POLY_KMAX is refused (C2D_ERR_INVALID_ARG) before a device is touched, in the order of c2d_sat_poly_broad_pairs.
+ * Asynchronous on `stream`, with no host synchronisation; the output is deterministic.  It works through the ctx scratch under the
+ * workspace guard, which it grows on first use and keeps; the size is that of c2d_sat_poly_broad_pairs and depends only on
+ * (n_a, n_b, same memory).  Graph capture follows c2d_sat_poly_broad_pairs: allowed after an eager call of the same or a larger
+ * size, refused (C2D_ERR_INVALID_ARG) before anything is enqueued if the scratch would have to grow. */
+int c2d_poly_near_broad_pairs(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b,
+                              float max_dist,                          /* finite, 0 <= max_dist < 2^60 */
+                              int flags,                               /* 0 or C2D_CROSS_UPPER (j > i only) */
+                              uint32_t* d_pairs, size_t capacity,      /* u32[capacity][2] */
+                              unsigned long long* d_count, c2d_stream stream);
+
 /* ---- binned polygon batches ---------------------------------------------------
  * The padded layout above moves 16 vertex rows per polygon whatever the polygons are: with
  * K ~ U{3..16} that is 259 bytes per pair for 155 bytes of real vertices, and no kernel can
