@@ -210,6 +210,9 @@ _SIGNATURES = {
                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_near_broad_pairs": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_float, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                             C.c_void_p]),
+    "c2d_poly_set_clearances_grid": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_float, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p,
+                                               C.c_void_p]),
+    "c2d_poly_set_clearances_grid_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "c2d_poly_bins_create": (C.c_int, [C.c_void_p, C.POINTER(_PolyBin), C.c_size_t, C.POINTER(C.c_void_p)]),
     "c2d_poly_bins_from_padded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "c2d_poly_bins_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -864,6 +867,28 @@ class Engine:
             raise ValueError("bases are not negative, and flags is 0 or CLEARANCE_SKIP_SELF")
         self._check(self.lib.c2d_poly_set_clearances(self.h, C.byref(a_set), C.byref(b_set), row_base, col_base, flags, _ptr_of(d_out), C.c_void_p(stream)),
                     "c2d_poly_set_clearances")
+
+    def poly_set_clearances_grid(self, a_set: _PolySet, b_set: _PolySet, max_dist: float, d_out, row_base: int = 0, col_base: int = 0, flags: int = 0,
+                                 stream: int = 0):
+        """c2d_poly_set_clearances_grid: poly_set_clearances among the polygons of b_set that are hit or no farther than max_dist (finite,
+        0 <= max_dist < 2^60), found through the grid of the pair searches; a query with nothing within max_dist gets the
+        CLEARANCE_NONE record.  d_out: CLEARANCE_DT[n_a], 16-byte aligned; flags: 0 or CLEARANCE_SKIP_SELF"""
+        if not isinstance(a_set, _PolySet) or not isinstance(b_set, _PolySet):
+            raise ValueError("need two poly_set() descriptions")
+        if d_out is None:
+            raise ValueError("need an output of CLEARANCE_DT[n_a]")
+        if isinstance(d_out, DeviceArray) and d_out.nbytes < CLEARANCE_DT.itemsize * a_set.n:
+            raise ValueError("the output holds fewer than n_a records")
+        if row_base < 0 or col_base < 0 or flags & ~CLEARANCE_SKIP_SELF:
+            raise ValueError("bases are not negative, and flags is 0 or CLEARANCE_SKIP_SELF")
+        self._check(self.lib.c2d_poly_set_clearances_grid(self.h, C.byref(a_set), C.byref(b_set), C.c_float(max_dist), row_base, col_base, flags,
+                                                          _ptr_of(d_out), C.c_void_p(stream)), "c2d_poly_set_clearances_grid")
+
+    def poly_set_clearances_grid_stats(self) -> dict:
+        """c2d_poly_set_clearances_grid_stats: the counters of the last poly_set_clearances_grid call with obstacles (synchronise first)"""
+        out = (C.c_ulonglong * 5)()
+        self._check(self.lib.c2d_poly_set_clearances_grid_stats(self.h, out), "c2d_poly_set_clearances_grid_stats")
+        return {"listed": int(out[0]), "walked": int(out[1]), "candidates": int(out[2]), "tested": int(out[3]), "walks": int(out[4])}
 
     # -- swept queries (include/c2d.h "swept queries: time of impact for listed pairs in linear motion") -----------------
     @staticmethod

@@ -31,6 +31,7 @@
 //                                 the routines the distance kernel uses, the whole record in two 16-byte stores
 #include "c2d_distance_rule.hpp"
 #include "c2d_clearance_bound.hpp"
+#include "c2d_clearance_parts.hpp"   // kClrNoKey and the two launches c2d_clearance_grid.hip shares
 #include "c2d_pair_list.hpp"   // PolySetDev, PolyObj, poly_load, poly_collide, the shared argument checks
 #include "c2d_ray_strips.hpp"
 #include "c2d_wave.hpp"
@@ -45,7 +46,6 @@ static_assert(sizeof(c2d_clearance) == 32 && offsetof(c2d_clearance, poly) == 0 
 constexpr int kClrBlock = 256;   // queries per block: one per lane
 constexpr int kClrCols = 64;     // polygons of B per staged tile
 constexpr int kClrK = C2D_POLY_KMAX;
-constexpr unsigned long long kClrNoKey = ~0ull;
 
 __global__ __launch_bounds__(kClrBlock) void clearance_init_kernel(size_t n_a, c2d_clearance* __restrict__ out)
 {
@@ -368,6 +368,20 @@ __global__ __launch_bounds__(kClrBlock) void clearance_finalise_kernel(PolySetDe
     }
 }
 
+int clearance_launch_init(c2d_ctx* ctx, hipStream_t s, size_t n_a, c2d_clearance* d_out)
+{
+    hipLaunchKernelGGL(clearance_init_kernel, dim3(grid_for(n_a, kClrBlock, 1 << 16)), dim3(kClrBlock), 0, s, n_a, d_out);
+    C2D_LAUNCH_CHECK(ctx);
+    return C2D_OK;
+}
+
+int clearance_launch_finalise(c2d_ctx* ctx, hipStream_t s, const PolySetDev& A, const PolySetDev& B, size_t col_base, c2d_clearance* d_out)
+{
+    hipLaunchKernelGGL(clearance_finalise_kernel, dim3(grid_for(A.n, kClrBlock, 1 << 16)), dim3(kClrBlock), 0, s, A, B, col_base, d_out, ctx->d_async_err);
+    C2D_LAUNCH_CHECK(ctx);
+    return C2D_OK;
+}
+
 }  // namespace c2d
 
 using namespace c2d;
@@ -395,8 +409,7 @@ int c2d_poly_set_clearances(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_
 
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(clearance_init_kernel, dim3(grid_for(A.n, kClrBlock, 1 << 16)), dim3(kClrBlock), 0, s, A.n, d_out);
-    C2D_LAUNCH_CHECK(ctx);
+    if (int rc = clearance_launch_init(ctx, s, A.n, d_out)) return rc;
     if (B.n != 0) {
         const size_t row_tiles = (A.n + kClrBlock - 1) / kClrBlock, col_tiles = (B.n + kClrCols - 1) / kClrCols;
         const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 1;
@@ -406,9 +419,7 @@ int c2d_poly_set_clearances(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_
                            (flags & C2D_CLEARANCE_SKIP_SELF) ? 1 : 0, col_tiles, (uint32_t)strips, d_out, ctx->d_async_err);
         C2D_LAUNCH_CHECK(ctx);
     }
-    hipLaunchKernelGGL(clearance_finalise_kernel, dim3(grid_for(A.n, kClrBlock, 1 << 16)), dim3(kClrBlock), 0, s, A, B, col_base, d_out, ctx->d_async_err);
-    C2D_LAUNCH_CHECK(ctx);
-    return C2D_OK;
+    return clearance_launch_finalise(ctx, s, A, B, col_base, d_out);
 }
 
 }  // extern "C"

@@ -955,6 +955,65 @@ int c2d_poly_near_broad_pairs(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_pol
                               uint32_t* d_pairs, size_t capacity,      /* u32[capacity][2] */
                               unsigned long long* d_count, c2d_stream stream);
 
+/* ---- clearance queries through a grid: the nearest polygon within a distance ---------
+ * An addition to 0.6 (c2d_version() stays 6), found by symbol lookup like the calls above.
+ *
+ * c2d_poly_set_clearances_grid: c2d_poly_set_clearances restricted to the obstacles that are hit or no farther than max_dist, found
+ * through the grid of the pair searches instead of a visit to all n_a x n_b pairs: "which obstacle is nearest to each of my 10^5
+ * footprints, among 10^6 obstacles, if any is within the margin".  It is the reduction of the list of c2d_poly_near_broad_pairs, made
+ * on the device with nothing of that list written.
+ *
+ * The contract is the contract of c2d_poly_set_clearances (above), word for word, with one more clause in "considered":
+ *   considered         polygon j is considered for query i when its vertex count is within 1..rows, it is not the self pair (with
+ *                      C2D_CLEARANCE_SKIP_SELF the pair with row_base + i == col_base + j, without the flag there is none) and
+ *                          D(i, j).hit == 1 || D(i, j).dist <= max_dist
+ *                      — the binary32 compare of c2d_poly_near_broad_pairs on the record's own dist, for every input bit pattern.
+ *                      A C2D_DISTANCE_NO_CANDIDATE pair (dist = +inf) is considered only when it is hit.
+ *   the pick           unchanged: the considered polygon with the smallest key (bits of D(i, j).dist, col_base + j); equal distances
+ *                      fall to the smaller index.
+ *   the record         unchanged: the winner's fields copied from D(i, j*) bit for bit; the C2D_CLEARANCE_NONE record for a query with
+ *                      nothing considered, which now includes "nothing within max_dist"; the C2D_DISTANCE_BAD_PAIR record for a query
+ *                      with a vertex count outside 1..rows.
+ * Three consequences:
+ *   the cut      a record whose poly is not 0xFFFFFFFF has hit == 1 || dist <= max_dist;
+ *   NONE         a query gets the NONE record exactly when row i of the list of c2d_poly_near_broad_pairs is empty for the same
+ *                sets and max_dist (with the self pair removed under C2D_CLEARANCE_SKIP_SELF);
+ *   all winners  where every query of a call has a winner, the output is byte for byte that of c2d_poly_set_clearances.
+ * Raising max_dist only turns NONE records into winners: it never changes a winner.
+ *
+ *   a, b       : as c2d_poly_near_broad_pairs: rows, stride, d_k == NULL; a and b may describe the same memory (same pointers, n,
+ *                stride, rows and d_k): the boxes and the sort are then made once.
+ *   max_dist   : finite, 0 <= max_dist < 2^60; -0 counts as 0.  Anything else, NaN included, is refused (C2D_ERR_INVALID_ARG) before a
+ *                device is touched and before the sets are looked at.
+ *   row_base, col_base, flags, d_out : as c2d_poly_set_clearances (flags: 0 or C2D_CLEARANCE_SKIP_SELF; d_out: c2d_clearance[n_a],
+ *                16-byte aligned).  Records at or beyond n_a are never touched.
+ *
+ * n_a == 0 is a no-op; n_b == 0 writes the NONE record (BAD_PAIR for a bad query) for every query.  NULL arguments, `rows` out of
+ * range, misaligned planes or a misaligned d_out, stride < n, unknown flag bits, n_a or n_b above 2^32 and row_base + n_a or
+ * col_base + n_b above 2^32 are refused (C2D_ERR_INVALID_ARG) before a device is touched.  A vertex count outside 1..rows in a or b is
+ * reported by the next c2d_stream_synchronize / c2d_ctx_check_async (C2D_ASYNC_ERR_POLY_K).
+ *
+ * The candidates are found as c2d_poly_near_broad_pairs finds them (the same margin boxes, grid and sort; polygons it calls wild are
+ * compared with everything), and a certified bound skips the candidate walk of a pair that cannot be considered or cannot win; the
+ * results equal the rule above.  The cost grows with the candidates: a max_dist of many polygon sizes makes every
+ * polygon a neighbour of many.  Asynchronous on `stream`, with no host synchronisation; deterministic: two runs give the same bytes.
+ * It works through the ctx scratch under the workspace guard, which it grows on first use and keeps; the size is that of
+ * c2d_sat_poly_broad_pairs and depends only on (n_a, n_b, same memory).  Graph capture follows c2d_sat_poly_broad_pairs: allowed after
+ * an eager call of the same or a larger size, refused (C2D_ERR_INVALID_ARG) before anything is enqueued if the scratch would have to
+ * grow. */
+int c2d_poly_set_clearances_grid(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b,
+                                 float max_dist,            /* finite, 0 <= max_dist < 2^60; -0 counts as 0 */
+                                 size_t row_base, size_t col_base, int flags,   /* 0 or C2D_CLEARANCE_SKIP_SELF */
+                                 c2d_clearance* d_out, c2d_stream stream);
+
+/* The counters of the last c2d_poly_set_clearances_grid call with n_b > 0 on this ctx, for measurements (csrc/tools/clearance_grid_bench.py):
+ * synchronise the call's stream first; the read blocks.  Refused when no such call has run, or when another call has used the ctx
+ * scratch since.  out[0] = queries answered by the list kernel (wild ones, and walks past the candidate cap), out[1] = sorted grid
+ * entries the walks looked at, out[2] = candidates (entries whose box meets the query's, wild polygons, and what the list kernel's
+ * box filter let through), out[3] = of those, the pairs that ran the pairwise test, out[4] = of those, the pairs that ran the
+ * candidate walk of the distance rule (the certified bound skipped the others). */
+int c2d_poly_set_clearances_grid_stats(c2d_ctx* ctx, unsigned long long out[5]);
+
 /* ---- binned polygon batches ---------------------------------------------------
  * The padded layout above moves 16 vertex rows per polygon whatever the polygons are: with
  * K ~ U{3..16} that is 259 bytes per pair for 155 bytes of real vertices, and no kernel can
