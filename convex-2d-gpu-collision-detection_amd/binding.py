@@ -213,6 +213,9 @@ _SIGNATURES = {
     "c2d_poly_set_clearances_grid": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_float, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p,
                                                C.c_void_p]),
     "c2d_poly_set_clearances_grid_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
+    "c2d_poly_set_casts_grid": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "c2d_poly_set_casts_grid_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "c2d_poly_bins_create": (C.c_int, [C.c_void_p, C.POINTER(_PolyBin), C.c_size_t, C.POINTER(C.c_void_p)]),
     "c2d_poly_bins_from_padded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "c2d_poly_bins_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -941,6 +944,30 @@ class Engine:
         bdx, bdy = self._motion(b_motion, "b")
         self._check(self.lib.c2d_poly_set_casts(self.h, C.byref(a_set), C.byref(b_set), adx, ady, bdx, bdy, row_base, col_base, flags, _ptr_of(out),
                                                 C.c_void_p(stream)), "c2d_poly_set_casts")
+
+    def poly_set_casts_grid(self, a_set: _PolySet, b_set: _PolySet, a_motion=None, b_motion=None, row_base: int = 0, col_base: int = 0, flags: int = 0,
+                            out=None, stream: int = 0):
+        """c2d_poly_set_casts_grid: poly_set_casts found through the grid of the pair searches on swept boxes; the arguments and the
+        output are those of poly_set_casts, byte for byte (out: CAST_DT[n_a], 8-byte aligned; flags: 0 or CAST_SKIP_SELF).  The same
+        set twice with the same motion planes: boxes and sort are made once"""
+        if not isinstance(a_set, _PolySet) or not isinstance(b_set, _PolySet):
+            raise ValueError("need two poly_set() descriptions")
+        if out is None:
+            raise ValueError("need an output of CAST_DT[n_a]")
+        if isinstance(out, DeviceArray) and out.nbytes < CAST_DT.itemsize * a_set.n:
+            raise ValueError("the output holds fewer than n_a records")
+        if row_base < 0 or col_base < 0 or flags & ~CAST_SKIP_SELF:
+            raise ValueError("bases are not negative, and flags is 0 or CAST_SKIP_SELF")
+        adx, ady = self._motion(a_motion, "a")
+        bdx, bdy = self._motion(b_motion, "b")
+        self._check(self.lib.c2d_poly_set_casts_grid(self.h, C.byref(a_set), C.byref(b_set), adx, ady, bdx, bdy, row_base, col_base, flags, _ptr_of(out),
+                                                     C.c_void_p(stream)), "c2d_poly_set_casts_grid")
+
+    def poly_set_casts_grid_stats(self) -> dict:
+        """c2d_poly_set_casts_grid_stats: the counters of the last poly_set_casts_grid call with obstacles (synchronise first)"""
+        out = (C.c_ulonglong * 5)()
+        self._check(self.lib.c2d_poly_set_casts_grid_stats(self.h, out), "c2d_poly_set_casts_grid_stats")
+        return {"listed": int(out[0]), "walked": int(out[1]), "candidates": int(out[2]), "walks": int(out[3])}
 
     # -- swept broad phase (include/c2d.h "swept broad-phase pair search of two convex polygon sets") -----------------
     def poly_sweep_broad_pairs(self, a: _PolySet, b: _PolySet, pairs, capacity: int, count, a_motion=None, b_motion=None, upper: bool = False,

@@ -36,6 +36,7 @@
 //                            in the low word; the strips of a row tile meet in an atomic minimum on those bytes
 //   3. cast_finalise_kernel  one lane per query: A_i and the winner in registers with their motions, the exact test and the sweep
 //                            record by the routines the sweep kernel uses, the whole record in three 8-byte stores
+#include "c2d_cast_parts.hpp"   // kCastNoKey and the two launches c2d_cast_grid.hip shares
 #include "c2d_sweep_rule.hpp"   // SweepPick; through it c2d_pair_list.hpp: PolySetDev, PolyObj, poly_load, poly_collide, poly_axes, the checks
 #include "c2d_ray_strips.hpp"
 #include "c2d_wave.hpp"
@@ -50,7 +51,6 @@ static_assert(sizeof(c2d_cast) == 24 && offsetof(c2d_cast, poly) == 0 && offseto
 constexpr int kCastBlock = 256;   // queries per block: one per lane
 constexpr int kCastCols = 64;     // polygons of B per staged tile
 constexpr int kCastK = C2D_POLY_KMAX;
-constexpr unsigned long long kCastNoKey = ~0ull;
 
 __global__ __launch_bounds__(kCastBlock) void cast_init_kernel(size_t n_a, c2d_cast* __restrict__ out)
 {
@@ -338,6 +338,22 @@ __global__ __launch_bounds__(kCastBlock) void cast_finalise_kernel(PolySetDev A,
     }
 }
 
+int cast_launch_init(c2d_ctx* ctx, hipStream_t s, size_t n_a, c2d_cast* d_out)
+{
+    hipLaunchKernelGGL(cast_init_kernel, dim3(grid_for(n_a, kCastBlock, 1 << 16)), dim3(kCastBlock), 0, s, n_a, d_out);
+    C2D_LAUNCH_CHECK(ctx);
+    return C2D_OK;
+}
+
+int cast_launch_finalise(c2d_ctx* ctx, hipStream_t s, const PolySetDev& A, const PolySetDev& B, const float* d_a_dx, const float* d_a_dy,
+                         const float* d_b_dx, const float* d_b_dy, size_t col_base, c2d_cast* d_out)
+{
+    hipLaunchKernelGGL(cast_finalise_kernel, dim3(grid_for(A.n, kCastBlock, 1 << 16)), dim3(kCastBlock), 0, s, A, B, d_a_dx, d_a_dy, d_b_dx, d_b_dy,
+                       col_base, d_out, ctx->d_async_err);
+    C2D_LAUNCH_CHECK(ctx);
+    return C2D_OK;
+}
+
 }  // namespace c2d
 
 using namespace c2d;
@@ -365,8 +381,7 @@ int c2d_poly_set_casts(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* 
 
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(cast_init_kernel, dim3(grid_for(A.n, kCastBlock, 1 << 16)), dim3(kCastBlock), 0, s, A.n, d_out);
-    C2D_LAUNCH_CHECK(ctx);
+    if (int rc = cast_launch_init(ctx, s, A.n, d_out)) return rc;
     if (B.n != 0) {
         const size_t row_tiles = (A.n + kCastBlock - 1) / kCastBlock, col_tiles = (B.n + kCastCols - 1) / kCastCols;
         const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 1;
@@ -376,10 +391,7 @@ int c2d_poly_set_casts(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* 
                            col_base, (flags & C2D_CAST_SKIP_SELF) ? 1 : 0, col_tiles, (uint32_t)strips, d_out, ctx->d_async_err);
         C2D_LAUNCH_CHECK(ctx);
     }
-    hipLaunchKernelGGL(cast_finalise_kernel, dim3(grid_for(A.n, kCastBlock, 1 << 16)), dim3(kCastBlock), 0, s, A, B, d_a_dx, d_a_dy, d_b_dx, d_b_dy,
-                       col_base, d_out, ctx->d_async_err);
-    C2D_LAUNCH_CHECK(ctx);
-    return C2D_OK;
+    return cast_launch_finalise(ctx, s, A, B, d_a_dx, d_a_dy, d_b_dx, d_b_dy, col_base, d_out);
 }
 
 }  // extern "C"

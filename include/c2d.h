@@ -1014,6 +1014,54 @@ int c2d_poly_set_clearances_grid(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_
  * candidate walk of the distance rule (the certified bound skipped the others). */
 int c2d_poly_set_clearances_grid_stats(c2d_ctx* ctx, unsigned long long out[5]);
 
+/* ---- shape casts through a grid: each moving polygon's first touch via the grid -------
+ * An addition to 0.6 (c2d_version() stays 6), found by symbol lookup like the calls above.
+ *
+ * c2d_poly_set_casts_grid: c2d_poly_set_casts (above) found through the grid of the pair searches instead of a visit to all
+ * n_a x n_b pairs: "which obstacle does each of my 10^5 footprints touch first in this step, among 10^5 or 10^6 obstacles, when, and
+ * with which face".  It is the per-row reduction of the chain c2d_poly_sweep_broad_pairs + c2d_poly_pair_sweeps, made on the device
+ * with nothing of that list written.
+ *
+ * The contract is the contract of c2d_poly_set_casts, word for word: the per-pair records S(i, j), which polygons are considered, the
+ * pick by the key (bits of S(i, j).toi, col_base + j), the three records (a winner's, the miss record, the C2D_SWEEP_BAD_PAIR record of
+ * a query with a vertex count outside 1..rows), C2D_CAST_SKIP_SELF, and C2D_ASYNC_ERR_POLY_K reported by the next
+ * c2d_stream_synchronize / c2d_ctx_check_async for a vertex count outside 1..rows in a or b.  The consequence: on the same arguments
+ * the two calls write the same bytes, for every input bit pattern — NaN, inf, huge and subnormal coordinates and motions, degenerate
+ * and clockwise polygons, ties, any order of the obstacles.  No margin and no tolerance enters: two regular polygons whose swept boxes
+ * (those of c2d_poly_sweep_broad_pairs) are disjoint have a computed sweep record with hit == 0, and every other
+ * pair is evaluated by the sweep rule itself.
+ *
+ *   a, b, d_a_dx, d_a_dy, d_b_dx, d_b_dy, row_base, col_base, flags, d_out : as c2d_poly_set_casts (flags: 0 or C2D_CAST_SKIP_SELF;
+ *                d_out: c2d_cast[n_a], 8-byte aligned).  Records at or beyond n_a are never touched.  a and b may describe the same
+ *                memory (same pointers, n, stride, rows, d_k AND the same motion planes): the boxes and the sort are then made once.
+ *                One set against itself with different motion planes is two sets.
+ *
+ * The arguments are checked in the order of c2d_poly_set_casts, half a motion first.  n_a == 0 is a no-op; n_b == 0 writes the miss
+ * record (BAD_PAIR for a bad query) for every query without touching the ctx scratch.  NULL arguments, `rows` out of range, misaligned
+ * planes or motion planes, a d_out that is not 8-byte aligned, stride < n, unknown flag bits, half a motion, n_a or n_b above 2^32 and
+ * row_base + n_a or col_base + n_b above 2^32 are refused (C2D_ERR_INVALID_ARG) before a device is touched.
+ *
+ * The candidates are found as c2d_poly_sweep_broad_pairs finds them (the same swept boxes, grid and sort; polygons it calls wild —
+ * among them a mover whose swept box is far wider than the scene's typical one — are compared with everything).  The cost follows
+ * the candidates, not n_b: a scene in which many polygons move many polygon sizes per step has many candidates per query and belongs
+ * to c2d_poly_set_casts or to shorter steps.  Asynchronous on `stream`, with no host synchronisation;
+ * deterministic: two runs give the same bytes.  It works through the ctx scratch under the workspace guard, which it grows on first
+ * use and keeps; the size is that of c2d_poly_sweep_broad_pairs and depends only on (n_a, n_b, same memory).  Graph capture follows
+ * c2d_sat_poly_broad_pairs: allowed after an eager call of the same or a larger size, refused (C2D_ERR_INVALID_ARG) before anything
+ * is enqueued if the scratch would have to grow. */
+int c2d_poly_set_casts_grid(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b,
+                            const float* d_a_dx, const float* d_a_dy, const float* d_b_dx, const float* d_b_dy,
+                            size_t row_base, size_t col_base, int flags,   /* 0 or C2D_CAST_SKIP_SELF */
+                            c2d_cast* d_out, c2d_stream stream);
+
+/* The counters of the last c2d_poly_set_casts_grid call with n_b > 0 on this ctx, for measurements (csrc/tools/cast_grid_bench.py):
+ * synchronise the call's stream first; the read blocks.  Refused when no such call has run, or when another call has used the ctx
+ * scratch since (the last grid call on the ctx was not a grid cast).  out[0] = queries answered by the list kernel (wild ones, and
+ * walks past the candidate cap), out[1] = sorted grid entries the walks looked at, out[2] = candidates (entries whose box meets the
+ * query's, wild polygons, and what the list kernel's box filter let through), out[3] = of those, the pairs that ran the axis walk (the
+ * others could not beat a best at time 0 with a smaller index), out[4] = 0 (reserved). */
+int c2d_poly_set_casts_grid_stats(c2d_ctx* ctx, unsigned long long out[5]);
+
 /* ---- binned polygon batches ---------------------------------------------------
  * The padded layout above moves 16 vertex rows per polygon whatever the polygons are: with
  * K ~ U{3..16} that is 259 bytes per pair for 155 bytes of real vertices, and no kernel can
