@@ -116,6 +116,19 @@ C2D_DEV uint32_t cell_of(float v, double v0, double inv, uint32_t g)
     return (uint32_t)(t < top ? t : top);
 }
 
+// The cells whose sorted entries a query with the regular box `ba` has to look at: B_j overlaps ba only if cx(min x_j) is in
+// [cx(min x_i) - 1, cx(max x_i)], and the same in y.  The - 1: a sorted box is filed under the cell of its low corner and spans at
+// most two cells, and cell_of is monotone.  (gx, gy: the caller's copies of g->gx, g->gy.)
+struct BroadCells { uint32_t cx0, cx1, cy0, cy1; };
+C2D_DEV BroadCells broad_cell_range(const BroadGrid* g, uint32_t gx, uint32_t gy, float4 ba)
+{
+    uint32_t cx0 = cell_of(ba.x, g->x0, g->ix, gx), cx1 = cell_of(ba.z, g->x0, g->ix, gx);
+    uint32_t cy0 = cell_of(ba.y, g->y0, g->iy, gy), cy1 = cell_of(ba.w, g->y0, g->iy, gy);
+    cx0 = cx0 ? cx0 - 1u : 0u;
+    cy0 = cy0 ? cy0 - 1u : 0u;
+    return BroadCells{cx0, cx1, cy0, cy1};
+}
+
 // 1. boxes (NaN box = wild) and the extent histogram
 template <class S>
 __global__ __launch_bounds__(kBroadBlock) void broad_box_kernel(typename S::Set X, size_t n, float4* __restrict__ box, BroadGrid* __restrict__ g)
@@ -176,7 +189,7 @@ C2D_DEV bool broad_row_query(const BroadQuery<S>& q, size_t i, const float4& ba,
 {
     const BroadGrid* g = q.g;
     const uint32_t gx = g->gx, gy = g->gy;
-    // B_j overlaps ba only if cx(min x_j) is in [cx(min x_i) - 1, cx(max x_i)]: B_j spans at most two cells and cell_of is monotone
+    // broad_cell_range's cells, spelt out: through the helper this walk's registers come out renamed in every count and emit kernel
     uint32_t cx0 = cell_of(ba.x, g->x0, g->ix, gx), cx1 = cell_of(ba.z, g->x0, g->ix, gx);
     uint32_t cy0 = cell_of(ba.y, g->y0, g->iy, gy), cy1 = cell_of(ba.w, g->y0, g->iy, gy);
     cx0 = cx0 ? cx0 - 1u : 0u;
@@ -327,17 +340,14 @@ __global__ __launch_bounds__(kBroadBlock) void broad_long_emit_kernel(BroadQuery
         S::load(q.A, i, ra);
         bool done = false;
         if (!box_wild(ba) && cnt <= (unsigned long long)kMidHits) {
-            uint32_t cx0 = cell_of(ba.x, g->x0, g->ix, gx), cx1 = cell_of(ba.z, g->x0, g->ix, gx);
-            uint32_t cy0 = cell_of(ba.y, g->y0, g->iy, gy), cy1 = cell_of(ba.w, g->y0, g->iy, gy);
-            cx0 = cx0 ? cx0 - 1u : 0u;
-            cy0 = cy0 ? cy0 - 1u : 0u;
+            const BroadCells c = broad_cell_range(g, gx, gy, ba);
             uint32_t lo[3], hi[3], walked = 0;   // a regular row spans at most two cells: at most three cell rows
-            const uint32_t rows = cy1 - cy0 + 1u <= 3u ? cy1 - cy0 + 1u : 0u;
+            const uint32_t rows = c.cy1 - c.cy0 + 1u <= 3u ? c.cy1 - c.cy0 + 1u : 0u;
             if (rows == 0u) walked = kCandidateCap + 1u;
             for (uint32_t r = 0; r < rows; r++) {
-                const uint32_t cy = cy0 + r;
-                lo[r] = lower_bound_u32(q.keys, n_reg, cy * gx + cx0);
-                hi[r] = lower_bound_u32(q.keys, n_reg, cy * gx + cx1 + 1u);
+                const uint32_t cy = c.cy0 + r;
+                lo[r] = lower_bound_u32(q.keys, n_reg, cy * gx + c.cx0);
+                hi[r] = lower_bound_u32(q.keys, n_reg, cy * gx + c.cx1 + 1u);
                 walked += hi[r] - lo[r];
             }
             if (walked <= kCandidateCap) {
@@ -445,24 +455,35 @@ int broad_grid_and_sort(c2d_ctx* ctx, hipStream_t s, BroadScratch& W, size_t n_a
 // exclusive scan of the row counts into W.row_off; the total is added to d_count
 int broad_scan_and_total(c2d_ctx* ctx, hipStream_t s, const BroadScratch& W, size_t n_a, unsigned long long* d_count);
 
+// The first half of every call that searches through the grid, for box policy S: the scratch behind the workspace guard, the scene
+// header, the boxes of both sets (once when B is A) and B's sorted keys.  `use` is the caller's: it is armed here, once the scratch
+// is held and before the first enqueue, and stamps when the caller calls done() behind its own last kernel, or leaves its scope on
+// an error (a refusal of the scratch leaves it unarmed: nothing was queued).
+template <class S>
+int broad_prepare(c2d_ctx* ctx, hipStream_t s, const char* what, const typename S::Set& A, size_t n_a, const typename S::Set& B, size_t n_b, bool same,
+                  BroadScratch& W, WorkspaceUse& use)
+{
+    if (int rc = broad_scratch(ctx, s, what, n_a, n_b, same, W)) return rc;
+    use.arm();   // the kernels work through the scratch: stamp behind the last one
+    if (int rc = broad_begin(ctx, s, W)) return rc;
+    hipLaunchKernelGGL(broad_box_kernel<S>, dim3(grid_for(n_a, kBroadBlock, 8192)), dim3(kBroadBlock), 0, s, A, n_a, W.box_a, W.g);
+    C2D_LAUNCH_CHECK(ctx);
+    if (!same) {
+        hipLaunchKernelGGL(broad_box_kernel<S>, dim3(grid_for(n_b, kBroadBlock, 8192)), dim3(kBroadBlock), 0, s, B, n_b, W.box_b, W.g);
+        C2D_LAUNCH_CHECK(ctx);
+    }
+    return broad_grid_and_sort(ctx, s, W, n_a, n_b, same);
+}
+
 // One call of the pair search for shape S.  The caller has checked its arguments and holds the DeviceGuard.
 template <class S>
 int broad_run(c2d_ctx* ctx, hipStream_t s, const char* what, const typename S::Set& A, size_t n_a, const typename S::Set& B, size_t n_b, bool same,
               int flags, uint32_t* d_pairs, size_t capacity, unsigned long long* d_count)
 {
     BroadScratch W;
-    if (int rc = broad_scratch(ctx, s, what, n_a, n_b, same, W)) return rc;
-    WorkspaceUse use(ctx, s);   // the kernels work through the scratch: stamp behind the last one
-    use.arm();
-    if (int rc = broad_begin(ctx, s, W)) return rc;
-    const int grid_a = grid_for(n_a, kBroadBlock, 8192), grid_b = grid_for(n_b, kBroadBlock, 8192);
-    hipLaunchKernelGGL(broad_box_kernel<S>, dim3(grid_a), dim3(kBroadBlock), 0, s, A, n_a, W.box_a, W.g);
-    C2D_LAUNCH_CHECK(ctx);
-    if (!same) {
-        hipLaunchKernelGGL(broad_box_kernel<S>, dim3(grid_b), dim3(kBroadBlock), 0, s, B, n_b, W.box_b, W.g);
-        C2D_LAUNCH_CHECK(ctx);
-    }
-    if (int rc = broad_grid_and_sort(ctx, s, W, n_a, n_b, same)) return rc;
+    WorkspaceUse use(ctx, s);
+    if (int rc = broad_prepare<S>(ctx, s, what, A, n_a, B, n_b, same, W, use)) return rc;
+    const int grid_a = grid_for(n_a, kBroadBlock, 8192);
 
     BroadQuery<S> q{A, B, W.box_a, W.box_b, W.keys, W.idx, W.sbox, W.g, n_a, n_b, (flags & C2D_CROSS_UPPER) ? 1 : 0};
     hipLaunchKernelGGL(broad_count_kernel<S>, dim3(grid_a), dim3(kBroadBlock), 0, s, q, W.row_count, W.long_rows, W.g);

@@ -395,17 +395,12 @@ int c2d_poly_set_clearances(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_
     if (!ctx) return C2D_ERR_INVALID_ARG;
     if (!a || !b || !d_out) return cross_fail(ctx, what, "NULL argument");
     if (a->n == 0) return C2D_OK;
-    PolySetDev A, B{nullptr, nullptr, nullptr, 0, 0, (int)b->rows};
+    PolySetDev A, B;
     if (int rc = poly_set_check(ctx, what, "a", a, A)) return rc;
-    if (b->n == 0) {   // (no plane is read: only `rows` is looked at)
-        if (b->rows < 1 || b->rows > (uint32_t)C2D_POLY_KMAX) return cross_fail(ctx, what, "set b: rows must be 1..C2D_POLY_KMAX");
-    } else if (int rc = poly_set_check(ctx, what, "b", b, B)) {
-        return rc;
-    }
+    if (int rc = poly_set_check(ctx, what, "b", b, B, kEmptySetOk)) return rc;
     if (reinterpret_cast<uintptr_t>(d_out) & 15u) return cross_fail(ctx, what, "the output must be 16-byte aligned");
     if (flags & ~C2D_CLEARANCE_SKIP_SELF) return cross_fail(ctx, what, "unknown flag");
-    if (A.n > kIndexLimit || row_base > kIndexLimit - A.n || B.n > kIndexLimit || col_base > kIndexLimit - B.n)
-        return cross_fail(ctx, what, "row_base + n_a and col_base + n_b must not exceed 2^32");
+    if (int rc = cross_check_index_bases(ctx, what, A.n, B.n, row_base, col_base, "row_base + n_a and col_base + n_b must not exceed 2^32")) return rc;
 
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;

@@ -36,6 +36,13 @@ inline int cross_check_flags_bases(c2d_ctx* ctx, const char* what, size_t n_a, s
     return C2D_OK;
 }
 
+// the bases of a per-row reduction, whose keys carry base + index as u32; refused with the entry point's own `beyond`
+inline int cross_check_index_bases(c2d_ctx* ctx, const char* what, size_t n_a, size_t n_b, size_t row_base, size_t col_base, const char* beyond)
+{
+    if (n_a > kIndexLimit || row_base > kIndexLimit - n_a || n_b > kIndexLimit || col_base > kIndexLimit - n_b) return cross_fail(ctx, what, beyond);
+    return C2D_OK;
+}
+
 // the output of a mask form: rows of ld_words 64-bit words, n_b columns
 inline int cross_check_mask(c2d_ctx* ctx, const char* what, const unsigned long long* d_mask, size_t ld_words, size_t n_b)
 {

@@ -62,10 +62,8 @@ int c2d_sat_poly_broad_pairs(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly
     if (int rc = poly_set_check(ctx, what, "b", b, B.set)) return rc;
     if (int rc = broad_check_list(ctx, what, flags, d_pairs, capacity, d_count, A.set.n, B.set.n)) return rc;
     A.async_err = B.async_err = ctx->d_async_err;
-    const bool same = A.set.vx == B.set.vx && A.set.vy == B.set.vy && A.set.k == B.set.k && A.set.n == B.set.n && A.set.stride == B.set.stride &&
-                      A.set.rows == B.set.rows;
     DeviceGuard dg(ctx->device);
-    return broad_run<PolyShape>(ctx, (hipStream_t)stream, what, A, A.set.n, B, B.set.n, same, flags, d_pairs, capacity, d_count);
+    return broad_run<PolyShape>(ctx, (hipStream_t)stream, what, A, A.set.n, B, B.set.n, poly_sets_same(A.set, B.set), flags, d_pairs, capacity, d_count);
 }
 
 }  // extern "C"

@@ -25,8 +25,11 @@ struct PolySetDev {
     int rows;
 };
 
-// The checks of one c2d_poly_set (rows, planes, alignment, stride); C2D_OK or the status to return.
-inline int poly_set_check(c2d_ctx* ctx, const char* what, const char* which, const c2d_poly_set* set, PolySetDev& out)
+constexpr bool kEmptySetOk = true;
+
+// The checks of one c2d_poly_set (rows, planes, alignment, stride); C2D_OK or the status to return.  empty_ok, for set b of a query
+// that has a result against no polygons at all: of an empty set only `rows` is looked at, and no plane is read.
+inline int poly_set_check(c2d_ctx* ctx, const char* what, const char* which, const c2d_poly_set* set, PolySetDev& out, bool empty_ok = false)
 {
     char msg[192];
     auto fail = [&](const char* why) {
@@ -34,12 +37,23 @@ inline int poly_set_check(c2d_ctx* ctx, const char* what, const char* which, con
         return fail_arg(ctx, msg);
     };
     if (set->rows < 1 || set->rows > (uint32_t)C2D_POLY_KMAX) return fail("rows must be 1..C2D_POLY_KMAX");
+    if (empty_ok && set->n == 0) {
+        out = PolySetDev{nullptr, nullptr, nullptr, 0, 0, (int)set->rows};
+        return C2D_OK;
+    }
     if (!set->d_vx || !set->d_vy) return fail("NULL plane");
     if ((reinterpret_cast<uintptr_t>(set->d_vx) | reinterpret_cast<uintptr_t>(set->d_vy)) & 3u) return fail("planes must be 4-byte aligned");
     const size_t stride = set->stride ? set->stride : set->n;
     if (stride < set->n) return fail("stride < n");
     out = PolySetDev{set->d_vx, set->d_vy, set->d_k, set->n, stride, (int)set->rows};
     return C2D_OK;
+}
+
+
+// "B is A": the same planes read the same way, so one pass over them serves both sides
+inline bool poly_sets_same(const PolySetDev& A, const PolySetDev& B)
+{
+    return A.vx == B.vx && A.vy == B.vy && A.k == B.k && A.n == B.n && A.stride == B.stride && A.rows == B.rows;
 }
 
 // one polygon: k real vertices, slots >= k repeat vertex 0

@@ -177,12 +177,7 @@ int ray_launch_finalise(c2d_ctx* ctx, hipStream_t s, const RayPlanes& R, size_t 
 int ray_check_args(c2d_ctx* ctx, const char* what, const float* const d_rays[4], size_t n_rays, const c2d_poly_set* b, size_t col_base,
                    c2d_ray_hit* d_out, PolySetDev& B)
 {
-    B = PolySetDev{nullptr, nullptr, nullptr, 0, 0, (int)b->rows};
-    if (b->n == 0) {   // (no plane is read: only `rows` is looked at)
-        if (b->rows < 1 || b->rows > (uint32_t)C2D_POLY_KMAX) return cross_fail(ctx, what, "set b: rows must be 1..C2D_POLY_KMAX");
-    } else if (int rc = poly_set_check(ctx, what, "b", b, B)) {
-        return rc;
-    }
+    if (int rc = poly_set_check(ctx, what, "b", b, B, kEmptySetOk)) return rc;
     for (int p = 0; p < 4; p++) {
         if (!d_rays[p]) return cross_fail(ctx, what, "NULL ray plane");
         if (reinterpret_cast<uintptr_t>(d_rays[p]) & 3u) return cross_fail(ctx, what, "ray planes must be 4-byte aligned");

@@ -20,7 +20,11 @@
 //   7. finalise   ray_launch_finalise (c2d_ray.hip, unchanged): the record of the winning polygon.
 // There is no early termination by t: with a ray nearly collinear with an edge the rule's booleans are rounding noise, and a computed
 // t says nothing reliable about where a polygon is.
-#include "c2d_broad.hpp"
+//
+// The walk is this file's own: another enumeration (along the segment), a grid built from B alone, outliers.  Shared with the best-key
+// queries (c2d_grid_best.hpp, c2d_wave.hpp): the wave minimum of the list kernel, the reader of the _stats entry, and the place of the
+// counters, the scene header's dead extent histogram.  RayGridStats keeps its own layout: n_outliers is live state of the kernels.
+#include "c2d_grid_best.hpp"
 #include "c2d_ray_rule.hpp"
 #include "c2d_ray_walk.hpp"
 
@@ -271,11 +275,7 @@ __global__ __launch_bounds__(kBroadBlock) void ray_list_kernel(RayGridQuery q, c
                 best = key < best ? key : best;
             }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned long long o = __shfl_down(best, off, 64);
-            best = o < best ? o : best;
-        }
+        best = wave_min_u64(best);
         if (lane == 0 && best != kRayNoKey) reinterpret_cast<unsigned long long*>(out)[2 * r] = best;
     }
 }
@@ -335,20 +335,12 @@ int c2d_poly_ray_casts_grid(c2d_ctx* ctx, const float* const d_rays[4], size_t n
 /* The counters of the last c2d_poly_ray_casts_grid call with n_b > 0 on this ctx (a blocking read of the scene header). */
 int c2d_poly_ray_casts_grid_stats(c2d_ctx* ctx, unsigned long long out[4])
 {
-    const char* what = "c2d_poly_ray_casts_grid_stats";
-    if (!ctx) return C2D_ERR_INVALID_ARG;
-    if (!out) return cross_fail(ctx, what, "NULL argument");
-    if (!ctx->d_scratch || ctx->scratch_bytes < sizeof(BroadGrid)) return cross_fail(ctx, what, "no grid ray query has run on this ctx");
-    DeviceGuard dg(ctx->device);
-    static_assert(sizeof(BroadGrid) % 8 == 0, "copied as 64-bit words");
-    unsigned long long raw[sizeof(BroadGrid) / 8];
-    C2D_HIP(ctx, hipMemcpy(raw, ctx->d_scratch, sizeof(BroadGrid), hipMemcpyDeviceToHost));
-    BroadGrid h;
-    std::memcpy(&h, raw, sizeof h);
     RayGridStats st;
-    std::memcpy(&st, h.hist, sizeof st);
-    if (st.magic != kRayGridMagic) return cross_fail(ctx, what, "the ctx scratch does not hold a grid ray query (another call has used it since)");
-    out[0] = h.n_long;
+    unsigned int n_long;
+    if (int rc = grid_stats_read(ctx, "c2d_poly_ray_casts_grid_stats", out, "no grid ray query has run on this ctx",
+                                 "the ctx scratch does not hold a grid ray query (another call has used it since)", kRayGridMagic, st, n_long))
+        return rc;
+    out[0] = n_long;
     out[1] = st.visited;
     out[2] = st.candidates;
     out[3] = st.n_outliers;

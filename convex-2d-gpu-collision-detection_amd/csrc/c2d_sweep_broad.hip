@@ -27,8 +27,7 @@ int c2d_poly_sweep_broad_pairs(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_po
     B.set.dy = d_b_dy;
     A.async_err = B.async_err = ctx->d_async_err;
     // one set against itself only when it moves as itself: the boxes are swept boxes
-    const bool same = A.set.s.vx == B.set.s.vx && A.set.s.vy == B.set.s.vy && A.set.s.k == B.set.s.k && A.set.s.n == B.set.s.n &&
-                      A.set.s.stride == B.set.s.stride && A.set.s.rows == B.set.s.rows && d_a_dx == d_b_dx && d_a_dy == d_b_dy;
+    const bool same = poly_sets_same(A.set.s, B.set.s) && d_a_dx == d_b_dx && d_a_dy == d_b_dy;
     DeviceGuard dg(ctx->device);
     return broad_run<PolySweepBroadShape>(ctx, (hipStream_t)stream, what, A, A.set.s.n, B, B.set.s.n, same, flags, d_pairs, capacity, d_count);
 }

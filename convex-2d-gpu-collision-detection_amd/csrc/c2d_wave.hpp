@@ -1,5 +1,5 @@
 // c2d_wave.hpp — the small device helpers that several kernel files need and that must mean the same thing in each of them:
-// the 16-byte float vector, the wave-wide u32 maximum, the same-wave LDS hand-over and the register launder.
+// the 16-byte float vector, the wave-wide u32 maximum and u64 minimum, the same-wave LDS hand-over and the register launder.
 #pragma once
 
 #include "c2d_math.hpp"
@@ -17,6 +17,17 @@ C2D_DEV uint32_t wave_max_u32(uint32_t v)
         v = o > v ? o : v;
     }
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+// the smallest v of the wave's 64 lanes, in lane 0 (the other lanes hold partial minima): the best key of a listed query
+C2D_DEV unsigned long long wave_min_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_down(v, off, 64);
+        v = o < v ? o : v;
+    }
+    return v;
 }
 
 // LDS written by some lanes of a wave and read by others of the SAME wave (or read, then rewritten): a wave's LDS instructions

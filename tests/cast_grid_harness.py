@@ -8,7 +8,6 @@ import functools
 import itertools
 
 import numpy as np
-import pytest
 
 import cast_cases as cases
 import cast_harness as ch
@@ -35,25 +34,8 @@ def call(eng, a_set, b_set, n_a, a_motion=None, b_motion=None, capacity=None, ex
     every record at or beyond n_a must be untouched; under expect_error the next synchronise reports status -1, once.
     band: a buffer of h.banded(eng, cap, DT) to use again."""
     cap = max(n_a, 4) if capacity is None else capacity
-    d = h.banded(eng, cap, DT) if band is None else band
-    try:
-        if band is not None:
-            assert d.nbytes == (cap + 2 * h.GUARD) * DT.itemsize
-            eng.memset(d, h.BAND, d.nbytes)
-        method = eng.poly_set_casts_grid if grid else eng.poly_set_casts
-        method(a_set, b_set, a_motion, b_motion, out=d.ptr + DT.itemsize * h.GUARD, **kw)
-        if expect_error:
-            with pytest.raises(Exception) as e:
-                eng.synchronize()
-            assert getattr(e.value, "status", None) == -1
-            eng.synchronize()
-            eng.check_async()      # reported once, then clear
-        else:
-            eng.synchronize()
-        return h.unband(d, cap, n_a, DT)[:n_a].copy()
-    finally:
-        if band is None:
-            d.free()
+    method = eng.poly_set_casts_grid if grid else eng.poly_set_casts
+    return h.banded_call(eng, DT, n_a, lambda ptr: method(a_set, b_set, a_motion, b_motion, out=ptr, **kw), cap, expect_error, band)[:n_a].copy()
 
 
 def check(eng, a_set, b_set, n_a, want, what, nxm=True, **kw):

@@ -5,7 +5,6 @@ test_cast_cases_cpu.py and the GPU tests alike.  A plain module on numpy and the
 import functools
 
 import numpy as np
-import pytest
 
 import cast_cases as cases
 import cast_ref as ref
@@ -21,24 +20,7 @@ def call(eng, a_set, b_set, n_a, a_motion=None, b_motion=None, capacity=None, ex
     untouched; under expect_error the next synchronise reports status -1, once.  a_motion, b_motion: None or the two plane pointers.
     band: a buffer of h.banded(eng, cap, DT) to use again (it is filled with the band's byte first and stays the caller's)"""
     cap = max(n_a, 4) if capacity is None else capacity
-    d = h.banded(eng, cap, DT) if band is None else band
-    try:
-        if band is not None:
-            assert d.nbytes == (cap + 2 * h.GUARD) * DT.itemsize
-            eng.memset(d, h.BAND, d.nbytes)
-        eng.poly_set_casts(a_set, b_set, a_motion, b_motion, out=d.ptr + DT.itemsize * h.GUARD, **kw)
-        if expect_error:
-            with pytest.raises(Exception) as e:
-                eng.synchronize()
-            assert getattr(e.value, "status", None) == -1
-            eng.synchronize()
-            eng.check_async()      # reported once, then clear
-        else:
-            eng.synchronize()
-        return h.unband(d, cap, n_a, DT)[:n_a].copy()
-    finally:
-        if band is None:
-            d.free()
+    return h.banded_call(eng, DT, n_a, lambda ptr: eng.poly_set_casts(a_set, b_set, a_motion, b_motion, out=ptr, **kw), cap, expect_error, band)[:n_a].copy()
 
 
 def twice(eng, a_set, b_set, n_a, what, **kw):

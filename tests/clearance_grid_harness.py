@@ -6,7 +6,6 @@ import functools
 import itertools
 
 import numpy as np
-import pytest
 
 import clearance_grid_ref as ref
 import near_broad_harness as nh
@@ -29,27 +28,11 @@ def call(eng, a_set, b_set, n_a, max_dist, capacity=None, expect_error=False, ba
     the n_a records; the bands and every record at or beyond n_a must be untouched; under expect_error the next synchronise reports
     status -1, once.  band: a buffer of h.banded(eng, cap, DT) to use again."""
     cap = max(n_a, 4) if capacity is None else capacity
-    d = h.banded(eng, cap, DT) if band is None else band
-    try:
-        if band is not None:
-            assert d.nbytes == (cap + 2 * h.GUARD) * DT.itemsize
-            eng.memset(d, h.BAND, d.nbytes)
-        if grid:
-            eng.poly_set_clearances_grid(a_set, b_set, max_dist, d.ptr + DT.itemsize * h.GUARD, **kw)
-        else:
-            eng.poly_set_clearances(a_set, b_set, d.ptr + DT.itemsize * h.GUARD, **kw)
-        if expect_error:
-            with pytest.raises(Exception) as e:
-                eng.synchronize()
-            assert getattr(e.value, "status", None) == -1
-            eng.synchronize()
-            eng.check_async()      # reported once, then clear
-        else:
-            eng.synchronize()
-        return h.unband(d, cap, n_a, DT)[:n_a].copy()
-    finally:
-        if band is None:
-            d.free()
+    if grid:
+        launch = lambda ptr: eng.poly_set_clearances_grid(a_set, b_set, max_dist, ptr, **kw)   # noqa: E731
+    else:
+        launch = lambda ptr: eng.poly_set_clearances(a_set, b_set, ptr, **kw)   # noqa: E731
+    return h.banded_call(eng, DT, n_a, launch, cap, expect_error, band)[:n_a].copy()
 
 
 def assert_same(got, want, what):

@@ -5,7 +5,6 @@ test_clearance_cases_cpu.py and the GPU tests alike.  A plain module on numpy an
 import functools
 
 import numpy as np
-import pytest
 
 import clearance_cases as cases
 import clearance_ref as ref
@@ -19,24 +18,7 @@ def call(eng, a_set, b_set, n_a, capacity=None, expect_error=False, band=None, *
     must be untouched; under expect_error the next synchronise reports status -1, once.  band: a buffer of h.banded(eng, cap, DT) to
     use again (many small calls: it is filled with the band's byte first and stays the caller's)"""
     cap = max(n_a, 4) if capacity is None else capacity
-    d = h.banded(eng, cap, DT) if band is None else band
-    try:
-        if band is not None:
-            assert d.nbytes == (cap + 2 * h.GUARD) * DT.itemsize
-            eng.memset(d, h.BAND, d.nbytes)
-        eng.poly_set_clearances(a_set, b_set, d.ptr + DT.itemsize * h.GUARD, **kw)
-        if expect_error:
-            with pytest.raises(Exception) as e:
-                eng.synchronize()
-            assert getattr(e.value, "status", None) == -1
-            eng.synchronize()
-            eng.check_async()      # reported once, then clear
-        else:
-            eng.synchronize()
-        return h.unband(d, cap, n_a, DT)[:n_a].copy()
-    finally:
-        if band is None:
-            d.free()
+    return h.banded_call(eng, DT, n_a, lambda ptr: eng.poly_set_clearances(a_set, b_set, ptr, **kw), cap, expect_error, band)[:n_a].copy()
 
 
 def twice(eng, a_set, b_set, n_a, what, **kw):

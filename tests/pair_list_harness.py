@@ -149,6 +149,37 @@ def unband(d, cap, bound, dt):
     return out[GUARD: GUARD + cap]
 
 
+def synchronize(eng, expect_error=False):
+    """the synchronise behind the call(s) under test; under expect_error it reports status -1, once"""
+    if expect_error:
+        with pytest.raises(Exception) as e:
+            eng.synchronize()
+        assert getattr(e.value, "status", None) == -1
+        eng.synchronize()
+        eng.check_async()      # reported once, then clear
+    else:
+        eng.synchronize()
+
+
+def banded_call(eng, dt, n, launch, capacity=None, expect_error=False, band=None):
+    """launch(ptr) queues a call that writes n records of dt at ptr, the start of `capacity` records (default n) between two guard
+    bands -> dt[capacity]: the bands and every record at or beyond n must be untouched (unband); under expect_error the next
+    synchronise reports status -1, once.  band: a buffer of banded(eng, capacity, dt) to use again (many small calls: it is filled
+    with the band's byte first and stays the caller's)."""
+    cap = n if capacity is None else capacity
+    d = banded(eng, cap, dt) if band is None else band
+    try:
+        if band is not None:
+            assert d.nbytes == (cap + 2 * GUARD) * dt.itemsize
+            eng.memset(d, BAND, d.nbytes)
+        launch(d.ptr + dt.itemsize * GUARD)
+        synchronize(eng, expect_error)
+        return unband(d, cap, n, dt)
+    finally:
+        if band is None:
+            d.free()
+
+
 def run(eng, queue, pairs, dts, capacity=None, n_dev=None, expect_error=False):
     """queue(d_pairs, capacity, out_ptrs, d_n) queues the call(s) under test; out_ptrs[q] is where output q (dts[q][capacity]) begins,
     between two guard bands.  -> [dts[q][capacity]]: the bands must be intact and every record at or beyond min(capacity, n_dev)
@@ -161,14 +192,7 @@ def run(eng, queue, pairs, dts, capacity=None, n_dev=None, expect_error=False):
     d_n = None if n_dev is None else eng.to_device(np.array([n_dev], np.uint64))
     try:
         queue(d_pairs, cap, [d.ptr + dt.itemsize * GUARD for d, dt in zip(d_outs, dts)], d_n)
-        if expect_error:
-            with pytest.raises(Exception) as e:
-                eng.synchronize()
-            assert getattr(e.value, "status", None) == -1
-            eng.synchronize()
-            eng.check_async()      # reported once, then clear
-        else:
-            eng.synchronize()
+        synchronize(eng, expect_error)
         bound = cap if n_dev is None else min(cap, n_dev)
         return [unband(d, cap, bound, dt) for d, dt in zip(d_outs, dts)]
     finally:

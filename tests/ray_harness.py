@@ -28,23 +28,7 @@ class RaysOnDevice:
 def cast(eng, rays, n_rays, b_set, col_base=0, capacity=None, expect_error=False):
     """c2d_poly_ray_casts on the first n_rays rays of a RaysOnDevice into a banded output of `capacity` records -> RAY_HIT_DT[capacity];
     the bands and every record at or beyond n_rays must be untouched; under expect_error the synchronise reports status -1, once"""
-    import pytest
-
-    cap = n_rays if capacity is None else capacity
-    d = h.banded(eng, cap, DT)
-    try:
-        eng.poly_ray_casts(rays.ptrs, n_rays, b_set, d.ptr + DT.itemsize * h.GUARD, col_base=col_base)
-        if expect_error:
-            with pytest.raises(Exception) as e:
-                eng.synchronize()
-            assert getattr(e.value, "status", None) == -1
-            eng.synchronize()
-            eng.check_async()      # reported once, then clear
-        else:
-            eng.synchronize()
-        return h.unband(d, cap, n_rays, DT)
-    finally:
-        d.free()
+    return h.banded_call(eng, DT, n_rays, lambda ptr: eng.poly_ray_casts(rays.ptrs, n_rays, b_set, ptr, col_base=col_base), capacity, expect_error)
 
 
 def assert_same(got, want, what):

@@ -1,6 +1,7 @@
 """CPU test of tests/pair_list_harness.py itself: run(), banded() and unband() carry the guard-band coverage of all four list-driven
-queries, so a silent mistake there would remove it everywhere at once.  The stand-in engine's device arrays are numpy buffers, the
-stand-in query a Python function that writes records through the pointers run() hands it."""
+queries, and banded_call() that of the N x M reductions, their grid forms and the ray queries, so a silent mistake there would remove
+it everywhere at once.  The stand-in engine's device arrays are numpy buffers, the stand-in query a Python function that writes
+records through the pointers it is handed."""
 import ctypes as C
 import os
 import sys
@@ -132,6 +133,53 @@ def test_expect_error_wants_one_report():
             h.run(HostEngine(reports=reports), writer(dts), pairs, dts, expect_error=True)
     with pytest.raises(Status):                                                  # and without expect_error a report is an error
         h.run(HostEngine(reports=1), writer(dts), pairs, dts)
+
+
+def test_banded_call_asserts_what_the_per_query_calls_asserted():
+    """banded_call carries the guard bands of the N x M reductions and the ray queries (the call / cast wrappers of clearance_harness,
+    cast_harness, clearance_grid_harness, cast_grid_harness and ray_harness): a stand-in kernel that writes (a) exactly n records
+    passes, (b) one byte into the lower band, (c) one record beyond n raise."""
+    dt, n, cap = h.DISTANCES.dts[0], 5, 8
+
+    def kernel(records, stray=None):
+        def launch(ptr):
+            for p in range(records):
+                bytes_at(ptr + p * dt.itemsize, dt.itemsize)[:] = record(p, 0, dt.itemsize)
+            if stray is not None:
+                bytes_at(ptr + stray, 1)[:] = 0
+        return launch
+
+    eng = HostEngine()
+    got = h.banded_call(eng, dt, n, kernel(n), capacity=cap)                     # (a)
+    raw = got.view(np.uint8).reshape(cap, dt.itemsize)
+    assert got.dtype == dt and got.shape == (cap,) and (raw[n:] == h.BAND).all()
+    assert all((raw[p] == record(p, 0, dt.itemsize)).all() for p in range(n))
+    assert len(eng.live) == 1 and eng.live[0].freed
+    assert h.banded_call(HostEngine(), dt, n, kernel(n)).shape == (n,)           # capacity defaults to n
+    with pytest.raises(AssertionError, match="written outside the output"):      # (b)
+        h.banded_call(HostEngine(), dt, n, kernel(n, stray=-1), capacity=cap)
+    with pytest.raises(AssertionError, match="written at or beyond"):            # (c)
+        h.banded_call(HostEngine(), dt, n, kernel(n + 1), capacity=cap)
+    with pytest.raises(AssertionError, match="written outside the output"):      # (c) with no room behind n: the upper band
+        h.banded_call(HostEngine(), dt, n, kernel(n + 1))
+
+    # a band of the caller's: refilled before the call, checked for its size, and left to the caller
+    eng = HostEngine()
+    band = h.banded(eng, cap, dt)
+    band.a.view(np.uint8)[:] = 0
+    assert (h.banded_call(eng, dt, n, kernel(n), capacity=cap, band=band).view(np.uint8).reshape(cap, -1)[n:] == h.BAND).all()
+    assert not getattr(band, "freed", False)
+    with pytest.raises(AssertionError):
+        h.banded_call(eng, dt, n, kernel(n), capacity=cap + 1, band=band)
+
+    # expect_error: status -1, once, then clear
+    assert len(h.banded_call(HostEngine(reports=1), dt, n, kernel(n), expect_error=True)) == n
+    with pytest.raises(pytest.fail.Exception, match="DID NOT RAISE"):
+        h.banded_call(HostEngine(reports=0), dt, n, kernel(n), expect_error=True)
+    with pytest.raises(Status):
+        h.banded_call(HostEngine(reports=2), dt, n, kernel(n), expect_error=True)
+    with pytest.raises(Status):
+        h.banded_call(HostEngine(reports=1), dt, n, kernel(n))
 
 
 def test_the_manifolds_entry_compares_its_contacts_with_the_contacts_call():
