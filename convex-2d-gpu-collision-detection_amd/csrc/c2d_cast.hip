@@ -8,9 +8,8 @@
 // (bits of S(i, j).toi, col_base + j); a hit's toi is t_in, never NaN, never -0 and at most 1, so the order of its bits is the order
 // of its values, and equal times fall to the smaller index.
 //
-// Mapping: queries over lanes, polygons of B wave-uniform (the mapping of c2d_clearance.hip).  A block of 256 lanes owns 256 queries
-// — per lane the padded vertices, the count, the motion and the centre of the vertex box — and a strip of consecutive column tiles of
-// B (c2d_ray_strips.hpp).  Per tile it stages 64 polygons in LDS: per live edge {x0, y0, ex, ey} (the vertex and the edge vector),
+// The frame is c2d_set_best.hpp's (the mapping, the strips, the three launches).  A lane keeps of its query the padded vertices, the
+// count, the motion and the centre of the vertex box; a tile stages per live edge {x0, y0, ex, ey} (the vertex and the edge vector),
 // {mn, mx, nan0, off} (the polygon's OWN interval on that edge's normal, whether its first projection there is NaN, and the offset of
 // the facing heuristic) and {ux, uy} (the outward unit normal: a heuristic that only chooses WHICH axis is walked first), and per
 // polygon the count and the motion.  Every staged value the walk uses is made by the contract's own unfused operations.
@@ -21,7 +20,7 @@
 //      correctly rounded divisions.  All four are order-independent as VALUES — an OR, an OR, a maximum and a minimum under
 //      compare-and-select, a NaN bound failing its compare — so the axes are visited in another order than the contract's: first
 //      B_j's edge whose outward normal sees the query's box centre farthest out, then behind a wave-uniform branch B_j's edges
-//      (intervals of A from registers, B_j's own staged), then A's (A turned by one slot per trip, as in c2d_clearance.hip).
+//      (intervals of A from registers, B_j's own staged), then A's (A turned by one slot per trip).
 //   3. THE EXACT ABANDON.  t_in only grows and t_out only shrinks while axes are added, and sep and never only rise.  Once an axis
 //      has set sep, the pair cannot win when `never`, when t_in > t_out, or when t_in >= the lane's best toi: the lane's best came
 //      from a smaller j of the same strip, so an equal time loses too.  Such a lane is done with the pair, and the wave leaves the
@@ -30,15 +29,11 @@
 //   4. hit0, or a hit with t_in below the best, updates the lane's best.  Only the values hit and toi are carried: no axis, sign or
 //      normal.
 //
-// Three launches on the stream, no scratch, nothing read back:
-//   1. cast_init_kernel      every record's first eight bytes (poly, toi) = all ones: "nothing yet" (no hit has that key: toi <= 1)
-//   2. cast_main_kernel      per query and strip the smallest (toi, j) as a 64-bit key, toi's bits in the high word and col_base + j
-//                            in the low word; the strips of a row tile meet in an atomic minimum on those bytes
-//   3. cast_finalise_kernel  one lane per query: A_i and the winner in registers with their motions, the exact test and the sweep
-//                            record by the routines the sweep kernel uses, the whole record in three 8-byte stores
-#include "c2d_cast_parts.hpp"   // kCastNoKey and the two launches c2d_cast_grid.hip shares
+//   main      cast_main_kernel: the key's value is toi (no hit has the key of "nothing yet": toi <= 1)
+//   finalise  cast_finalise_kernel, one lane per query: A_i and the winner in registers with their motions, the exact test and the
+//             sweep record by the routines the sweep kernel uses, the whole record in three 8-byte stores
+#include "c2d_cast_parts.hpp"   // the last launch, which c2d_cast_grid.hip shares; through it c2d_set_best.hpp
 #include "c2d_sweep_rule.hpp"   // SweepPick; through it c2d_pair_list.hpp: PolySetDev, PolyObj, poly_load, poly_collide, poly_axes, the checks
-#include "c2d_ray_strips.hpp"
 #include "c2d_wave.hpp"
 
 namespace c2d {
@@ -47,16 +42,6 @@ static_assert(sizeof(c2d_cast) == 24 && offsetof(c2d_cast, poly) == 0 && offseto
                   offsetof(c2d_cast, ny) == 12 && offsetof(c2d_cast, axis) == 16 && offsetof(c2d_cast, hit) == 18 && offsetof(c2d_cast, flags) == 19 &&
                   offsetof(c2d_cast, reserved0) == 20,
               "the kernels treat a cast as three pairs of dwords, (poly, toi) being the 64-bit key");
-
-constexpr int kCastBlock = 256;   // queries per block: one per lane
-constexpr int kCastCols = 64;     // polygons of B per staged tile
-constexpr int kCastK = C2D_POLY_KMAX;
-
-__global__ __launch_bounds__(kCastBlock) void cast_init_kernel(size_t n_a, c2d_cast* __restrict__ out)
-{
-    const size_t step = (size_t)gridDim.x * kCastBlock;
-    for (size_t i = (size_t)blockIdx.x * kCastBlock + threadIdx.x; i < n_a; i += step) reinterpret_cast<unsigned long long*>(out)[3 * i] = kCastNoKey;
-}
 
 // What the main kernel keeps of one pair: the four values of the sweep rule that decide `hit` and `toi`.  add() is SweepPick::add
 // without what the finalise pass recomputes (axis, sign, normal) and with the pairwise test's separation beside it; `live` masks an
@@ -83,35 +68,23 @@ struct CastWalk {
     C2D_DEV bool hit() const { return !never && t_in <= t_out; }
 };
 
-// the polygon turned by one slot: slot r takes slot r + 1, slot 15 takes slot 0
-C2D_DEV void cast_turn(float (&x)[kCastK], float (&y)[kCastK])
-{
-    const float fx = x[0], fy = y[0];
-#pragma unroll
-    for (int r = 0; r + 1 < kCastK; r++) {
-        x[r] = x[r + 1];
-        y[r] = y[r + 1];
-    }
-    x[kCastK - 1] = fx;
-    y[kCastK - 1] = fy;
-}
-
 // Block b: row tile b / strips, strip b % strips of the col_tiles column tiles of B.
-__global__ __launch_bounds__(kCastBlock) void cast_main_kernel(PolySetDev A, PolySetDev B, const float* __restrict__ a_dx, const float* __restrict__ a_dy,
+__global__ __launch_bounds__(kSetBlock) void cast_main_kernel(PolySetDev A, PolySetDev B, const float* __restrict__ a_dx, const float* __restrict__ a_dy,
                                                                const float* __restrict__ b_dx, const float* __restrict__ b_dy, size_t row_base, size_t col_base,
                                                                int skip_self, size_t col_tiles, uint32_t strips, c2d_cast* __restrict__ out,
                                                                uint32_t* __restrict__ async_err)
 {
-    __shared__ __attribute__((aligned(16))) float4 s_edge[kCastCols][kCastK];   // 16 KiB: {x0, y0, ex, ey} of every live edge
-    __shared__ __attribute__((aligned(16))) float4 s_own[kCastCols][kCastK];    // 16 KiB: {mn, mx, nan0 (1 or 0), off}
-    __shared__ __attribute__((aligned(8))) float2 s_face[kCastCols][kCastK];    //  8 KiB: {ux, uy}
-    __shared__ float2 s_move[kCastCols];                                         // the polygon's (dx, dy)
-    __shared__ int s_k[kCastCols];   // the count; 0: not considered by any query (out of range, or beyond n)
+    __shared__ __attribute__((aligned(16))) float4 s_edge[kSetCols][kSetK];   // 16 KiB: {x0, y0, ex, ey} of every live edge
+    __shared__ __attribute__((aligned(16))) float4 s_own[kSetCols][kSetK];    // 16 KiB: {mn, mx, nan0 (1 or 0), off}
+    __shared__ __attribute__((aligned(8))) float2 s_face[kSetCols][kSetK];    //  8 KiB: {ux, uy}
+    __shared__ float2 s_move[kSetCols];                                         // the polygon's (dx, dy)
+    __shared__ int s_k[kSetCols];   // the count; 0: not considered by any query (out of range, or beyond n)
     const uint32_t lane = threadIdx.x;
     const float inf = __builtin_inff();
 
+    // (the same text, up to what this query adds, in c2d_clearance.hip; spelt out in both: c2d_set_best.hpp says why)
     // ---- the lane's query: count, padded vertices, motion, the centre of the vertex box ---------------------------------------
-    const size_t i = (size_t)(blockIdx.x / strips) * kCastBlock + lane;
+    const size_t i = (size_t)(blockIdx.x / strips) * kSetBlock + lane;
     const bool row_valid = i < A.n;
     int ka = 1;
     bool bad_a = false;
@@ -119,9 +92,9 @@ __global__ __launch_bounds__(kCastBlock) void cast_main_kernel(PolySetDev A, Pol
     ka = bad_a ? 1 : ka;
     const bool row_live = row_valid && !bad_a;   // (a query with a count out of range gets its record from the finalise pass)
     const int kmax_a = (int)wave_max_u32((uint32_t)ka);   // wave-uniform bound of the loops over A's slots
-    float ax[kCastK], ay[kCastK];
+    float ax[kSetK], ay[kSetK];
 #pragma unroll
-    for (int r = 0; r < kCastK; r++) {
+    for (int r = 0; r < kSetK; r++) {
         ax[r] = 0.0f;
         ay[r] = 0.0f;
         if (row_live && r < ka) {   // r < ka <= A.rows: inside the planes
@@ -136,7 +109,7 @@ __global__ __launch_bounds__(kCastBlock) void cast_main_kernel(PolySetDev A, Pol
     }
     float xlo = ax[0], xhi = ax[0], ylo = ay[0], yhi = ay[0];
 #pragma unroll
-    for (int r = 1; r < kCastK; r++) {
+    for (int r = 1; r < kSetK; r++) {
         const bool used = r < ka;
         ax[r] = used ? ax[r] : ax[0];   // neutral padding: a repeated vertex adds a zero-length edge and repeats a projection
         ay[r] = used ? ay[r] : ay[0];
@@ -149,6 +122,7 @@ __global__ __launch_bounds__(kCastBlock) void cast_main_kernel(PolySetDev A, Pol
     const float ax0 = ax[0], ay0 = ay[0];   // vertex 0, whichever way the polygon is turned
     const size_t gi = row_base + i;
 
+    // (the strip, the tile loop and the staging of the frame, spelt out in each of the three main kernels: c2d_set_best.hpp says why)
     size_t tile0, tiles;
     ray_strip_tiles(col_tiles, (size_t)strips, (size_t)(blockIdx.x % strips), tile0, tiles);
 
@@ -156,8 +130,8 @@ __global__ __launch_bounds__(kCastBlock) void cast_main_kernel(PolySetDev A, Pol
     uint32_t best_j = 0;
 #pragma unroll 1
     for (size_t tile = tile0; tile < tile0 + tiles; tile++) {
-        const size_t j0 = tile * (size_t)kCastCols;
-        const uint32_t nj = (uint32_t)(B.n - j0 < (size_t)kCastCols ? B.n - j0 : (size_t)kCastCols);
+        const size_t j0 = tile * (size_t)kSetCols;
+        const uint32_t nj = (uint32_t)(B.n - j0 < (size_t)kSetCols ? B.n - j0 : (size_t)kSetCols);
         __syncthreads();   // the previous tile's readers are done
         // ---- stage 64 polygons: vertices and edge vectors, the count, the motion ---------------------------------------------------
         {
@@ -177,7 +151,7 @@ __global__ __launch_bounds__(kCastBlock) void cast_main_kernel(PolySetDev A, Pol
                 if (__ballot(bad) != 0ull && c == 0) __hip_atomic_fetch_or(async_err, C2D_ASYNC_ERR_POLY_K, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
 #pragma unroll
-            for (int m = 0; m < kCastK / 4; m++) {
+            for (int m = 0; m < kSetK / 4; m++) {
                 const int e = (int)g + 4 * m;
                 if (e < k) {   // e, e1 < k <= B.rows: inside the planes
                     const int e1 = e + 1 < k ? e + 1 : 0;
@@ -188,10 +162,11 @@ __global__ __launch_bounds__(kCastBlock) void cast_main_kernel(PolySetDev A, Pol
             }
         }
         __syncthreads();
+        // (the own interval, the NaN bit and the outward sign are the same text in c2d_clearance.hip; spelt out in both: c2d_set_best.hpp)
         // ---- hoist: lane (polygon c, edge a) -> the own interval on the edge's normal, its NaN bit and the facing heuristic ----------
 #pragma unroll 1
-        for (int m = 0; m < kCastCols * kCastK / kCastBlock; m++) {
-            const uint32_t item = lane + (uint32_t)kCastBlock * m, c = item >> 4, a = item & 15u;
+        for (int m = 0; m < kSetCols * kSetK / kSetBlock; m++) {
+            const uint32_t item = lane + (uint32_t)kSetBlock * m, c = item >> 4, a = item & 15u;
             const int k = s_k[c];
             if ((int)a < k) {
                 const float4 ed = s_edge[c][a];
@@ -223,6 +198,7 @@ __global__ __launch_bounds__(kCastBlock) void cast_main_kernel(PolySetDev A, Pol
             if (__ballot(considered) == 0ull) continue;   // (wave-uniform)
             const float2 mv = s_move[c];
             CastWalk w{mv.x - adx, mv.y - ady};
+            // (the pick below is the same text in c2d_clearance.hip, over another staged layout; spelt out in both: c2d_set_best.hpp)
             // the first axis: the edge of B_j whose outward normal sees the query's box centre farthest out
             uint32_t fe = 0;
             {
@@ -241,7 +217,7 @@ __global__ __launch_bounds__(kCastBlock) void cast_main_kernel(PolySetDev A, Pol
                 const float nx = -ed.w, ny = ed.z;
                 float mn = inf, mx = -inf;
 #pragma unroll
-                for (int r = 0; r < kCastK; r++)
+                for (int r = 0; r < kSetK; r++)
                     if (r < kmax_a) poly_minmax(nx, ny, ax[r], ay[r], mn, mx);
                 w.add(true, nx, ny, mn, mx, own.x, own.y, own.z == 0.0f && !__builtin_isnan(nx * ax0 + ny * ay0));
             }
@@ -254,7 +230,7 @@ __global__ __launch_bounds__(kCastBlock) void cast_main_kernel(PolySetDev A, Pol
                     const float nx = -ed.w, ny = ed.z;
                     float mn = inf, mx = -inf;
 #pragma unroll
-                    for (int r = 0; r < kCastK; r++)
+                    for (int r = 0; r < kSetK; r++)
                         if (r < kmax_a) poly_minmax(nx, ny, ax[r], ay[r], mn, mx);
                     w.add(true, nx, ny, mn, mx, own.x, own.y, own.z == 0.0f && !__builtin_isnan(nx * ax0 + ny * ay0));
                     open = __ballot(considered && !w.lost(best)) != 0ull;   // (wave-uniform)
@@ -264,12 +240,12 @@ __global__ __launch_bounds__(kCastBlock) void cast_main_kernel(PolySetDev A, Pol
                 // Once the wave is done the trips only turn.
                 if (open) {   // (wave-uniform)
 #pragma unroll 1
-                    for (int a = 0; a < kCastK; a++) {
+                    for (int a = 0; a < kSetK; a++) {
                         if (a < kmax_a && open) {   // (wave-uniform) beyond kmax_a every lane's axis is padding
                             const float nx = -(ay[1] - ay[0]), ny = ax[1] - ax[0];
                             float mnp = inf, mxp = -inf, mnq = inf, mxq = -inf;
 #pragma unroll
-                            for (int r = 0; r < kCastK; r++) poly_minmax(nx, ny, ax[r], ay[r], mnp, mxp);
+                            for (int r = 0; r < kSetK; r++) poly_minmax(nx, ny, ax[r], ay[r], mnp, mxp);
 #pragma unroll 1
                             for (int r = 0; r < k; r++) {
                                 const float4 v = s_edge[c][r];
@@ -279,7 +255,7 @@ __global__ __launch_bounds__(kCastBlock) void cast_main_kernel(PolySetDev A, Pol
                             w.add(a < ka, nx, ny, mnp, mxp, mnq, mxq, first_projections_ordered(nx * ax0 + ny * ay0, nx * v0.x + ny * v0.y));
                             open = __ballot(considered && !w.lost(best)) != 0ull;   // (wave-uniform)
                         }
-                        cast_turn(ax, ay);
+                        set_best_turn(ax, ay);
                     }
                 }
             }
@@ -292,20 +268,19 @@ __global__ __launch_bounds__(kCastBlock) void cast_main_kernel(PolySetDev A, Pol
             best_j = take ? (uint32_t)(j0 + c) : best_j;
         }
     }
-    if (best != inf) {
-        const unsigned long long key = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(uint32_t)(col_base + best_j);
-        __hip_atomic_fetch_min(reinterpret_cast<unsigned long long*>(out) + 3 * i, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (best != inf) set_best_publish(__float_as_uint(best), (uint32_t)col_base, best_j, out, i);
 }
 
+// (The wave-trip loop, the bad-count report, the key decode and the two loads are the same text in c2d_clearance.hip; spelt out in both,
+// because as one routine or kernel template they changed this kernel's code: c2d_set_best.hpp.)
 // One lane per query: the record of the key's polygon by the routines of the sweep kernel (the key holds col_base + j).
-__global__ __launch_bounds__(kCastBlock) void cast_finalise_kernel(PolySetDev A, PolySetDev B, const float* __restrict__ a_dx, const float* __restrict__ a_dy,
+__global__ __launch_bounds__(kSetBlock) void cast_finalise_kernel(PolySetDev A, PolySetDev B, const float* __restrict__ a_dx, const float* __restrict__ a_dy,
                                                                    const float* __restrict__ b_dx, const float* __restrict__ b_dy, size_t col_base,
                                                                    c2d_cast* __restrict__ out, uint32_t* __restrict__ async_err)
 {
-    const size_t step = (size_t)gridDim.x * kCastBlock;
+    const size_t step = (size_t)gridDim.x * kSetBlock;
     // every lane of a wave makes the same trips: the ballot below sees whole waves
-    for (size_t i0 = (size_t)blockIdx.x * kCastBlock + (threadIdx.x & ~63u); i0 < A.n; i0 += step) {
+    for (size_t i0 = (size_t)blockIdx.x * kSetBlock + (threadIdx.x & ~63u); i0 < A.n; i0 += step) {
         const size_t i = i0 + (threadIdx.x & 63u);
         const bool in = i < A.n;
         int ka = 1;
@@ -318,7 +293,7 @@ __global__ __launch_bounds__(kCastBlock) void cast_finalise_kernel(PolySetDev A,
         const size_t j = (size_t)(uint32_t)((uint32_t)key - (uint32_t)col_base);   // the main pass wrote it: j < B.n (checked all the same)
         if (bad_a) {
             s = make_uint4(0u, 0u, 0u, kSweepNoAxis | ((uint32_t)C2D_SWEEP_BAD_PAIR << 24));
-        } else if (key != kCastNoKey && j < B.n) {
+        } else if (key != kSetNoKey && j < B.n) {
             PolyObj a, b;
             poly_load(A, i, a);
             poly_load(B, j, b);
@@ -338,17 +313,12 @@ __global__ __launch_bounds__(kCastBlock) void cast_finalise_kernel(PolySetDev A,
     }
 }
 
-int cast_launch_init(c2d_ctx* ctx, hipStream_t s, size_t n_a, c2d_cast* d_out)
-{
-    hipLaunchKernelGGL(cast_init_kernel, dim3(grid_for(n_a, kCastBlock, 1 << 16)), dim3(kCastBlock), 0, s, n_a, d_out);
-    C2D_LAUNCH_CHECK(ctx);
-    return C2D_OK;
-}
+template int set_best_launch_init<3>(c2d_ctx*, hipStream_t, size_t, void*);
 
 int cast_launch_finalise(c2d_ctx* ctx, hipStream_t s, const PolySetDev& A, const PolySetDev& B, const float* d_a_dx, const float* d_a_dy,
                          const float* d_b_dx, const float* d_b_dy, size_t col_base, c2d_cast* d_out)
 {
-    hipLaunchKernelGGL(cast_finalise_kernel, dim3(grid_for(A.n, kCastBlock, 1 << 16)), dim3(kCastBlock), 0, s, A, B, d_a_dx, d_a_dy, d_b_dx, d_b_dy,
+    hipLaunchKernelGGL(cast_finalise_kernel, dim3(grid_for(A.n, kSetBlock, 1 << 16)), dim3(kSetBlock), 0, s, A, B, d_a_dx, d_a_dy, d_b_dx, d_b_dy,
                        col_base, d_out, ctx->d_async_err);
     C2D_LAUNCH_CHECK(ctx);
     return C2D_OK;
@@ -376,17 +346,15 @@ int c2d_poly_set_casts(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* 
 
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = cast_launch_init(ctx, s, A.n, d_out)) return rc;
-    if (B.n != 0) {
-        const size_t row_tiles = (A.n + kCastBlock - 1) / kCastBlock, col_tiles = (B.n + kCastCols - 1) / kCastCols;
-        const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 1;
-        const size_t strips = ray_strip_count(row_tiles, col_tiles, (size_t)cus * 8);
-        // row_tiles <= 2^24; with more than one strip, row_tiles * strips <= 8 * cus
-        hipLaunchKernelGGL(cast_main_kernel, dim3((unsigned)(row_tiles * strips)), dim3(kCastBlock), 0, s, A, B, d_a_dx, d_a_dy, d_b_dx, d_b_dy, row_base,
-                           col_base, (flags & C2D_CAST_SKIP_SELF) ? 1 : 0, col_tiles, (uint32_t)strips, d_out, ctx->d_async_err);
-        C2D_LAUNCH_CHECK(ctx);
-    }
-    return cast_launch_finalise(ctx, s, A, B, d_a_dx, d_a_dy, d_b_dx, d_b_dy, col_base, d_out);
+    return set_best_run<3>(
+        ctx, s, A.n, B.n, d_out,
+        [&](unsigned blocks, size_t col_tiles, uint32_t strips) {
+            hipLaunchKernelGGL(cast_main_kernel, dim3(blocks), dim3(kSetBlock), 0, s, A, B, d_a_dx, d_a_dy, d_b_dx, d_b_dy, row_base, col_base,
+                               (flags & C2D_CAST_SKIP_SELF) ? 1 : 0, col_tiles, strips, d_out, ctx->d_async_err);
+            C2D_LAUNCH_CHECK(ctx);
+            return (int)C2D_OK;
+        },
+        [&] { return cast_launch_finalise(ctx, s, A, B, d_a_dx, d_a_dy, d_b_dx, d_b_dy, col_base, d_out); });
 }
 
 }  // extern "C"

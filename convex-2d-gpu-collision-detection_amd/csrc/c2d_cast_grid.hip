@@ -49,7 +49,7 @@ struct CastGrid : PolySweepShape {   // Set (the polygons with their motion plan
     // could not beat a best at time 0)
     enum { kWalks = 2, kCounters = 3 };
     static constexpr unsigned int kMagic = 0x43534731u;   // "CSG1": the header's counters are those of a grid cast
-    static constexpr unsigned long long kNoKey = kCastNoKey;
+    static constexpr unsigned long long kNoKey = kSetNoKey;
     static C2D_DEV Aux aux(const Obj&) { return Aux{}; }
 
     // One candidate (the file's head, a to c): best = min(best, the pair's key) when the pair is a hit.
@@ -60,7 +60,7 @@ struct CastGrid : PolySweepShape {   // Set (the polygons with their motion plan
         n.n[kWalks]++;
         SweepPick pick{b.dx - a.dx, b.dy - a.dy};
         const bool hit0 = PolySweepShape::axes(a, b, pick);
-        unsigned long long key = kCastNoKey;
+        unsigned long long key = kSetNoKey;
         if (hit0) {
             key = (unsigned long long)gj;   // starts in overlap: toi = +0
         } else if (!pick.never && pick.t_in <= pick.t_out) {
@@ -99,7 +99,7 @@ int c2d_poly_set_casts_grid(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     if (B.set.s.n == 0) {   // no grid, no scratch: the miss record, or BAD_PAIR, for every query
-        if (int rc = cast_launch_init(ctx, s, A.set.s.n, d_out)) return rc;
+        if (int rc = set_best_launch_init<3>(ctx, s, A.set.s.n, d_out)) return rc;
         return cast_launch_finalise(ctx, s, A.set.s, B.set.s, d_a_dx, d_a_dy, d_b_dx, d_b_dy, col_base, d_out);
     }
     // one set against itself only when it moves as itself: the boxes are swept boxes

@@ -7,12 +7,11 @@
 // row_base + i != col_base + j.  The winner is the considered j with the smallest (bits of D(i, j).dist, col_base + j); dist is never
 // NaN and never -0, so the order of its bits is the order of its values, and equal distances fall to the smaller index.
 //
-// Mapping: queries over lanes, polygons of B wave-uniform.  A block of 256 lanes owns 256 queries — per lane the padded vertices,
-// the count, the vertex box and the largest |coordinate| — and a strip of consecutive column tiles of B (c2d_ray_strips.hpp).  Per
-// tile it stages 64 polygons in LDS: per live edge {x0, y0, ex, ey}, {x1, y1, len2, lo}, {ux, uy, off, hi} — the edge vector and len2
-// made once by the contract's own operations, (lo, hi) the polygon's own interval on that edge's normal with the NaN rule of its
-// first projection folded in (c2d_poly_cross.hip), (ux, uy, off) the edge's outward unit normal and offset, a heuristic that only
-// chooses WHICH canonical axis is tried first — and per polygon the count, the vertex box and the largest |coordinate|.
+// The frame is c2d_set_best.hpp's (the mapping, the strips, the three launches).  A lane keeps of its query the padded vertices, the
+// count, the vertex box and the largest |coordinate|; a tile stages per live edge {x0, y0, ex, ey}, {x1, y1, len2, lo} and
+// {ux, uy, off, hi} — len2 made once by the contract's own operations, (lo, hi) the polygon's own interval on that edge's normal
+// with the NaN rule of its first projection folded in (c2d_poly_cross.hip), (ux, uy, off) the edge's outward unit normal and offset,
+// a heuristic that only chooses WHICH canonical axis is tried first — and per polygon the vertex box and the largest |coordinate|.
 // Per (lane, j), in order of j:
 //   1. a lane whose best is already at distance 0 is done with its strip: no later j beats (+0, smaller j).
 //   2. hit, the exact test, for every remaining pair: first B_j's edge that faces the query best (one canonical axis; an axis that
@@ -23,17 +22,13 @@
 //      square root gives the pair's dist.  The minimum's VALUE does not depend on the candidates' order, and the value is all the
 //      key needs: the finalise pass recomputes the winner's record by the rule's own sequence.
 //
-// Three launches on the stream, no scratch, nothing read back:
-//   1. clearance_init_kernel      every record's first eight bytes (poly, dist) = all ones: "nothing yet"
-//   2. clearance_main_kernel      per query and strip the smallest (dist, j) as a 64-bit key, dist's bits in the high word and
-//                                 col_base + j in the low word; the strips of a row tile meet in an atomic minimum on those bytes
-//   3. clearance_finalise_kernel  one lane per query: A_i and the winner in registers, the exact test and the distance record by
-//                                 the routines the distance kernel uses, the whole record in two 16-byte stores
+//   main      clearance_main_kernel: the key's value is dist
+//   finalise  clearance_finalise_kernel, one lane per query: A_i and the winner in registers, the exact test and the distance record
+//             by the routines the distance kernel uses, the whole record in two 16-byte stores
 #include "c2d_distance_rule.hpp"
 #include "c2d_clearance_bound.hpp"
-#include "c2d_clearance_parts.hpp"   // kClrNoKey and the two launches c2d_clearance_grid.hip shares
+#include "c2d_clearance_parts.hpp"   // the last launch, which c2d_clearance_grid.hip shares; through it c2d_set_best.hpp
 #include "c2d_pair_list.hpp"   // PolySetDev, PolyObj, poly_load, poly_collide, the shared argument checks
-#include "c2d_ray_strips.hpp"
 #include "c2d_wave.hpp"
 
 namespace c2d {
@@ -42,16 +37,6 @@ static_assert(sizeof(c2d_clearance) == 32 && offsetof(c2d_clearance, poly) == 0 
                   offsetof(c2d_clearance, bx) == 16 && offsetof(c2d_clearance, edge) == 24 && offsetof(c2d_clearance, vert) == 26 &&
                   offsetof(c2d_clearance, hit) == 28 && offsetof(c2d_clearance, flags) == 29 && offsetof(c2d_clearance, reserved0) == 30,
               "the kernels treat a clearance as two halves of four dwords, (poly, dist) being the 64-bit key");
-
-constexpr int kClrBlock = 256;   // queries per block: one per lane
-constexpr int kClrCols = 64;     // polygons of B per staged tile
-constexpr int kClrK = C2D_POLY_KMAX;
-
-__global__ __launch_bounds__(kClrBlock) void clearance_init_kernel(size_t n_a, c2d_clearance* __restrict__ out)
-{
-    const size_t step = (size_t)gridDim.x * kClrBlock;
-    for (size_t i = (size_t)blockIdx.x * kClrBlock + threadIdx.x; i < n_a; i += step) reinterpret_cast<unsigned long long*>(out)[4 * i] = kClrNoKey;
-}
 
 // d2 of one candidate by the contract's own sequence: the edge (x0, y0) -> (x1, y1) with its vector and len2, the vertex (xq, yq)
 C2D_DEV float clearance_candidate(float x0, float y0, float x1, float y1, float ex, float ey, float len2, float xq, float yq)
@@ -66,33 +51,21 @@ C2D_DEV float clearance_candidate(float x0, float y0, float x1, float y1, float 
     return dx * dx + dy * dy;
 }
 
-// the polygon turned by one slot: slot r takes slot r + 1, slot 15 takes slot 0
-C2D_DEV void clearance_turn(float (&x)[kClrK], float (&y)[kClrK])
-{
-    const float fx = x[0], fy = y[0];
-#pragma unroll
-    for (int r = 0; r + 1 < kClrK; r++) {
-        x[r] = x[r + 1];
-        y[r] = y[r + 1];
-    }
-    x[kClrK - 1] = fx;
-    y[kClrK - 1] = fy;
-}
-
 // Block b: row tile b / strips, strip b % strips of the col_tiles column tiles of B.
-__global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A, PolySetDev B, size_t row_base, size_t col_base, int skip_self, size_t col_tiles,
+__global__ __launch_bounds__(kSetBlock) void clearance_main_kernel(PolySetDev A, PolySetDev B, size_t row_base, size_t col_base, int skip_self, size_t col_tiles,
                                                                    uint32_t strips, c2d_clearance* __restrict__ out, uint32_t* __restrict__ async_err)
 {
-    __shared__ __attribute__((aligned(16))) float4 s_edge[kClrCols][kClrK];   // 16 KiB: {x0, y0, ex, ey} of every live edge
-    __shared__ __attribute__((aligned(16))) float4 s_aux[kClrCols][kClrK];    // 16 KiB: {x1, y1, len2, lo}
-    __shared__ __attribute__((aligned(16))) float4 s_face[kClrCols][kClrK];   // 16 KiB: {ux, uy, off, hi}
-    __shared__ ClearanceBox s_box[kClrCols];
-    __shared__ int s_k[kClrCols];   // the count; 0: not considered by any query (out of range, or beyond n)
+    __shared__ __attribute__((aligned(16))) float4 s_edge[kSetCols][kSetK];   // 16 KiB: {x0, y0, ex, ey} of every live edge
+    __shared__ __attribute__((aligned(16))) float4 s_aux[kSetCols][kSetK];    // 16 KiB: {x1, y1, len2, lo}
+    __shared__ __attribute__((aligned(16))) float4 s_face[kSetCols][kSetK];   // 16 KiB: {ux, uy, off, hi}
+    __shared__ ClearanceBox s_box[kSetCols];
+    __shared__ int s_k[kSetCols];   // the count; 0: not considered by any query (out of range, or beyond n)
     const uint32_t lane = threadIdx.x;
     const float inf = __builtin_inff();
 
+    // (the same text, up to what this query adds, in c2d_cast.hip; spelt out in both: c2d_set_best.hpp says why)
     // ---- the lane's query: count, padded vertices, vertex box, largest |coordinate| --------------------------------------------
-    const size_t i = (size_t)(blockIdx.x / strips) * kClrBlock + lane;
+    const size_t i = (size_t)(blockIdx.x / strips) * kSetBlock + lane;
     const bool row_valid = i < A.n;
     int ka = 1;
     bool bad_a = false;
@@ -100,9 +73,9 @@ __global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A,
     ka = bad_a ? 1 : ka;
     const bool row_live = row_valid && !bad_a;   // (a query with a count out of range gets its record from the finalise pass)
     const int kmax_a = (int)wave_max_u32((uint32_t)ka);   // wave-uniform bound of the loops over A's slots
-    float ax[kClrK], ay[kClrK];
+    float ax[kSetK], ay[kSetK];
 #pragma unroll
-    for (int r = 0; r < kClrK; r++) {
+    for (int r = 0; r < kSetK; r++) {
         ax[r] = 0.0f;
         ay[r] = 0.0f;
         if (row_live && r < ka) {   // r < ka <= A.rows: inside the planes
@@ -115,7 +88,7 @@ __global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A,
         float c = __builtin_fmaxf(__builtin_fabsf(ax[0]), __builtin_fabsf(ay[0]));
         bool finite = (__builtin_fabsf(ax[0]) < inf) & (__builtin_fabsf(ay[0]) < inf);
 #pragma unroll
-        for (int r = 1; r < kClrK; r++) {
+        for (int r = 1; r < kSetK; r++) {
             const bool used = r < ka;
             ax[r] = used ? ax[r] : ax[0];   // neutral padding: a repeated vertex adds a zero-length edge and repeats a projection
             ay[r] = used ? ay[r] : ay[0];
@@ -132,6 +105,7 @@ __global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A,
     const float ax0 = ax[0], ay0 = ay[0];   // vertex 0, whichever way the polygon is turned
     const size_t gi = row_base + i;
 
+    // (the strip, the tile loop and the staging of the frame, spelt out in each of the three main kernels: c2d_set_best.hpp says why)
     size_t tile0, tiles;
     ray_strip_tiles(col_tiles, (size_t)strips, (size_t)(blockIdx.x % strips), tile0, tiles);
 
@@ -140,8 +114,8 @@ __global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A,
     bool have = false;
 #pragma unroll 1
     for (size_t tile = tile0; tile < tile0 + tiles; tile++) {
-        const size_t j0 = tile * (size_t)kClrCols;
-        const uint32_t nj = (uint32_t)(B.n - j0 < (size_t)kClrCols ? B.n - j0 : (size_t)kClrCols);
+        const size_t j0 = tile * (size_t)kSetCols;
+        const uint32_t nj = (uint32_t)(B.n - j0 < (size_t)kSetCols ? B.n - j0 : (size_t)kSetCols);
         __syncthreads();   // the previous tile's readers are done
         // ---- stage 64 polygons: edges, len2, the count ---------------------------------------------------------------------------
         {
@@ -158,7 +132,7 @@ __global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A,
                 if (__ballot(bad) != 0ull && c == 0) __hip_atomic_fetch_or(async_err, C2D_ASYNC_ERR_POLY_K, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
 #pragma unroll
-            for (int m = 0; m < kClrK / 4; m++) {
+            for (int m = 0; m < kSetK / 4; m++) {
                 const int e = (int)g + 4 * m;
                 if (e < k) {   // e, e1 < k <= B.rows: inside the planes
                     const int e1 = e + 1 < k ? e + 1 : 0;
@@ -171,10 +145,11 @@ __global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A,
             }
         }
         __syncthreads();
+        // (the own interval, the NaN bit and the outward sign are the same text in c2d_cast.hip; spelt out in both: c2d_set_best.hpp)
         // ---- hoist: lane (polygon c, edge a) -> the own interval on the edge's normal and the facing heuristic; (c, 0): the box ------
 #pragma unroll 1
-        for (int m = 0; m < kClrCols * kClrK / kClrBlock; m++) {
-            const uint32_t item = lane + (uint32_t)kClrBlock * m, c = item >> 4, a = item & 15u;
+        for (int m = 0; m < kSetCols * kSetK / kSetBlock; m++) {
+            const uint32_t item = lane + (uint32_t)kSetBlock * m, c = item >> 4, a = item & 15u;
             const int k = s_k[c];
             if ((int)a < k) {
                 const float4 ed = s_edge[c][a];
@@ -223,6 +198,7 @@ __global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A,
             const size_t gj = col_base + j0 + c;
             const bool considered = row_live && !(have && best_dist == 0.0f) && !(skip_self && gi == gj);
             if (__ballot(considered) == 0ull) continue;   // (wave-uniform)
+            // (the pick below is the same text in c2d_cast.hip, over another staged layout; spelt out in both: c2d_set_best.hpp)
             // step 2, first axis: the edge of B_j whose outward normal sees the query's box centre farthest out
             uint32_t fe = 0;
             {
@@ -242,7 +218,7 @@ __global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A,
                 const float nx = -ed.w, ny = ed.z, lo = s_aux[c][fe].w, hi = s_face[c][fe].w;
                 float mn = inf, mx = -inf;
 #pragma unroll
-                for (int r = 0; r < kClrK; r++)
+                for (int r = 0; r < kSetK; r++)
                     if (r < kmax_a) poly_minmax(nx, ny, ax[r], ay[r], mn, mx);
                 // (B_j's own first projection is folded into lo / hi; A_i's is checked here: first_projections_ordered)
                 sep = ((hi < mn) || (mx < lo)) && !__builtin_isnan(nx * ax[0] + ny * ay[0]);
@@ -251,12 +227,12 @@ __global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A,
                 // A's axes: always the one from slot 0 to slot 1, A turned by one slot per trip and back in place after 16 (the loop
                 // stays rolled and nothing of an edge is kept across pairs); slot ka is vertex 0 again, so the polygon closes itself
 #pragma unroll 1
-                for (int a = 0; a < kClrK; a++) {
+                for (int a = 0; a < kSetK; a++) {
                     if (a < kmax_a) {   // (wave-uniform) beyond it every lane's axis is a zero vector: it never separates
                         const float nx = -(ay[1] - ay[0]), ny = ax[1] - ax[0];
                         float mnp = inf, mxp = -inf, mnq = inf, mxq = -inf;
 #pragma unroll
-                        for (int r = 0; r < kClrK; r++) poly_minmax(nx, ny, ax[r], ay[r], mnp, mxp);
+                        for (int r = 0; r < kSetK; r++) poly_minmax(nx, ny, ax[r], ay[r], mnp, mxp);
 #pragma unroll 1
                         for (int r = 0; r < k; r++) {
                             const float4 v = s_edge[c][r];
@@ -265,7 +241,7 @@ __global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A,
                         const float4 v0 = s_edge[c][0];
                         sep |= a < ka && ((mxp < mnq) || (mxq < mnp)) && first_projections_ordered(nx * ax0 + ny * ay0, nx * v0.x + ny * v0.y);
                     }
-                    clearance_turn(ax, ay);
+                    set_best_turn(ax, ay);
                 }
 #pragma unroll 1
                 for (int eb = 0; eb < k; eb++) {
@@ -273,7 +249,7 @@ __global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A,
                     const float nx = -ed.w, ny = ed.z, lo = s_aux[c][eb].w, hi = s_face[c][eb].w;
                     float mn = inf, mx = -inf;
 #pragma unroll
-                    for (int r = 0; r < kClrK; r++)
+                    for (int r = 0; r < kSetK; r++)
                         if (r < kmax_a) poly_minmax(nx, ny, ax[r], ay[r], mn, mx);
                     sep |= ((hi < mn) || (mx < lo)) && !__builtin_isnan(nx * ax[0] + ny * ay[0]);
                 }
@@ -290,7 +266,7 @@ __global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A,
             if (__ballot(run) != 0ull) {   // (wave-uniform)
                 // side 0: A's edges (registers) against B_j's vertices
 #pragma unroll 1
-                for (int e = 0; e < kClrK; e++) {   // (A turned by one slot per trip, as above)
+                for (int e = 0; e < kSetK; e++) {   // (A turned by one slot per trip, as above)
                     if (e < kmax_a) {   // (wave-uniform)
                         const float x0 = ax[0], y0 = ay[0], x1 = ax[1], y1 = ay[1];
                         const float ex = x1 - x0, ey = y1 - y0;
@@ -303,14 +279,14 @@ __global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A,
                             d2min = (live_e && d2 < d2min) ? d2 : d2min;   // strict, from +inf: a NaN never enters
                         }
                     }
-                    clearance_turn(ax, ay);
+                    set_best_turn(ax, ay);
                 }
                 // side 1: B_j's edges against A's vertices (registers)
 #pragma unroll 1
                 for (int e = 0; e < k; e++) {
                     const float4 ed = s_edge[c][e], au = s_aux[c][e];
 #pragma unroll
-                    for (int v = 0; v < kClrK; v++) {
+                    for (int v = 0; v < kSetK; v++) {
                         if (v < kmax_a) {   // (wave-uniform)
                             const float d2 = clearance_candidate(ed.x, ed.y, au.x, au.y, ed.z, ed.w, au.z, ax[v], ay[v]);
                             d2min = (v < ka && d2 < d2min) ? d2 : d2min;
@@ -326,20 +302,18 @@ __global__ __launch_bounds__(kClrBlock) void clearance_main_kernel(PolySetDev A,
             have |= take;
         }
     }
-    if (have) {
-        const uint32_t db = best_dist == 0.0f ? 0u : __float_as_uint(best_dist);   // (never -0; all the same)
-        const unsigned long long key = ((unsigned long long)db << 32) | (unsigned long long)(uint32_t)(col_base + best_j);
-        __hip_atomic_fetch_min(reinterpret_cast<unsigned long long*>(out) + 4 * i, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (have) set_best_publish(best_dist == 0.0f ? 0u : __float_as_uint(best_dist), (uint32_t)col_base, best_j, out, i);   // (never -0; all the same)
 }
 
+// (The wave-trip loop, the bad-count report, the key decode and the two loads are the same text in c2d_cast.hip; spelt out in both,
+// because as one routine or kernel template they changed this kernel's code: c2d_set_best.hpp.)
 // One lane per query: the record of the key's polygon by the routines of the distance kernel (the key holds col_base + j).
-__global__ __launch_bounds__(kClrBlock) void clearance_finalise_kernel(PolySetDev A, PolySetDev B, size_t col_base, c2d_clearance* __restrict__ out,
+__global__ __launch_bounds__(kSetBlock) void clearance_finalise_kernel(PolySetDev A, PolySetDev B, size_t col_base, c2d_clearance* __restrict__ out,
                                                                        uint32_t* __restrict__ async_err)
 {
-    const size_t step = (size_t)gridDim.x * kClrBlock;
+    const size_t step = (size_t)gridDim.x * kSetBlock;
     // every lane of a wave makes the same trips: the ballot below sees whole waves
-    for (size_t i0 = (size_t)blockIdx.x * kClrBlock + (threadIdx.x & ~63u); i0 < A.n; i0 += step) {
+    for (size_t i0 = (size_t)blockIdx.x * kSetBlock + (threadIdx.x & ~63u); i0 < A.n; i0 += step) {
         const size_t i = i0 + (threadIdx.x & 63u);
         const bool in = i < A.n;
         int ka = 1;
@@ -354,7 +328,7 @@ __global__ __launch_bounds__(kClrBlock) void clearance_finalise_kernel(PolySetDe
         if (bad_a) {
             d0 = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
             d1 = make_uint4(0u, 0u, kDistanceNone, (uint32_t)C2D_DISTANCE_BAD_PAIR << 8);
-        } else if (key != kClrNoKey && j < B.n) {
+        } else if (key != kSetNoKey && j < B.n) {
             PolyObj a, b;
             poly_load(A, i, a);
             poly_load(B, j, b);
@@ -368,16 +342,11 @@ __global__ __launch_bounds__(kClrBlock) void clearance_finalise_kernel(PolySetDe
     }
 }
 
-int clearance_launch_init(c2d_ctx* ctx, hipStream_t s, size_t n_a, c2d_clearance* d_out)
-{
-    hipLaunchKernelGGL(clearance_init_kernel, dim3(grid_for(n_a, kClrBlock, 1 << 16)), dim3(kClrBlock), 0, s, n_a, d_out);
-    C2D_LAUNCH_CHECK(ctx);
-    return C2D_OK;
-}
+template int set_best_launch_init<4>(c2d_ctx*, hipStream_t, size_t, void*);
 
 int clearance_launch_finalise(c2d_ctx* ctx, hipStream_t s, const PolySetDev& A, const PolySetDev& B, size_t col_base, c2d_clearance* d_out)
 {
-    hipLaunchKernelGGL(clearance_finalise_kernel, dim3(grid_for(A.n, kClrBlock, 1 << 16)), dim3(kClrBlock), 0, s, A, B, col_base, d_out, ctx->d_async_err);
+    hipLaunchKernelGGL(clearance_finalise_kernel, dim3(grid_for(A.n, kSetBlock, 1 << 16)), dim3(kSetBlock), 0, s, A, B, col_base, d_out, ctx->d_async_err);
     C2D_LAUNCH_CHECK(ctx);
     return C2D_OK;
 }
@@ -404,17 +373,15 @@ int c2d_poly_set_clearances(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_
 
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = clearance_launch_init(ctx, s, A.n, d_out)) return rc;
-    if (B.n != 0) {
-        const size_t row_tiles = (A.n + kClrBlock - 1) / kClrBlock, col_tiles = (B.n + kClrCols - 1) / kClrCols;
-        const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 1;
-        const size_t strips = ray_strip_count(row_tiles, col_tiles, (size_t)cus * 8);
-        // row_tiles <= 2^24; with more than one strip, row_tiles * strips <= 8 * cus
-        hipLaunchKernelGGL(clearance_main_kernel, dim3((unsigned)(row_tiles * strips)), dim3(kClrBlock), 0, s, A, B, row_base, col_base,
-                           (flags & C2D_CLEARANCE_SKIP_SELF) ? 1 : 0, col_tiles, (uint32_t)strips, d_out, ctx->d_async_err);
-        C2D_LAUNCH_CHECK(ctx);
-    }
-    return clearance_launch_finalise(ctx, s, A, B, col_base, d_out);
+    return set_best_run<4>(
+        ctx, s, A.n, B.n, d_out,
+        [&](unsigned blocks, size_t col_tiles, uint32_t strips) {
+            hipLaunchKernelGGL(clearance_main_kernel, dim3(blocks), dim3(kSetBlock), 0, s, A, B, row_base, col_base, (flags & C2D_CLEARANCE_SKIP_SELF) ? 1 : 0,
+                               col_tiles, strips, d_out, ctx->d_async_err);
+            C2D_LAUNCH_CHECK(ctx);
+            return (int)C2D_OK;
+        },
+        [&] { return clearance_launch_finalise(ctx, s, A, B, col_base, d_out); });
 }
 
 }  // extern "C"

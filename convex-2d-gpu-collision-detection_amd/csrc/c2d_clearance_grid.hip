@@ -73,7 +73,7 @@ struct ClearanceGrid {
     // bound skipped the others)
     enum { kTested = 2, kWalks = 3, kCounters = 4 };
     static constexpr unsigned int kMagic = 0x43474731u;   // "CGG1": the header's counters are those of a grid clearance query
-    static constexpr unsigned long long kNoKey = kClrNoKey;
+    static constexpr unsigned long long kNoKey = kSetNoKey;
     static __host__ __device__ size_t size(const Set& X) { return X.n; }
     static constexpr auto& load = poly_load;   // (the function itself: a wrapper renames the kernels' registers)
     static C2D_DEV Aux aux(const Obj& a) { return clearance_grid_box(a); }
@@ -131,7 +131,7 @@ int c2d_poly_set_clearances_grid(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     if (B.set.n == 0) {   // no grid, no scratch: the NONE record, or BAD_PAIR, for every query
-        if (int rc = clearance_launch_init(ctx, s, A.set.n, d_out)) return rc;
+        if (int rc = set_best_launch_init<4>(ctx, s, A.set.n, d_out)) return rc;
         return clearance_launch_finalise(ctx, s, A.set, B.set, col_base, d_out);
     }
     WorkspaceUse use(ctx, s);

@@ -9,21 +9,13 @@
 // Polygons in order of j, per polygon the inside candidate and then the edges in order of e; a candidate replaces the best only under
 // strict t < best.  So the smallest t wins, among equal t the smallest j, then inside before edges, then the smallest e.
 //
-// Mapping: rays over lanes, polygons wave-uniform.  A block of 256 lanes owns 256 rays (four VGPRs) and a strip of consecutive column
-// tiles of B (c2d_ray_strips.hpp).  Per tile it stages 64 polygons in LDS: per live edge one 16-byte entry {x0, y0, ex, ey}, the edge
-// vector made once per polygon by the rule's own two subtractions, and the count.  The polygon index is wave-uniform, so the edge loop
-// runs to that polygon's own k and every LDS read is a broadcast; per edge a lane makes the three cross products and the compares,
-// and the two divisions become one (t alone) under a wave-uniform "some lane has a usable edge" branch.
-//
-// Three launches on the stream, no scratch, nothing read back:
-//   1. ray_init_kernel      every record's first eight bytes (poly, t) = all ones: "nothing yet"
-//   2. ray_main_kernel      per ray and strip the smallest (t, j) as a 64-bit key, t's bits (a -0 made +0) in the high word and
-//                           col_base + j in the low word: for 0 <= t <= 1 the order of the bits is the order of t.  The strips of a
-//                           row tile meet in an atomic minimum on those eight bytes, which does not depend on who arrives first.
-//   3. ray_finalise_kernel  one lane per ray: re-evaluates the winning polygon alone (at most 16 edges) by the rule's own sequence
-//                           and writes the whole record with one 16-byte store.
+// The frame is c2d_set_best.hpp's (the mapping, the strips, the three launches); the query in a lane's registers is a ray (four
+// VGPRs), and a tile stages the edges {x0, y0, ex, ey} and the counts alone.  Per edge a lane makes the three cross products and the
+// compares, and the two divisions become one (t alone) under a wave-uniform "some lane has a usable edge" branch.
+//   main      ray_main_kernel: the key's value is t, a -0 made +0: for 0 <= t <= 1 the order of the bits is the order of t
+//   finalise  ray_finalise_kernel, one lane per ray: re-evaluates the winning polygon alone (at most 16 edges) by the rule's own
+//             sequence and writes the whole record with one 16-byte store.
 #include "c2d_ray_rule.hpp"
-#include "c2d_ray_strips.hpp"
 
 namespace c2d {
 
@@ -31,34 +23,28 @@ static_assert(sizeof(c2d_ray_hit) == 16 && offsetof(c2d_ray_hit, poly) == 0 && o
                   offsetof(c2d_ray_hit, edge) == 12 && offsetof(c2d_ray_hit, hit) == 14 && offsetof(c2d_ray_hit, flags) == 15,
               "the kernels treat a ray hit as four dwords, (poly, t) being the 64-bit key");
 
-constexpr int kRayCols = 64;     // polygons of B per staged tile
-__global__ __launch_bounds__(kRayBlock) void ray_init_kernel(size_t n_rays, c2d_ray_hit* __restrict__ out)
-{
-    const size_t step = (size_t)gridDim.x * kRayBlock;
-    for (size_t r = (size_t)blockIdx.x * kRayBlock + threadIdx.x; r < n_rays; r += step) reinterpret_cast<unsigned long long*>(out)[2 * r] = kRayNoKey;
-}
-
 // Block b: row tile b / strips, strip b % strips of the col_tiles column tiles of B.
-__global__ __launch_bounds__(kRayBlock) void ray_main_kernel(RayPlanes R, size_t n_rays, PolySetDev B, uint32_t col_base, size_t col_tiles, uint32_t strips,
+__global__ __launch_bounds__(kSetBlock) void ray_main_kernel(RayPlanes R, size_t n_rays, PolySetDev B, uint32_t col_base, size_t col_tiles, uint32_t strips,
                                                              c2d_ray_hit* __restrict__ out, uint32_t* __restrict__ async_err)
 {
-    __shared__ __attribute__((aligned(16))) float4 s_edge[kRayCols][kRayK];   // 16 KiB: {x0, y0, ex, ey} of every live edge
-    __shared__ int s_k[kRayCols];                                             // the count; 0: not in any hit (out of range, or beyond n)
+    __shared__ __attribute__((aligned(16))) float4 s_edge[kSetCols][kSetK];   // 16 KiB: {x0, y0, ex, ey} of every live edge
+    __shared__ int s_k[kSetCols];                                             // the count; 0: not in any hit (out of range, or beyond n)
     const uint32_t lane = threadIdx.x;
-    const size_t r = (size_t)(blockIdx.x / strips) * kRayBlock + lane;
+    const size_t r = (size_t)(blockIdx.x / strips) * kSetBlock + lane;
     const bool row_valid = r < n_rays;
     // a lane without a ray carries NaN: every compare below fails, and it writes nothing
     const float nan = __builtin_nanf("");
     const float ox = row_valid ? R.ox[r] : nan, oy = row_valid ? R.oy[r] : nan, dx = row_valid ? R.dx[r] : nan, dy = row_valid ? R.dy[r] : nan;
-    size_t tile0, tiles;
-    ray_strip_tiles(col_tiles, (size_t)strips, (size_t)(blockIdx.x % strips), tile0, tiles);
 
     float best_t = __builtin_inff();
     uint32_t best_j = 0xFFFFFFFFu;
+    // (the strip, the tile loop and the staging of the frame, spelt out in each of the three main kernels: c2d_set_best.hpp says why)
+    size_t tile0, tiles;
+    ray_strip_tiles(col_tiles, (size_t)strips, (size_t)(blockIdx.x % strips), tile0, tiles);
 #pragma unroll 1
     for (size_t tile = tile0; tile < tile0 + tiles; tile++) {
-        const size_t j0 = tile * (size_t)kRayCols;
-        const uint32_t nj = (uint32_t)(B.n - j0 < (size_t)kRayCols ? B.n - j0 : (size_t)kRayCols);
+        const size_t j0 = tile * (size_t)kSetCols;
+        const uint32_t nj = (uint32_t)(B.n - j0 < (size_t)kSetCols ? B.n - j0 : (size_t)kSetCols);
         __syncthreads();   // the previous tile's readers are done
         {
             const uint32_t c = lane & 63u, g = lane >> 6;
@@ -74,7 +60,7 @@ __global__ __launch_bounds__(kRayBlock) void ray_main_kernel(RayPlanes R, size_t
                 if (__ballot(bad) != 0ull && c == 0) __hip_atomic_fetch_or(async_err, C2D_ASYNC_ERR_POLY_K, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
 #pragma unroll
-            for (int m = 0; m < kRayK / 4; m++) {
+            for (int m = 0; m < kSetK / 4; m++) {
                 const int e = (int)g + 4 * m;
                 if (e < k) {   // e, e1 < k <= B.rows: inside the planes
                     const int e1 = e + 1 < k ? e + 1 : 0;
@@ -111,11 +97,8 @@ __global__ __launch_bounds__(kRayBlock) void ray_main_kernel(RayPlanes R, size_t
             best_j = take ? (uint32_t)j0 + c : best_j;
         }
     }
-    if (row_valid && best_j != 0xFFFFFFFFu) {
-        const uint32_t tb = best_t == 0.0f ? 0u : __float_as_uint(best_t);   // -0 -> +0: then the bits order as t does
-        const unsigned long long key = ((unsigned long long)tb << 32) | (unsigned long long)(col_base + best_j);
-        __hip_atomic_fetch_min(reinterpret_cast<unsigned long long*>(out) + 2 * r, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (row_valid && best_j != 0xFFFFFFFFu)   // -0 -> +0: then the bits order as t does
+        set_best_publish(best_t == 0.0f ? 0u : __float_as_uint(best_t), col_base, best_j, out, r);
 }
 
 // One lane per ray: the record of the key's polygon by the rule's own sequence (the key holds the winner's t and col_base + j).
@@ -127,7 +110,7 @@ __global__ __launch_bounds__(kRayBlock) void ray_finalise_kernel(RayPlanes R, si
         uint4 rec = make_uint4(0xFFFFFFFFu, __float_as_uint(__builtin_inff()), 0u, kRayNone16);   // nothing chosen
         const uint32_t poly = (uint32_t)key;
         const size_t j = (size_t)(poly - col_base);   // the main pass wrote it: j < B.n (checked all the same: nothing outside B is read)
-        if (key != kRayNoKey && j < B.n) {
+        if (key != kSetNoKey && j < B.n) {
             const float ox = R.ox[r], oy = R.oy[r], dx = R.dx[r], dy = R.dy[r];
             int k;
             (void)poly_count(B, j, k);   // in range: the polygon was in a hit
@@ -160,12 +143,7 @@ __global__ __launch_bounds__(kRayBlock) void ray_finalise_kernel(RayPlanes R, si
     }
 }
 
-int ray_launch_init(c2d_ctx* ctx, hipStream_t s, size_t n_rays, c2d_ray_hit* d_out)
-{
-    hipLaunchKernelGGL(ray_init_kernel, dim3(grid_for(n_rays, kRayBlock, 1 << 16)), dim3(kRayBlock), 0, s, n_rays, d_out);
-    C2D_LAUNCH_CHECK(ctx);
-    return C2D_OK;
-}
+template int set_best_launch_init<2>(c2d_ctx*, hipStream_t, size_t, void*);
 
 int ray_launch_finalise(c2d_ctx* ctx, hipStream_t s, const RayPlanes& R, size_t n_rays, const PolySetDev& B, uint32_t col_base, c2d_ray_hit* d_out)
 {
@@ -207,17 +185,14 @@ int c2d_poly_ray_casts(c2d_ctx* ctx, const float* const d_rays[4], size_t n_rays
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     const RayPlanes R{d_rays[0], d_rays[1], d_rays[2], d_rays[3]};
-    if (int rc = ray_launch_init(ctx, s, n_rays, d_out)) return rc;
-    if (B.n != 0) {
-        const size_t row_tiles = (n_rays + kRayBlock - 1) / kRayBlock, col_tiles = (B.n + kRayCols - 1) / kRayCols;
-        const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 1;
-        const size_t strips = ray_strip_count(row_tiles, col_tiles, (size_t)cus * 8);   // eight blocks of 256 fill a CU
-        // row_tiles <= 2^24; with more than one strip, row_tiles * strips <= 8 * cus
-        hipLaunchKernelGGL(ray_main_kernel, dim3((unsigned)(row_tiles * strips)), dim3(kRayBlock), 0, s, R, n_rays, B, (uint32_t)col_base, col_tiles,
-                           (uint32_t)strips, d_out, ctx->d_async_err);
-        C2D_LAUNCH_CHECK(ctx);
-    }
-    return ray_launch_finalise(ctx, s, R, n_rays, B, (uint32_t)col_base, d_out);
+    return set_best_run<2>(
+        ctx, s, n_rays, B.n, d_out,
+        [&](unsigned blocks, size_t col_tiles, uint32_t strips) {
+            hipLaunchKernelGGL(ray_main_kernel, dim3(blocks), dim3(kSetBlock), 0, s, R, n_rays, B, (uint32_t)col_base, col_tiles, strips, d_out, ctx->d_async_err);
+            C2D_LAUNCH_CHECK(ctx);
+            return (int)C2D_OK;
+        },
+        [&] { return ray_launch_finalise(ctx, s, R, n_rays, B, (uint32_t)col_base, d_out); });
 }
 
 }  // extern "C"

@@ -7,7 +7,7 @@
 //   1. boxes      broad_box_kernel with the policy below: the float min / max of the live vertices; a NaN or an infinite coordinate
 //                 makes the polygon wild; a bad count makes it absent (reported through the asynchronous error word)
 //   2. grid, sort broad_grid_and_sort over B alone (the grid's bounds are B's)
-//   3. init       ray_launch_init: every record's key = "nothing yet"; ray_grid_begin_kernel: the counters of this call
+//   3. init       set_best_launch_init: every record's key = "nothing yet"; ray_grid_begin_kernel: the counters of this call
 //   4. outliers   ray_outlier_kernel: the regular boxes at or above the cell-size pick (at most max(4, n / 65536)) are the ones that may
 //                 lie outside the grid's bounds, where the walk's proof does not reach: they are listed and tested against every ray
 //   5. walk       ray_walk_kernel, the hot path: one ray per lane.  Per key row of the walk (c2d_ray_walk.hpp) a binary search on the
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(kRayBlock) void ray_walk_kernel(RayGridQuery q, c2d
         }
         RayWalk w;
         bool walked = ray_walk_begin(wg, rd, w);
-        unsigned long long best = kRayNoKey;
+        unsigned long long best = kSetNoKey;
         if (walked) {
             uint32_t seen = 0;
 #pragma unroll 1
@@ -236,7 +236,7 @@ __global__ __launch_bounds__(kRayBlock) void ray_walk_kernel(RayGridQuery q, c2d
                     best = key < best ? key : best;
                 }
             }
-            if (best != kRayNoKey) reinterpret_cast<unsigned long long*>(out)[2 * r] = best;
+            if (best != kSetNoKey) reinterpret_cast<unsigned long long*>(out)[2 * r] = best;
         } else {
             const unsigned int slot = atomicAdd(&g->n_long, 1u);   // each ray at most once: slot < n_rays
             if ((size_t)slot < q.n_rays) q.listed[slot] = (uint32_t)r;
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(kBroadBlock) void ray_list_kernel(RayGridQuery q, c
         if (r >= q.n_rays) continue;
         const float ox = q.R.ox[r], oy = q.R.oy[r], dx = q.R.dx[r], dy = q.R.dy[r];
         const RayD rd = ray_d(ox, oy, dx, dy);
-        unsigned long long best = kRayNoKey;
+        unsigned long long best = kSetNoKey;
         for (size_t j = lane; j < n_b; j += 64) {
             int kk;
             if (!poly_count(q.B, j, kk)) continue;   // absent (the box pass has reported it)
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(kBroadBlock) void ray_list_kernel(RayGridQuery q, c
             }
         }
         best = wave_min_u64(best);
-        if (lane == 0 && best != kRayNoKey) reinterpret_cast<unsigned long long*>(out)[2 * r] = best;
+        if (lane == 0 && best != kSetNoKey) reinterpret_cast<unsigned long long*>(out)[2 * r] = best;
     }
 }
 
@@ -300,7 +300,7 @@ int c2d_poly_ray_casts_grid(c2d_ctx* ctx, const float* const d_rays[4], size_t n
     hipStream_t s = (hipStream_t)stream;
     const RayPlanes R{d_rays[0], d_rays[1], d_rays[2], d_rays[3]};
     if (B.n == 0) {   // no grid, no scratch: the no-hit record for every ray
-        if (int rc = ray_launch_init(ctx, s, n_rays, d_out)) return rc;
+        if (int rc = set_best_launch_init<2>(ctx, s, n_rays, d_out)) return rc;
         return ray_launch_finalise(ctx, s, R, n_rays, B, (uint32_t)col_base, d_out);
     }
     // the scratch of a pair search of n_rays rows against B: the row list holds the listed rays; B's boxes are the only boxes
@@ -317,7 +317,7 @@ int c2d_poly_ray_casts_grid(c2d_ctx* ctx, const float* const d_rays[4], size_t n
     if (int rc = broad_grid_and_sort(ctx, s, W, B.n, B.n, true)) return rc;
     uint32_t* outliers = W.keys == W.keys0 ? W.keys1 : W.keys0;   // the sort's other buffer is free again
 
-    if (int rc = ray_launch_init(ctx, s, n_rays, d_out)) return rc;
+    if (int rc = set_best_launch_init<2>(ctx, s, n_rays, d_out)) return rc;
     hipLaunchKernelGGL(ray_grid_begin_kernel, dim3(1), dim3(64), 0, s, W.g);
     C2D_LAUNCH_CHECK(ctx);
     hipLaunchKernelGGL(ray_outlier_kernel, dim3(grid_b), dim3(kBroadBlock), 0, s, (const float4*)W.sbox, W.idx, B.n, W.g, outliers);

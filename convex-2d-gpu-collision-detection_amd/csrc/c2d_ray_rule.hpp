@@ -1,17 +1,15 @@
 // c2d_ray_rule.hpp — what the ray queries share (c2d_ray.hip: c2d_poly_ray_casts; c2d_ray_grid.hip: c2d_poly_ray_casts_grid): the ray
 // planes, the three cross products of one (ray, edge) and the usable-edge test of the contract of include/c2d.h, the 64-bit (t, j)
-// key, and the first and the last launch of either call.
+// key, and the last launch of either call (the first is c2d_set_best.hpp's set_best_launch_init<2>).
 #pragma once
 
 #include "c2d_cross.hpp"
 #include "c2d_math.hpp"
-#include "c2d_poly_pair.hpp"   // PolySetDev, poly_set_check, poly_count
+#include "c2d_set_best.hpp"   // kSetNoKey, set_best_launch_init; through it c2d_poly_pair.hpp: PolySetDev, poly_set_check, poly_count
 
 namespace c2d {
 
 constexpr int kRayBlock = 256;   // rays per block: one per lane
-constexpr int kRayK = C2D_POLY_KMAX;
-constexpr unsigned long long kRayNoKey = ~0ull;
 constexpr uint32_t kRayNone16 = 0xFFFFu;
 
 struct RayPlanes {
@@ -51,8 +49,7 @@ C2D_DEV unsigned long long ray_key(float t, uint32_t poly)
     return ((unsigned long long)tb << 32) | (unsigned long long)poly;
 }
 
-// c2d_ray.hip: every record's key = kRayNoKey ("nothing yet") / every record from its key, by the rule's own sequence
-int ray_launch_init(c2d_ctx* ctx, hipStream_t s, size_t n_rays, c2d_ray_hit* d_out);
+// c2d_ray.hip: every record from its key, by the rule's own sequence
 int ray_launch_finalise(c2d_ctx* ctx, hipStream_t s, const RayPlanes& R, size_t n_rays, const PolySetDev& B, uint32_t col_base, c2d_ray_hit* d_out);
 // the argument checks both calls share (everything but the ctx): C2D_OK with B filled in, or the refusal
 int ray_check_args(c2d_ctx* ctx, const char* what, const float* const d_rays[4], size_t n_rays, const c2d_poly_set* b, size_t col_base,

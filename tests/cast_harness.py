@@ -6,6 +6,7 @@ import functools
 
 import numpy as np
 
+import best_key_harness as best
 import cast_cases as cases
 import cast_ref as ref
 import clearance_cases
@@ -23,11 +24,8 @@ def call(eng, a_set, b_set, n_a, a_motion=None, b_motion=None, capacity=None, ex
     return h.banded_call(eng, DT, n_a, lambda ptr: eng.poly_set_casts(a_set, b_set, a_motion, b_motion, out=ptr, **kw), cap, expect_error, band)[:n_a].copy()
 
 
-def twice(eng, a_set, b_set, n_a, what, **kw):
-    """the call, run twice: the two outputs must be the same bytes"""
-    got, again = call(eng, a_set, b_set, n_a, **kw), call(eng, a_set, b_set, n_a, **kw)
-    assert got.tobytes() == again.tobytes(), f"{what}: two runs differ"
-    return got
+twice = functools.partial(best.twice, call)             # twice(eng, a_set, b_set, n_a, what, **kw): the call, run twice: the same bytes
+assert_same = functools.partial(best.assert_same, ref)  # assert_same(got, want, what)
 
 
 def take_motion(m, idx):
@@ -36,8 +34,8 @@ def take_motion(m, idx):
 
 def indexed_reference(a, ia, b, ib, ma=None, mb=None, S=None, **kw):
     """the reference of (take(a, ia), take(b, ib)) with the motions indexed alike: the per-pair records are computed for the distinct
-    polygons once (or handed in as S) and indexed.  Beyond 2^22 pairs the pick is made once per DISTINCT query and indexed by ia,
-    as clearance_harness.indexed_reference does."""
+    polygons once (or handed in as S) and indexed.  Beyond 2^22 pairs the pick is made once per DISTINCT query and indexed by ia
+    (best_key_harness.reduce_by_query)."""
     ia, ib = np.asarray(ia, np.int64), np.asarray(ib, np.int64)
     if len(ia) == 0:
         return np.zeros(0, DT)
@@ -46,22 +44,7 @@ def indexed_reference(a, ia, b, ib, ma=None, mb=None, S=None, **kw):
     bad_a, bad_b = ref.bad_counts(a), ref.bad_counts(b)[ib]
     if len(ia) * len(ib) <= 1 << 22:
         return ref.reduce(S[np.ix_(ia, ib)], bad_a[ia], bad_b, **kw)
-    rb, cb, flags = kw.get("row_base", 0), kw.get("col_base", 0), kw.get("flags", 0)
-    Sb = S[:, ib]
-    out = ref.reduce(Sb, bad_a, bad_b, col_base=cb)[ia]
-    if flags & ref.SKIP_SELF:      # the self pair matters only where it is the winner: those queries are reduced one by one
-        j_self = rb + np.arange(len(ia), dtype=np.int64) - cb
-        own = (j_self >= 0) & (j_self < len(ib)) & (out["poly"].astype(np.int64) == cb + j_self)
-        for q in np.flatnonzero(own):
-            out[q] = ref.reduce(Sb[ia[q]:ia[q] + 1], bad_a[ia[q]:ia[q] + 1], bad_b, row_base=rb + int(q), col_base=cb, flags=flags)[0]
-    return out
-
-
-def assert_same(got, want, what):
-    ok = ref.same(got, want)
-    if not ok.all():
-        q = int(np.flatnonzero(~ok)[0])
-        raise AssertionError(f"{what}: {int((~ok).sum())} of {len(want)} records differ; first at {q}: got {got[q]}, want {want[q]}")
+    return best.reduce_by_query(ref, S, ia, ib, bad_a, bad_b, **kw)
 
 
 class Scene:

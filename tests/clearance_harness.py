@@ -6,6 +6,7 @@ import functools
 
 import numpy as np
 
+import best_key_harness as best
 import clearance_cases as cases
 import clearance_ref as ref
 import pair_list_harness as h
@@ -21,11 +22,8 @@ def call(eng, a_set, b_set, n_a, capacity=None, expect_error=False, band=None, *
     return h.banded_call(eng, DT, n_a, lambda ptr: eng.poly_set_clearances(a_set, b_set, ptr, **kw), cap, expect_error, band)[:n_a].copy()
 
 
-def twice(eng, a_set, b_set, n_a, what, **kw):
-    """the call, run twice: the two outputs must be the same bytes"""
-    got, again = call(eng, a_set, b_set, n_a, **kw), call(eng, a_set, b_set, n_a, **kw)
-    assert got.tobytes() == again.tobytes(), f"{what}: two runs differ"
-    return got
+twice = functools.partial(best.twice, call)             # twice(eng, a_set, b_set, n_a, what, **kw): the call, run twice: the same bytes
+assert_same = functools.partial(best.assert_same, ref)  # assert_same(got, want, what)
 
 
 def take(s, idx):
@@ -37,8 +35,7 @@ def take(s, idx):
 def indexed_reference(a, ia, b, ib, D=None, by_query=None, **kw):
     """the reference of (take(a, ia), take(b, ib)): the per-pair records are computed for the distinct polygons once (or handed in
     as D) and indexed.  by_query (the default beyond 2^22 pairs): the pick is made once per DISTINCT query against take(b, ib) and
-    indexed by ia, so that the cost does not grow with len(ia); the self pair of SKIP_SELF depends on the query's own place, and
-    matters only where it is the winner: those queries are reduced one by one."""
+    indexed by ia (best_key_harness.reduce_by_query)."""
     ia, ib = np.asarray(ia, np.int64), np.asarray(ib, np.int64)
     if len(ia) == 0:
         return np.zeros(0, DT)
@@ -49,22 +46,7 @@ def indexed_reference(a, ia, b, ib, D=None, by_query=None, **kw):
         by_query = len(ia) * len(ib) > 1 << 22
     if not by_query:
         return ref.reduce(D[np.ix_(ia, ib)], bad_a[ia], bad_b, **kw)
-    rb, cb, flags = kw.get("row_base", 0), kw.get("col_base", 0), kw.get("flags", 0)
-    Db = D[:, ib]
-    out = ref.reduce(Db, bad_a, bad_b, col_base=cb)[ia]
-    if flags & ref.SKIP_SELF:
-        j_self = rb + np.arange(len(ia), dtype=np.int64) - cb
-        own = (j_self >= 0) & (j_self < len(ib)) & (out["poly"].astype(np.int64) == cb + j_self)
-        for q in np.flatnonzero(own):
-            out[q] = ref.reduce(Db[ia[q]:ia[q] + 1], bad_a[ia[q]:ia[q] + 1], bad_b, row_base=rb + int(q), col_base=cb, flags=flags)[0]
-    return out
-
-
-def assert_same(got, want, what):
-    ok = ref.same(got, want)
-    if not ok.all():
-        q = int(np.flatnonzero(~ok)[0])
-        raise AssertionError(f"{what}: {int((~ok).sum())} of {len(want)} records differ; first at {q}: got {got[q]}, want {want[q]}")
+    return best.reduce_by_query(ref, D, ia, ib, bad_a, bad_b, **kw)
 
 
 @functools.lru_cache(maxsize=None)

@@ -3,6 +3,7 @@ the contract of include/c2d.h, pinned by tests/test_ray_ref_cpu.py — t and u b
 the engine's own N x M polygon test on the segments as 2-gons.  Every output buffer handed to the library sits between guard bands
 that are checked afterwards."""
 import ctypes as C
+import functools
 import importlib.util
 import os
 import subprocess
@@ -13,6 +14,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import best_key_harness  # noqa: E402
 import contact_cases  # noqa: E402
 import ray_cases as cases  # noqa: E402
 import ray_ref as ref  # noqa: E402
@@ -41,11 +43,7 @@ def long_scene(wl):
     return rays, b, want
 
 
-def twice(eng, rays, n_rays, b_set, what, **kw):
-    """the call, run twice: the two outputs must be the same bytes"""
-    got, again = cast(eng, rays, n_rays, b_set, **kw), cast(eng, rays, n_rays, b_set, **kw)
-    assert got.tobytes() == again.tobytes(), f"{what}: two runs differ"
-    return got
+twice = functools.partial(best_key_harness.twice, cast)  # twice(eng, rays, n_rays, b_set, what, **kw): the call, run twice: the same bytes
 
 
 def test_every_number_of_rays(eng, long_scene):

@@ -3,6 +3,7 @@ numpy restatement of the contract of include/c2d.h, pinned by tests/test_ray_gri
 on the project's scenes the records also equal c2d_poly_ray_casts' byte for byte, in the same run.  Every output buffer handed to the
 library sits between guard bands that are checked afterwards (tests/ray_harness.py, tests/pair_list_harness.py)."""
 import ctypes as C
+import functools
 import importlib.util
 import os
 import subprocess
@@ -13,6 +14,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import best_key_harness  # noqa: E402
 import pair_list_harness as h  # noqa: E402
 import ray_cases as cases  # noqa: E402
 import ray_grid_cases as gcases  # noqa: E402
@@ -34,11 +36,7 @@ def cast_grid(eng, rays, n_rays, b_set, col_base=0, capacity=None, expect_error=
     return h.banded_call(eng, DT, n_rays, lambda ptr: eng.poly_ray_casts_grid(rays.ptrs, n_rays, b_set, ptr, col_base=col_base), capacity, expect_error)
 
 
-def twice(eng, rays, n_rays, b_set, what, **kw):
-    """the call, run twice: the two outputs must be the same bytes"""
-    got, again = cast_grid(eng, rays, n_rays, b_set, **kw), cast_grid(eng, rays, n_rays, b_set, **kw)
-    assert got.tobytes() == again.tobytes(), f"{what}: two runs differ"
-    return got
+twice = functools.partial(best_key_harness.twice, cast_grid)  # twice(eng, rays, n_rays, b_set, what, **kw): the call, run twice: the same bytes
 
 
 def check(eng, rays, b, what, n_rays=None, uploaded=None, on_device=None, **kw):
