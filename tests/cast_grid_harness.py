@@ -14,6 +14,7 @@ import cast_harness as ch
 import cast_ref as ref
 import clearance_grid_harness as gh
 import pair_list_harness as h
+import pair_search_harness as psh
 import sweep_broad_harness as sh
 import sweep_broad_ref
 import sweep_ref as sref
@@ -212,4 +213,4 @@ def wild_scene(wl, n_a=257, n_b=230):
     mb[0][51], mb[1][51] = F32(-1e6), F32(1e6)
     a[0][1, 70], a[1][0, 71], b[0][2, 72], b[1][1, 73] = np.nan, np.inf, -np.inf, np.nan      # NaN and inf vertices
     a[2][[60, 61, 62]], b[2][[63, 64, 65]] = [0, 17, 255], [0, 13, 200]   # counts 0 and rows + 1
-    return sh.nan_padded(a), sh.nan_padded(b), ma, mb
+    return psh.nan_padded(a), psh.nan_padded(b), ma, mb

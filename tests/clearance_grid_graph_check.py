@@ -1,5 +1,5 @@
 """Graph-capture check of c2d_poly_set_clearances_grid, run as a separate process by tests/test_gpu_clearances_grid.py, after
-tests/near_broad_graph_check.py.
+tests/pair_search_graph_check.py.
 
 torch must be imported before libc2d.so in a process that uses both (tests/graph_capture_check.py says why).  A capture on a
 fresh ctx must be refused before it enqueues anything (the ctx scratch would have to grow).  After one eager call of the same

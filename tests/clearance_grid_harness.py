@@ -11,6 +11,7 @@ import clearance_grid_ref as ref
 import near_broad_harness as nh
 import near_broad_ref as nref
 import pair_list_harness as h
+import pair_search_harness as psh
 
 DT = ref.CLEARANCE_DT
 F32 = np.float32
@@ -19,7 +20,6 @@ SIZES = [1, 63, 64, 65, 257, 1031]
 FORMS = ["two_sets", "self_skip", "mixed_layouts"]
 MARGIN_NAMES = ["zero", "below_median", "median", "all"]
 REACH = 3.0 * nh.SIZE          # the judge looks this far for the scenes' nearest neighbours
-Set = nh.Set
 
 
 # ---- the device side ----------------------------------------------------------------------------------------------------------
@@ -46,8 +46,8 @@ def check(eng, a, b, max_dist, what, want=None, place_a=(1, 3), place_b=(2, 0), 
     """a against b (b None: the set against itself, the same memory) through the call, twice (the same bytes), against the judge;
     where the judge says that every query has a winner (or all_winners is True), also against c2d_poly_set_clearances on the GPU,
     byte for byte.  Returns (records, the judge's)."""
-    A = Set(eng, a, None, offset=place_a[0], stride=a[0].shape[1] + place_a[1], with_k=with_k)
-    B = A if b is None else Set(eng, b, None, offset=place_b[0], stride=b[0].shape[1] + place_b[1], with_k=with_k)
+    A = psh.DeviceSet(eng, a, offset=place_a[0], stride=a[0].shape[1] + place_a[1], with_k=with_k)
+    B = A if b is None else psh.DeviceSet(eng, b, offset=place_b[0], stride=b[0].shape[1] + place_b[1], with_k=with_k)
     n_a = a[0].shape[1]
     try:
         got = call(eng, A.set, B.set, n_a, max_dist, expect_error=expect_error, **kw)
@@ -73,15 +73,15 @@ def check(eng, a, b, max_dist, what, want=None, place_a=(1, 3), place_b=(2, 0), 
 def scene_of(wl, n, form, shift=0):
     """(a, b, kw): the scene of test_gpu_near_broad.py for (n, form) at half its density, so that a good share of the queries touch
     nothing; b None: the set against itself under SKIP_SELF.  shift: another draw of the same scene"""
-    a = nh.sparse_scene(wl, n, 1000 + n + 100 * shift, density=0.5)
-    b = nh.sparse_scene(wl, n // 2 + 37, 2000 + n, density=0.5)
+    a = psh.sparse_set(wl, n, 1000 + n + 100 * shift, density=0.5)
+    b = psh.sparse_set(wl, n // 2 + 37, 2000 + n, density=0.5)
     kw = {}
     if form == "self_skip":
         b, kw = None, dict(flags=ref.SKIP_SELF, row_base=5, col_base=5)
     elif form == "mixed_layouts":                       # rows 4 without a count plane against rows 8 with one, other strides and offsets
         full = wl.random_convex_polygon_set(n, seed=3000 + n + 100 * shift, kmin=4, kmax=4, extent=400.0 * np.sqrt(max(n, 64) / 32768), rows=4)
         a = (full[0], full[1], None)
-        b = nh.sparse_scene(wl, n // 2 + 37, 2000 + n, rows=8, kmax=8, density=0.5)
+        b = psh.sparse_set(wl, n // 2 + 37, 2000 + n, rows=8, kmax=8, density=0.5)
     return a, b, kw
 
 

@@ -1,23 +1,14 @@
-"""What the tests of c2d_poly_near_broad_pairs share (test_gpu_near_broad.py, tools/near_broad_fuzz.py): the list call between guard
-entries, the judge that compares a list with the reference (tests/near_broad_ref.py), and the scenes.  The device-side set (row
-offset, stride, gaps of NaN) and the list comparison are tests/sweep_broad_harness.py's: a set at rest is a MovingSet without motion
-planes.  The judge and the scenes are numpy only, so the CPU tests can reach them."""
+"""What belongs to c2d_poly_near_broad_pairs alone in its tests (test_gpu_near_broad.py, tools/near_broad_fuzz.py, the grid clearances'
+tests): the size of a scene polygon, the exact grid squares, the wild scene, and check() against the reference
+(tests/near_broad_ref.py).  The device set, the list call between guard entries and the judge are tests/pair_search_harness.py's.
+numpy only."""
 import numpy as np
 
 import near_broad_ref as ref
-import sweep_broad_harness as sh
+import pair_search_harness as psh
 
 F32 = np.float32
-SENTINEL = sh.SENTINEL
-Set = sh.MovingSet
-compare = sh.compare
-nan_padded = sh.nan_padded
-SIZE = 2.5                     # a polygon of the sparse scenes is about this far across
-
-
-def sparse_scene(wl, n, seed, rows=16, kmax=16, density=1.0):
-    """the sparse scene of the polygon broad phase's tests"""
-    return sh.sparse_scene(wl, n, seed, rows=rows, kmax=kmax, density=density)[0]
+SIZE = 2.5                     # a polygon of the sparse scenes (pair_search_harness.sparse_set) is about this far across
 
 
 def grid_boxes(offsets, step=1.0 / 64):
@@ -38,41 +29,38 @@ def grid_boxes(offsets, step=1.0 / 64):
     return (ax, ay, k), (bx, by, k.copy())
 
 
-def run(eng, A, B, max_dist, upper=False, capacity=None, stream=0, absent=False):
-    """(pairs u32[capacity][2], total) of c2d_poly_near_broad_pairs on the Sets A, B; capacity None: count first, then exact.  The list
-    sits between four guard entries in front and four (plus everything past the capacity) behind, which are checked.  absent: the sets
-    hold a vertex count out of range, which every call must report."""
-    d_cnt = eng.zeros(1, np.uint64)
-    if capacity is None:
-        eng.poly_near_broad_pairs(A.set, B.set, max_dist, None, 0, d_cnt, upper=upper, stream=stream)
-        sh._synchronize(eng, absent)
-        capacity = int(d_cnt.get()[0])
-        eng.memset(d_cnt, 0, 8)
-    d_pairs = eng.empty((capacity + 8, 2), np.uint32)
-    eng.memset(d_pairs, 0xA5, d_pairs.nbytes)
-    eng.poly_near_broad_pairs(A.set, B.set, max_dist, d_pairs.ptr + 32, capacity, d_cnt, upper=upper, stream=stream)
-    sh._synchronize(eng, absent)
-    p, c = d_pairs.get(), int(d_cnt.get()[0])
-    d_pairs.free()
-    d_cnt.free()
-    assert (p[:4].view(np.uint64) == SENTINEL).all(), "written in front of the list"
-    assert (p[4 + capacity:].view(np.uint64) == SENTINEL).all(), "written past the capacity"
-    return p[4:4 + capacity], c
+def wild_scene(wl):
+    """(a, b): a sparse scene with non-finite and huge coordinates, tiny and huge polygons, points, segments and absent polygons"""
+    n = 900
+    a = psh.sparse_set(wl, n, 5001, density=2.0)
+    b = psh.sparse_set(wl, n - 150, 5002, rows=12, kmax=12, density=2.0)
+    a, b = tuple(np.array(x) for x in a), tuple(np.array(x) for x in b)
+    a[0][1, 10], a[1][0, 11], b[0][2, 20], b[1][1, 21] = np.nan, np.inf, -np.inf, np.nan            # non-finite live vertices
+    a[0][:, 30] = a[0][:, 30] * F32(2.0 ** 50) + F32(2.0 ** 60)                                      # coordinates at 2^60
+    a[1][:, 30] = a[1][:, 30] * F32(2.0 ** 50)
+    b[0][:, 31] = b[0][:, 31] + F32(-2.0 ** 59.9)                                                    # just below: regular, huge box
+    a[0][:, 32], a[1][:, 32] = a[0][:, 32] * F32(2.0 ** -110), a[1][:, 32] * F32(2.0 ** -110)       # below 2^-100, at the origin
+    b[0][:, 33], b[1][:, 33] = b[0][:, 33] * F32(2.0 ** -110), b[1][:, 33] * F32(2.0 ** -110)
+    b[0][:, 34], b[1][:, 34] = b[0][:, 34] * F32(2.0 ** -140), b[1][:, 34] * F32(2.0 ** -140)       # subnormal
+    a[2][[40, 41, 42]], b[2][[43, 44, 45]] = [1, 2, 2], [1, 1, 2]                                    # points and segments
+    a[0][:, 50], a[1][:, 50] = (a[0][:, 50] - np.nanmean(a[0][:, 50])) * F32(20.0), (a[1][:, 50] - np.nanmean(a[1][:, 50])) * F32(20.0)   # a huge polygon over the scene
+    a[2][[60, 61, 62]], b[2][[63, 64, 65]] = [0, 17, 255], [0, 13, 200]                              # counts 0 and rows + 1
+    return psh.nan_padded(a), psh.nan_padded(b)
 
 
 def check(eng, a, b, max_dist, upper=False, min_pairs=1, want=None, place_a=(1, 3), place_b=(2, 0), with_k=True, far_cache=None):
     """the list of a against b — b None: the set against itself, the same memory — equals the reference; returns (list, reference)"""
-    A = Set(eng, a, None, offset=place_a[0], stride=a[0].shape[1] + place_a[1], with_k=with_k)
-    B = A if b is None else Set(eng, b, None, offset=place_b[0], stride=b[0].shape[1] + place_b[1], with_k=with_k)
+    A = psh.DeviceSet(eng, a, offset=place_a[0], stride=a[0].shape[1] + place_a[1], with_k=with_k)
+    B = A if b is None else psh.DeviceSet(eng, b, offset=place_b[0], stride=b[0].shape[1] + place_b[1], with_k=with_k)
     try:
-        got, total = run(eng, A, B, max_dist, upper)
+        got, total = psh.run(eng, psh.near_broad(eng, A, B, max_dist, upper))
     finally:
         A.free()
         if B is not A:
             B.free()
     if want is None:
         want = ref.pairs(a, a if b is None else b, max_dist, upper=upper, far_cache=far_cache)
-    why = compare(got, total, want)
+    why = psh.compare(got, total, want)
     assert why is None, why
     assert total >= min_pairs, total
     return got, want

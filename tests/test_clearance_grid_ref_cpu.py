@@ -10,8 +10,8 @@ import clearance_grid_harness as gh
 import clearance_grid_ref as ref
 import clearance_harness as ch
 import clearance_ref as cref
-import near_broad_harness as nh
 import near_broad_ref as nref
+import pair_search_harness as psh
 
 F32 = np.float32
 NO_POLY = 0xFFFFFFFF
@@ -44,7 +44,7 @@ def direct(a, b, max_dist, row_base=0, col_base=0, flags=0):
 
 @pytest.mark.parametrize("n_a,n_b", [(1, 37), (17, 5), (64, 64), (40, 0)])
 def test_the_route_equals_the_direct_one(wl, n_a, n_b):
-    a, b = nh.sparse_scene(wl, n_a, 31 + n_a, density=0.6), nh.sparse_scene(wl, max(n_b, 1), 57 + n_b, rows=9, kmax=9, density=0.6)
+    a, b = psh.sparse_set(wl, n_a, 31 + n_a, density=0.6), psh.sparse_set(wl, max(n_b, 1), 57 + n_b, rows=9, kmax=9, density=0.6)
     b = tuple(None if x is None else np.ascontiguousarray(x[..., :n_b]) for x in b)
     if n_a > 8:
         k = a[2].copy()

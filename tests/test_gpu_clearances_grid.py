@@ -18,7 +18,7 @@ import clearance_grid_ref as ref
 import clearance_harness as ch
 import near_broad_harness as nh
 import near_threshold_cases as ntc
-import test_gpu_near_broad as tnb
+import pair_search_harness as psh
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -111,7 +111,7 @@ def test_hits_and_underflowed_distances_tie_at_zero(eng):
         bad = bool(ref.cref.bad_counts(a).any() or (b[0].shape[1] and ref.cref.bad_counts(b).any()))
         for r in (2000.0, 1.0, 0.0):
             if b[0].shape[1] == 0:
-                A = gh.Set(eng, a, None)
+                A = psh.DeviceSet(eng, a)
                 got = gh.call(eng, A.set, eng.poly_set(A.px, A.py, None, 0, 16, 0), a[0].shape[1], r, **kw)
                 gh.assert_same(got, ref.clearances(a, b, r, **kw), name)
                 A.free()
@@ -159,8 +159,8 @@ def test_exact_grid_cut(eng):
 
 def test_monotone_in_the_margin(eng, wl):
     """raising max_dist only turns NONE records into winners and never changes an existing winner: checked between the calls"""
-    a, b = nh.sparse_scene(wl, 900, 4301, density=0.7), nh.sparse_scene(wl, 700, 4302, density=0.7)
-    A, B = gh.Set(eng, a, None, offset=1), gh.Set(eng, b, None)
+    a, b = psh.sparse_set(wl, 900, 4301, density=0.7), psh.sparse_set(wl, 700, 4302, density=0.7)
+    A, B = psh.DeviceSet(eng, a, offset=1), psh.DeviceSet(eng, b)
     try:
         last = None
         for r in (0.0, 0.2, 0.4, 0.9, 1.7, 4.0, 9.0):
@@ -207,19 +207,19 @@ def test_path_switches_at_the_candidate_cap(eng, covers):
 def test_wide_boxes_all_wild_sets(eng, wl):
     """a polygon whose margin box spans more than two cells (as a query and as an obstacle), an all-wild B (points and segments) and
     an A of wild queries"""
-    a = tuple(np.array(x) for x in nh.sparse_scene(wl, 200, 5101, density=0.7))
-    b = tuple(np.array(x) for x in nh.sparse_scene(wl, 150, 5102, density=0.7))
+    a = tuple(np.array(x) for x in psh.sparse_set(wl, 200, 5101, density=0.7))
+    b = tuple(np.array(x) for x in psh.sparse_set(wl, 150, 5102, density=0.7))
     for s, q in ((a, 50), (b, 60)):
         s[0][:, q], s[1][:, q] = (s[0][:, q] - np.nanmean(s[0][:, q])) * F32(12.0), (s[1][:, q] - np.nanmean(s[1][:, q])) * F32(12.0)
-    a, b = nh.nan_padded(a), nh.nan_padded(b)
+    a, b = psh.nan_padded(a), psh.nan_padded(b)
     for r in (0.0, 0.8, 6.0):
         got, want = gh.check(eng, a, b, r, f"wide boxes, margin {r}")
         assert got["hit"][50] == 1
     low = lambda s: (s[0], s[1], np.where(np.arange(s[0].shape[1]) % 2, 1, 2).astype(np.uint8))      # noqa: E731
     for r in (0.0, 1.5):
-        got, _ = gh.check(eng, a, nh.nan_padded(low(b)), r, f"all-wild B, margin {r}")
+        got, _ = gh.check(eng, a, psh.nan_padded(low(b)), r, f"all-wild B, margin {r}")
         assert r == 0.0 or (got["poly"] != NO_POLY).sum() > 20
-        got, _ = gh.check(eng, nh.nan_padded(low(a)), b, r, f"wild queries, margin {r}")
+        got, _ = gh.check(eng, psh.nan_padded(low(a)), b, r, f"wild queries, margin {r}")
         assert r == 0.0 or (got["poly"] != NO_POLY).sum() > 20
     eng.check_async()
 
@@ -229,7 +229,7 @@ def test_wide_boxes_all_wild_sets(eng, wl):
 def test_wild_and_absent(eng, wl, max_dist):
     """test_gpu_near_broad.py's wild scene: points and segments, NaN and infinite vertices, coordinates at 2^60 and below 2^-100, a
     huge polygon, counts of 0 and rows + 1 as queries and as obstacles; the asynchronous error is reported once per call"""
-    a, b = tnb.wild_scene(wl)
+    a, b = nh.wild_scene(wl)
     got, want = gh.check(eng, a, b, max_dist, f"wild scene, margin {max_dist}", expect_error=True, place_a=(1, 3))
     assert (got["flags"][[60, 61, 62]] == 8).all() and (got["poly"][[60, 61, 62]] == NO_POLY).all(), "a bad query gets the BAD_PAIR record"
     assert not np.isin(got["poly"], [63, 64, 65]).any(), "an absent obstacle is never the winner"
@@ -240,9 +240,9 @@ def test_wild_and_absent(eng, wl, max_dist):
 
 # ---- bases, shards and edges ----------------------------------------------------------------------------------------------------
 def test_bases_shards_and_edges(eng, wl):
-    a = nh.sparse_scene(wl, 300, 6101, density=0.7)
+    a = psh.sparse_set(wl, 300, 6101, density=0.7)
     n = 300
-    A = gh.Set(eng, a, None, offset=1, stride=307)
+    A = psh.DeviceSet(eng, a, offset=1, stride=307)
     try:
         r = 1.0
         got = gh.call(eng, A.set, A.set, n, r, flags=ref.SKIP_SELF)
@@ -277,8 +277,8 @@ def test_bases_shards_and_edges(eng, wl):
 def test_the_counters(eng, wl):
     """c2d_poly_set_clearances_grid_stats: refused on a ctx whose scratch holds another call's header; after a call the bound has
     skipped candidate walks, and a best at distance 0 pairwise tests"""
-    a, b = nh.sparse_scene(wl, 2000, 8101), nh.sparse_scene(wl, 2000, 8102)
-    A, B = gh.Set(eng, a, None), gh.Set(eng, b, None)
+    a, b = psh.sparse_set(wl, 2000, 8101), psh.sparse_set(wl, 2000, 8102)
+    A, B = psh.DeviceSet(eng, a), psh.DeviceSet(eng, b)
     try:
         d_cnt = eng.zeros(1, np.uint64)
         eng.poly_near_broad_pairs(A.set, B.set, 1.0, None, 0, d_cnt)
@@ -299,8 +299,8 @@ def test_the_counters(eng, wl):
 
 def test_same_memory_detection(eng, wl):
     """one set against itself as the same memory (boxes and sort made once) and as a second copy: the same records"""
-    a = nh.sparse_scene(wl, 1000, 8001, density=0.7)
-    A, A2 = gh.Set(eng, a, None, offset=1), gh.Set(eng, a, None, offset=2, stride=1007)
+    a = psh.sparse_set(wl, 1000, 8001, density=0.7)
+    A, A2 = psh.DeviceSet(eng, a, offset=1), psh.DeviceSet(eng, a, offset=2, stride=1007)
     try:
         want = ref.clearances(a, a, 0.6, flags=ref.SKIP_SELF)
         one = gh.call(eng, A.set, A.set, 1000, 0.6, flags=ref.SKIP_SELF)
@@ -316,7 +316,7 @@ def test_same_memory_detection(eng, wl):
 
 def test_argument_errors(eng, pkg, wl):
     a = wl.random_convex_polygon_set(100, seed=5, extent=3.0)
-    A = gh.Set(eng, a, None)
+    A = psh.DeviceSet(eng, a)
     d = eng.empty(104, pkg.CLEARANCE_DT)
     eng.memset(d, 0xA5, d.nbytes)
     S = A.set
@@ -371,8 +371,8 @@ def test_fused_validation_builds_match_their_own_distances(pkg, wl, k):
     fe = pkg.Engine(0, lib_path=os.path.join(PKG_DIR, "lib", f"libc2d_fmad{k}.so"))
     try:
         n = 257
-        a, b = nh.sparse_scene(wl, n, 9001, density=0.5), nh.sparse_scene(wl, n, 9002, density=0.5)
-        A, B = gh.Set(fe, a, None, offset=1), gh.Set(fe, b, None)
+        a, b = psh.sparse_set(wl, n, 9001, density=0.5), psh.sparse_set(wl, n, 9002, density=0.5)
+        A, B = psh.DeviceSet(fe, a, offset=1), psh.DeviceSet(fe, b)
         allp = np.stack([np.repeat(np.arange(n), n), np.tile(np.arange(n), n)], axis=1).astype(np.uint32)
         d_all = fe.to_device(allp)
         for flags, Y in ((0, B), (ref.SKIP_SELF, A)):

@@ -13,6 +13,7 @@ import pytest
 
 import distance_ref
 import near_broad_harness as nh
+import pair_search_harness as psh
 import near_broad_ref as ref
 import near_threshold_cases as ntc
 import test_near_broad_margin_cpu as margin
@@ -26,20 +27,6 @@ MARGINS = {"zero": 0.0, "tenth": 0.1 * nh.SIZE, "one": nh.SIZE, "ten": 10 * nh.S
 # (at ten sizes the list grows with n^2, to a million pairs at n = 4099: the judge's bounds, tests/near_broad_ref.py, keep that to seconds)
 CASES = [(n, m) for n in SIZES for m in MARGINS]
 _FAR = {}            # the judge's first-axis matrices of a scene, shared by the cases that differ in the margin only
-
-
-def static_broad(eng, A, B, upper=False):
-    """the list of c2d_sat_poly_broad_pairs on the same sets"""
-    d_cnt = eng.zeros(1, np.uint64)
-    eng.sat_poly_broad_pairs(A.set, B.set, None, 0, d_cnt, upper=upper)
-    total = int(d_cnt.get()[0])
-    eng.memset(d_cnt, 0, 8)
-    d_pairs = eng.zeros((total + 1, 2), np.uint32)
-    eng.sat_poly_broad_pairs(A.set, B.set, d_pairs, total, d_cnt, upper=upper)
-    out = d_pairs.get()[:total]
-    d_pairs.free()
-    d_cnt.free()
-    return out
 
 
 def chained_distances(eng, pkg, A, B, max_dist, cap, upper=False):
@@ -66,14 +53,14 @@ def as_set(p):
 
 
 def scene_of(wl, n, form):
-    a = nh.sparse_scene(wl, n, 1000 + n)
-    b = nh.sparse_scene(wl, n // 2 + 37, 2000 + n)
+    a = psh.sparse_set(wl, n, 1000 + n)
+    b = psh.sparse_set(wl, n // 2 + 37, 2000 + n)
     if form == "self_upper":
         b = None
     elif form == "mixed_layouts":                       # rows 4 without a count plane against rows 8 with one, other strides and offsets
         full = wl.random_convex_polygon_set(n, seed=3000 + n, kmin=4, kmax=4, extent=200.0 * np.sqrt(max(n, 64) / 32768), rows=4)
         a = (full[0], full[1], None)
-        b = nh.sparse_scene(wl, n // 2 + 37, 2000 + n, rows=8, kmax=8)
+        b = psh.sparse_set(wl, n // 2 + 37, 2000 + n, rows=8, kmax=8)
     return a, b
 
 
@@ -86,18 +73,18 @@ def test_random_sparse_scenes(eng, pkg, wl, n, form, margin_name):
     a, b = scene_of(wl, n, form)
     upper = form == "self_upper"
     mixed = form == "mixed_layouts"
-    A = nh.Set(eng, a, None, offset=3 if mixed else 1, stride=n + (11 if mixed else 3), with_k=a[2] is not None)
-    B = A if b is None else nh.Set(eng, b, None, offset=2, stride=b[0].shape[1] + (5 if mixed else 0))
+    A = psh.DeviceSet(eng, a, offset=3 if mixed else 1, stride=n + (11 if mixed else 3), with_k=a[2] is not None)
+    B = A if b is None else psh.DeviceSet(eng, b, offset=2, stride=b[0].shape[1] + (5 if mixed else 0))
     try:
-        got, total = nh.run(eng, A, B, r, upper)
-        static = static_broad(eng, A, B, upper)
+        got, total = psh.run(eng, psh.near_broad(eng, A, B, r, upper))
+        static = psh.static_broad(eng, A, B, upper)
         pairs, rec = chained_distances(eng, pkg, A, B, r, total + 3, upper)
     finally:
         A.free()
         if B is not A:
             B.free()
     want = ref.pairs(a, a if b is None else b, r, upper=upper, far_cache=_FAR.setdefault((n, form), {}))
-    why = nh.compare(got, total, want)
+    why = psh.compare(got, total, want)
     assert why is None, why
     assert np.array_equal(pairs, got)
     assert ((rec["hit"] == 1) | (rec["dist"] <= F32(r))).all()
@@ -141,14 +128,14 @@ def test_near_touching(eng, scale):
 
 
 def test_monotone_in_the_margin(eng, wl):
-    a, b = nh.sparse_scene(wl, 900, 4301, density=2.0), nh.sparse_scene(wl, 700, 4302, density=2.0)
-    A, B = nh.Set(eng, a, None, offset=1), nh.Set(eng, b, None)
+    a, b = psh.sparse_set(wl, 900, 4301, density=2.0), psh.sparse_set(wl, 700, 4302, density=2.0)
+    A, B = psh.DeviceSet(eng, a, offset=1), psh.DeviceSet(eng, b)
     try:
-        last = as_set(static_broad(eng, A, B))
+        last = as_set(psh.static_broad(eng, A, B))
         assert len(last) > 50
         for r in (0.0, 0.4, 1.7):
-            got, total = nh.run(eng, A, B, r)
-            assert nh.compare(got, total, ref.pairs(a, b, r)) is None
+            got, total = psh.run(eng, psh.near_broad(eng, A, B, r))
+            assert psh.compare(got, total, ref.pairs(a, b, r)) is None
             assert last <= as_set(got), r
             assert r == 0.0 or len(got) > len(last) + 50
             last = as_set(got)
@@ -165,15 +152,15 @@ def test_path_switches_through_the_margin(eng, covers):
     a, b, info = ntc.near_station_scene(covers=covers)
     got, want = nh.check(eng, a, b, ntc.MARGIN, min_pairs=3000)
     assert np.array_equal(np.bincount(got[:, 0], minlength=len(info["h"])), info["h"] + covers)
-    A, B = nh.Set(eng, a, None), nh.Set(eng, b, None)
+    A, B = psh.DeviceSet(eng, a), psh.DeviceSet(eng, b)
     try:
-        assert len(static_broad(eng, A, B)) == covers * len(info["h"])
+        assert len(psh.static_broad(eng, A, B)) == covers * len(info["h"])
         starts = np.concatenate([[0], np.cumsum(info["h"] + covers)])
         for s in (4, 5, 10, 13, len(info["h"]) - 1):          # inside a short row, a wave-path row, rows above 512 pairs and over the cap
             if starts[s + 1] - starts[s] < 2:
                 continue
             cap = int(starts[s] + (starts[s + 1] - starts[s]) // 2)
-            part, total = nh.run(eng, A, B, ntc.MARGIN, capacity=cap)
+            part, total = psh.run(eng, psh.near_broad(eng, A, B, ntc.MARGIN), capacity=cap)
             assert total == len(want) and np.array_equal(part, want[:cap]), s
     finally:
         A.free()
@@ -181,39 +168,21 @@ def test_path_switches_through_the_margin(eng, covers):
     eng.check_async()
 
 
-def wild_scene(wl):
-    n = 900
-    a = nh.sparse_scene(wl, n, 5001, density=2.0)
-    b = nh.sparse_scene(wl, n - 150, 5002, rows=12, kmax=12, density=2.0)
-    a, b = tuple(np.array(x) for x in a), tuple(np.array(x) for x in b)
-    a[0][1, 10], a[1][0, 11], b[0][2, 20], b[1][1, 21] = np.nan, np.inf, -np.inf, np.nan            # non-finite live vertices
-    a[0][:, 30] = a[0][:, 30] * F32(2.0 ** 50) + F32(2.0 ** 60)                                      # coordinates at 2^60
-    a[1][:, 30] = a[1][:, 30] * F32(2.0 ** 50)
-    b[0][:, 31] = b[0][:, 31] + F32(-2.0 ** 59.9)                                                    # just below: regular, huge box
-    a[0][:, 32], a[1][:, 32] = a[0][:, 32] * F32(2.0 ** -110), a[1][:, 32] * F32(2.0 ** -110)       # below 2^-100, at the origin
-    b[0][:, 33], b[1][:, 33] = b[0][:, 33] * F32(2.0 ** -110), b[1][:, 33] * F32(2.0 ** -110)
-    b[0][:, 34], b[1][:, 34] = b[0][:, 34] * F32(2.0 ** -140), b[1][:, 34] * F32(2.0 ** -140)       # subnormal
-    a[2][[40, 41, 42]], b[2][[43, 44, 45]] = [1, 2, 2], [1, 1, 2]                                    # points and segments
-    a[0][:, 50], a[1][:, 50] = (a[0][:, 50] - np.nanmean(a[0][:, 50])) * F32(20.0), (a[1][:, 50] - np.nanmean(a[1][:, 50])) * F32(20.0)   # a huge polygon over the scene
-    a[2][[60, 61, 62]], b[2][[63, 64, 65]] = [0, 17, 255], [0, 13, 200]                              # counts 0 and rows + 1
-    return nh.nan_padded(a), nh.nan_padded(b)
-
-
 @pytest.mark.parametrize("max_dist", [0.0, 1.5])
 def test_wild_and_absent(eng, wl, max_dist):
-    a, b = wild_scene(wl)
+    a, b = nh.wild_scene(wl)
     want = ref.pairs(a, b, max_dist)
-    A, B = nh.Set(eng, a, None, offset=1, stride=903), nh.Set(eng, b, None)
+    A, B = psh.DeviceSet(eng, a, offset=1, stride=903), psh.DeviceSet(eng, b)
     try:
-        got, total = nh.run(eng, A, B, max_dist, absent=True)     # (each call's synchronise reports the counts, once)
+        got, total = psh.run(eng, psh.near_broad(eng, A, B, max_dist), absent=True)     # (each call's synchronise reports the counts, once)
         eng.check_async()
-        why = nh.compare(got, total, want)
+        why = psh.compare(got, total, want)
         assert why is None, why
         rows = np.bincount(got[:, 0], minlength=900)
         assert rows[[60, 61, 62]].sum() == 0 and not np.isin(got[:, 1], [63, 64, 65]).any(), "an absent polygon is in no pair"
         assert rows[50] > 20, "the huge polygon covers the scene"
-        gu, tu = nh.run(eng, A, A, max_dist, upper=True, absent=True)
-        why = nh.compare(gu, tu, ref.pairs(a, a, max_dist, upper=True))
+        gu, tu = psh.run(eng, psh.near_broad(eng, A, A, max_dist, True), absent=True)
+        why = psh.compare(gu, tu, ref.pairs(a, a, max_dist, upper=True))
         assert why is None, why
     finally:
         A.free()
@@ -222,14 +191,14 @@ def test_wild_and_absent(eng, wl, max_dist):
 
 
 def test_capacity_count_and_determinism(eng, wl):
-    a, b = nh.sparse_scene(wl, 1500, 6001, density=2.0), nh.sparse_scene(wl, 1201, 6002, density=2.0)
+    a, b = psh.sparse_set(wl, 1500, 6001, density=2.0), psh.sparse_set(wl, 1201, 6002, density=2.0)
     r = 0.8
-    A, B = nh.Set(eng, a, None, offset=1), nh.Set(eng, b, None, stride=1208)
+    A, B = psh.DeviceSet(eng, a, offset=1), psh.DeviceSet(eng, b, stride=1208)
     try:
         for upper, Y, y in ((False, B, b), (True, A, a)):
             want = ref.pairs(a, y, r, upper=upper)
-            full, total = nh.run(eng, A, Y, r, upper)
-            assert total > 1500 and nh.compare(full, total, want) is None
+            full, total = psh.run(eng, psh.near_broad(eng, A, Y, r, upper))
+            assert total > 1500 and psh.compare(full, total, want) is None
             d_cnt = eng.zeros(1, np.uint64)             # capacity 0, no buffer: count only
             eng.poly_near_broad_pairs(A.set, Y.set, r, None, 0, d_cnt, upper=upper)
             assert int(d_cnt.get()[0]) == total
@@ -237,12 +206,12 @@ def test_capacity_count_and_determinism(eng, wl):
             assert int(d_cnt.get()[0]) == 2 * total, "d_count is incremented, not set"
             d_cnt.free()
             for cap in (1, total // 3 + 1, total - 1, total, total + 5):      # overflow: the total is reported, the first `cap` pairs written
-                p, c = nh.run(eng, A, Y, r, upper, capacity=cap)
+                p, c = psh.run(eng, psh.near_broad(eng, A, Y, r, upper), capacity=cap)
                 assert c == total and np.array_equal(p[:min(cap, total)], full[:cap])
                 if cap > total:
-                    assert (p[total:].view(np.uint64) == nh.SENTINEL).all(), "written past the total"
-            p1, _ = nh.run(eng, A, Y, r, upper, capacity=total // 2)
-            p2, _ = nh.run(eng, A, Y, r, upper, capacity=total // 2)
+                    assert (p[total:].view(np.uint64) == psh.SENTINEL).all(), "written past the total"
+            p1, _ = psh.run(eng, psh.near_broad(eng, A, Y, r, upper), capacity=total // 2)
+            p2, _ = psh.run(eng, psh.near_broad(eng, A, Y, r, upper), capacity=total // 2)
             assert p1.tobytes() == p2.tobytes()
         got = eng.poly_near_broad_pairs_host(*a, r, *b)
         assert got.dtype == np.uint32 and np.array_equal(got, ref.pairs(a, b, r))
@@ -257,9 +226,9 @@ def test_capacity_count_and_determinism(eng, wl):
 def test_chain_into_the_distances(eng, pkg, wl):
     """the list and its DEVICE count into c2d_poly_pair_distances on one stream with no synchronisation between: every record has
     hit == 1 || dist <= max_dist and equals distance_ref's, field by field; hit and separated pairs are both there"""
-    a, b = nh.sparse_scene(wl, 2000, 7001, density=2.0), nh.sparse_scene(wl, 1700, 7002, density=2.0)
+    a, b = psh.sparse_set(wl, 2000, 7001, density=2.0), psh.sparse_set(wl, 1700, 7002, density=2.0)
     r = 1.2
-    A, B = nh.Set(eng, a, None), nh.Set(eng, b, None)
+    A, B = psh.DeviceSet(eng, a), psh.DeviceSet(eng, b)
     try:
         pairs, rec = chained_distances(eng, pkg, A, B, r, 100_000)
         assert 4000 < len(pairs) < 100_000
@@ -267,7 +236,7 @@ def test_chain_into_the_distances(eng, pkg, wl):
         want = distance_ref.poly_distances(a, b, pairs[:, 0].astype(np.int64), pairs[:, 1].astype(np.int64))
         assert distance_ref.same(rec, want).all()
         assert 100 < (rec["hit"] == 1).sum() < len(pairs) - 100
-        assert np.array_equal(pairs[rec["hit"] == 1], static_broad(eng, A, B))
+        assert np.array_equal(pairs[rec["hit"] == 1], psh.static_broad(eng, A, B))
     finally:
         A.free()
         B.free()
@@ -276,7 +245,7 @@ def test_chain_into_the_distances(eng, pkg, wl):
 
 def test_argument_errors(eng, pkg, wl):
     a = wl.random_convex_polygon_set(100, seed=5, extent=3.0)
-    A = nh.Set(eng, a, None)
+    A = psh.DeviceSet(eng, a)
     d_pairs = eng.zeros((16, 2), np.uint32)
     d_cnt = eng.zeros(1, np.uint64)
     S = A.set
@@ -324,14 +293,14 @@ def test_argument_errors(eng, pkg, wl):
 
 def test_same_memory_detection(eng, wl):
     """one set against itself as the same memory (boxes and sort made once) and as a second copy (two sets): both equal the reference"""
-    a = nh.sparse_scene(wl, 1000, 8001, density=2.0)
-    A, A2 = nh.Set(eng, a, None, offset=1), nh.Set(eng, a, None, offset=2, stride=1007)
+    a = psh.sparse_set(wl, 1000, 8001, density=2.0)
+    A, A2 = psh.DeviceSet(eng, a, offset=1), psh.DeviceSet(eng, a, offset=2, stride=1007)
     try:
         for upper in (False, True):
             want = ref.pairs(a, a, 0.6, upper=upper)
             for Y in (A, A2):
-                got, total = nh.run(eng, A, Y, 0.6, upper)
-                why = nh.compare(got, total, want)
+                got, total = psh.run(eng, psh.near_broad(eng, A, Y, 0.6, upper))
+                why = psh.compare(got, total, want)
                 assert why is None, (upper, why)
                 assert total > 400
     finally:
@@ -346,10 +315,10 @@ def test_fused_validation_builds_match_their_own_distances(pkg, wl, k):
     fe = pkg.Engine(0, lib_path=os.path.join(PKG_DIR, "lib", f"libc2d_fmad{k}.so"))
     try:
         n, r = 257, 0.9
-        a, b = nh.sparse_scene(wl, n, 9001), nh.sparse_scene(wl, n, 9002)
-        A, B = nh.Set(fe, a, None, offset=1), nh.Set(fe, b, None)
+        a, b = psh.sparse_set(wl, n, 9001), psh.sparse_set(wl, n, 9002)
+        A, B = psh.DeviceSet(fe, a, offset=1), psh.DeviceSet(fe, b)
         for upper, Y in ((False, B), (True, A)):
-            got, total = nh.run(fe, A, Y, r, upper)
+            got, total = psh.run(fe, psh.near_broad(fe, A, Y, r, upper))
             allp = np.stack([np.repeat(np.arange(n), n), np.tile(np.arange(n), n)], axis=1).astype(np.uint32)
             d_all, d_rec = fe.to_device(allp), fe.empty(n * n, pkg.DISTANCE_DT)
             fe.poly_pair_distances(A.set, Y.set, d_all, n * n, d_rec)
@@ -383,7 +352,7 @@ def test_fuzz_at_a_fixed_seed(eng):
 
 def test_graph_capture():
     """replay after a warm-up equals the direct call, two-set and self; a capture that would have to grow the scratch is refused
-    (tests/near_broad_graph_check.py, its own process: torch has to be imported before libc2d.so)"""
-    out = subprocess.run([sys.executable, os.path.join(HERE, "near_broad_graph_check.py")], capture_output=True, text=True, timeout=300)
+    (tests/pair_search_graph_check.py, its own process: torch has to be imported before libc2d.so)"""
+    out = subprocess.run([sys.executable, os.path.join(HERE, "pair_search_graph_check.py"), "near_broad"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-1500:]
     assert "near broad graph ok" in out.stdout

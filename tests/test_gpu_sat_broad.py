@@ -10,10 +10,12 @@ import sys
 import numpy as np
 import pytest
 
+import pair_search_harness as psh
+from sat_cross_harness import rect_oracle_pairs
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_PAIRS = 3_000_000
-SENTINEL = np.uint64(0xA5A5A5A5A5A5A5A5)
 FUZZ_SEED = 2026
 
 
@@ -25,39 +27,6 @@ def planes_of(d):
     return [d.row(k) for k in range(8)]
 
 
-def run(eng, fn, pa, n_a, pb, n_b, upper, capacity=None):
-    """(pairs u32[k][2], total) of fn = sat_rect_cross_pairs / sat_rect_broad_pairs; capacity None: count first, then exact.
-    Checks that nothing past the capacity was written."""
-    def call(pairs, cap, cnt):
-        if fn == "cross":
-            eng.sat_rect_cross_pairs(pa, n_a, pb, n_b, pairs, cap, cnt, upper=upper)
-        else:
-            eng.sat_rect_broad_pairs(pa, n_a, pb, n_b, pairs, cap, cnt, upper=upper)
-
-    d_cnt = eng.zeros(1, np.uint64)
-    if capacity is None:
-        call(None, 0, d_cnt)
-        capacity = int(d_cnt.get()[0])
-        eng.memset(d_cnt, 0, 8)
-    d_pairs = eng.empty((capacity + 4, 2), np.uint32)
-    eng.memset(d_pairs, 0xA5, d_pairs.nbytes)
-    call(d_pairs, capacity, d_cnt)
-    p, c = d_pairs.get(), int(d_cnt.get()[0])
-    d_pairs.free()
-    d_cnt.free()
-    assert (p[capacity:].view(np.uint64) == SENTINEL).all(), f"{fn}: written past the capacity"
-    return p[:capacity], c
-
-
-def oracle_pairs(oracle, a, b, upper):
-    n_a, n_b = a.shape[1], b.shape[1]
-    res, _ = oracle.sat_rect_pairs_verts(np.concatenate([np.repeat(a, n_b, axis=1), np.tile(b, n_a)]))
-    m = res.reshape(n_a, n_b).astype(bool)
-    if upper:
-        m &= np.triu(np.ones((n_a, n_b), bool), 1)
-    return np.argwhere(m).astype(np.uint32)
-
-
 def check(eng, oracle, a, b=None, upper=False, min_pairs=0):
     """broad == cross (and == oracle below ORACLE_PAIRS) on a (self when b is None) against b; returns the list"""
     n_a = a.shape[1]
@@ -65,15 +34,9 @@ def check(eng, oracle, a, b=None, upper=False, min_pairs=0):
     db = da if b is None else eng.to_device(b)
     n_b = n_a if b is None else b.shape[1]
     pa, pb = planes_of(da), planes_of(db)
-    want, wc = run(eng, "cross", pa, n_a, pb, n_b, upper)
-    got, gc = run(eng, "broad", pa, n_a, pb, n_b, upper)
-    assert gc == wc and len(got) == wc, (gc, wc)
-    if not np.array_equal(got, want):
-        gs, ws = set(map(tuple, got.tolist())), set(map(tuple, want.tolist()))
-        raise AssertionError(f"lists differ: {len(ws - gs)} missing, e.g. {sorted(ws - gs)[:3]}, {len(gs - ws)} extra, "
-                             f"e.g. {sorted(gs - ws)[:3]}")
+    got, wc = psh.same_as(eng, psh.rect_broad(eng, pa, n_a, pb, n_b, upper), psh.rect_cross(eng, pa, n_a, pb, n_b, upper))
     if n_a * n_b <= ORACLE_PAIRS:
-        assert np.array_equal(got, oracle_pairs(oracle, a, a if b is None else b, upper))
+        assert np.array_equal(got, rect_oracle_pairs(oracle, a, a if b is None else b, upper))
     assert wc >= min_pairs, wc
     da.free()
     if b is not None:
@@ -220,7 +183,7 @@ def test_capacity_and_determinism(eng, oracle, wl):
     da, db = eng.to_device(a), eng.to_device(b)
     pa, pb = planes_of(da), planes_of(db)
     for upper in (False, True):
-        full, total = run(eng, "broad", pa, n, pb, 12_345, upper)
+        full, total = psh.run(eng, psh.rect_broad(eng, pa, n, pb, 12_345, upper))
         assert total > 10_000
         d_cnt = eng.zeros(1, np.uint64)             # capacity 0, no buffer: count only
         eng.sat_rect_broad_pairs(pa, n, pb, 12_345, None, 0, d_cnt, upper=upper)
@@ -229,15 +192,15 @@ def test_capacity_and_determinism(eng, oracle, wl):
         assert int(d_cnt.get()[0]) == 2 * total, "d_count is incremented, not set"
         d_cnt.free()
         for cap in (1, total // 3 + 1, total - 1):
-            p, c = run(eng, "broad", pa, n, pb, 12_345, upper, capacity=cap)
+            p, c = psh.run(eng, psh.rect_broad(eng, pa, n, pb, 12_345, upper), capacity=cap)
             assert c == total and np.array_equal(p, full[:cap])
-        p1, _ = run(eng, "broad", pa, n, pb, 12_345, upper, capacity=total // 2)
-        p2, _ = run(eng, "broad", pa, n, pb, 12_345, upper, capacity=total // 2)
+        p1, _ = psh.run(eng, psh.rect_broad(eng, pa, n, pb, 12_345, upper), capacity=total // 2)
+        p2, _ = psh.run(eng, psh.rect_broad(eng, pa, n, pb, 12_345, upper), capacity=total // 2)
         assert p1.tobytes() == p2.tobytes()
     got = eng.rect_broad_pairs_host(a, b)
-    assert np.array_equal(got, run(eng, "cross", pa, n, pb, 12_345, False)[0])
+    assert np.array_equal(got, psh.run(eng, psh.rect_cross(eng, pa, n, pb, 12_345))[0])
     got = eng.rect_broad_pairs_host(a, upper=True)
-    assert np.array_equal(got, run(eng, "cross", pa, n, pa, n, True)[0])
+    assert np.array_equal(got, psh.run(eng, psh.rect_cross(eng, pa, n, pa, n, True))[0])
     da.free()
     db.free()
 
@@ -271,8 +234,8 @@ def test_argument_errors(eng, pkg, oracle, wl):
 
 def test_graph_capture():
     """replay after a warm-up equals the direct call, two-set and self; a capture that would have to grow the scratch is refused
-    (tests/broad_graph_check.py, its own process: torch has to be imported before libc2d.so)"""
-    out = subprocess.run([sys.executable, os.path.join(HERE, "broad_graph_check.py")], capture_output=True, text=True, timeout=600)
+    (tests/pair_search_graph_check.py, its own process: torch has to be imported before libc2d.so)"""
+    out = subprocess.run([sys.executable, os.path.join(HERE, "pair_search_graph_check.py"), "rect_broad"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-1500:]
     assert "broad graph ok" in out.stdout
 

@@ -1,59 +1,51 @@
 """GPU tests of the broad-phase pair searches (c2d_sat_rect_broad_pairs, c2d_sat_poly_broad_pairs) with rows placed exactly on the
 emit routes' switches (csrc/c2d_broad.hpp: kShortHits 16, kMidHits 512, kCandidateCap 1024): the station scene of
 tests/threshold_cases.py, whose construction tests/test_threshold_cases_cpu.py proves on the oracle.  The tests cannot see which
-route emitted a row; the scene guarantees it.  Every list must equal the cross list of the same call bit for bit (run / check of
-test_gpu_sat_broad.py and test_gpu_sat_poly_broad.py: guard entries, count first, then the exact capacity), and the two-set call
-the oracle's list as well."""
+route emitted a row; the scene guarantees it.  Every list must equal the cross list of the same call bit for bit (run / compare of
+tests/pair_search_harness.py: guard entries, count first, then the exact capacity), and the two-set call the oracle's list as well."""
 import numpy as np
 import pytest
 
-import test_gpu_sat_broad as rect_tests
-import test_gpu_sat_poly_broad as poly_tests
+import pair_search_harness as psh
 import threshold_cases as tc
-from test_gpu_sat_poly_cross import Uploaded, reference
+from sat_cross_harness import rect_oracle_pairs, reference
 
 pytestmark = pytest.mark.gpu
 SHAPES = ["rect", "poly4", "poly16"]
 
 
-class Rects:
-    """rectangle planes on the device, behind the interface the tests below use for either shape"""
+class Side:
+    """one set of the scene on the device, as rectangle planes ("rect") or as the same vertices as 4-gons in a layout of 4 or 16 vertex
+    rows with NaN in the padded slots ("poly4", "poly16"): .search holds the adaptors of tests/pair_search_harness.py, .args is what
+    they take for this set"""
 
-    def __init__(self, eng, planes):
-        self.eng, self.host, self.n = eng, planes, planes.shape[1]
-        self.d = eng.to_device(planes)
-        self.arg = rect_tests.planes_of(self.d)
+    def __init__(self, eng, shape, planes):
+        self.eng, self.n = eng, planes.shape[1]
+        if shape == "rect":
+            self.search = {"cross": psh.rect_cross, "broad": psh.rect_broad}
+            self.d = eng.to_device(planes)
+            self.args = ([self.d.row(k) for k in range(8)], self.n)
+        else:
+            self.search = {"cross": psh.poly_cross, "broad": psh.poly_broad}
+            self.d = psh.DeviceSet(eng, tc.as_polygons(planes, int(shape[4:])), offset=1, stride=self.n + 3)
+            self.args = (self.d,)
+
+    def call(self, fn, other, upper):
+        return self.search[fn](self.eng, *self.args, *other.args, upper)
 
     def run(self, fn, other, upper, capacity=None):
-        return rect_tests.run(self.eng, fn, self.arg, self.n, other.arg, other.n, upper, capacity)
+        """(pairs, total) of fn = "cross" / "broad" between guard entries, count first when capacity is None"""
+        return psh.run(self.eng, self.call(fn, other, upper), capacity)
 
-    def check(self, oracle, other=None, upper=False):
-        return rect_tests.check(self.eng, oracle, self.host, None if other is None else other.host, upper=upper)
+    def check(self, other=None, upper=False):
+        """broad == cross, list and count, against `other` (itself when None); returns the list"""
+        other = self if other is None else other
+        got, _ = psh.same_as(self.eng, self.call("broad", other, upper), self.call("cross", other, upper))
+        self.eng.check_async()
+        return got
 
     def free(self):
         self.d.free()
-
-
-class Polys:
-    """the same vertices as 4-gons in a layout of `rows` vertex rows, NaN in the padded slots"""
-
-    def __init__(self, eng, planes, rows):
-        self.eng, self.host, self.n = eng, tc.as_polygons(planes, rows), planes.shape[1]
-        self.up = Uploaded(eng, self.host, offset=1, stride=self.n + 3)
-
-    def run(self, fn, other, upper, capacity=None):
-        return poly_tests.run(self.eng, fn, self.up.set, other.up.set, upper, capacity)
-
-    def check(self, oracle, other=None, upper=False):
-        o = self if other is None else other
-        return poly_tests.check(self.eng, oracle, self.host, None if other is None else o.host, upper=upper, ua=self.up, ub=o.up, use_oracle=False)
-
-    def free(self):
-        self.up.free()
-
-
-def upload(eng, shape, planes):
-    return Rects(eng, planes) if shape == "rect" else Polys(eng, planes, int(shape[4:]))
 
 
 @pytest.fixture(scope="module")
@@ -68,7 +60,7 @@ def oracle_lists(eng, oracle, scenes):
     same polygons, so one polygon list serves both."""
     out = {}
     for covers, (a, b, _) in scenes.items():
-        out["rect", covers] = rect_tests.oracle_pairs(oracle, a, b, False)
+        out["rect", covers] = rect_oracle_pairs(oracle, a, b, False)
         out["poly", covers] = np.argwhere(reference(eng, oracle, tc.as_polygons(a, 4), tc.as_polygons(b, 4))).astype(np.uint32)
     return out
 
@@ -82,8 +74,8 @@ def per_row(pairs, n):
 def test_two_sets(eng, oracle, scenes, oracle_lists, shape, covers):
     """probes against piles: a probe with h hitters has h hits (+ 3 through the wild tail with the covers)"""
     a, b, info = scenes[covers]
-    A, B = upload(eng, shape, a), upload(eng, shape, b)
-    got = A.check(oracle, B)                                   # broad == cross, list and count
+    A, B = Side(eng, shape, a), Side(eng, shape, b)
+    got = A.check(B)                                   # broad == cross, list and count
     hits = per_row(got, A.n)
     assert np.array_equal(hits, info["h"] + covers)
     sides = {tc.SHORT_HITS - 1, tc.SHORT_HITS, tc.SHORT_HITS + 1, tc.MID_HITS - 1, tc.MID_HITS, tc.MID_HITS + 1}
@@ -99,8 +91,8 @@ def test_two_sets(eng, oracle, scenes, oracle_lists, shape, covers):
 def test_transposed(eng, oracle, scenes, oracle_lists, shape, covers):
     """piles against probes: every pile object is a row with 0 or 1 hits, every cover a wild row that hits every probe"""
     a, b, info = scenes[covers]
-    A, B = upload(eng, shape, a), upload(eng, shape, b)
-    got = B.check(oracle, A)
+    A, B = Side(eng, shape, a), Side(eng, shape, b)
+    got = B.check(A)
     hits = per_row(got, B.n)
     assert set(hits[info["owner"] >= 0].tolist()) == {0, 1} and (hits[info["owner"] < 0] == A.n).all()
     want = oracle_lists[shape[:4], covers][:, ::-1]
@@ -118,8 +110,8 @@ def test_self_upper(eng, oracle, scenes, shape, order):
     both = np.concatenate([a, b], axis=1)
     if order == "shuffled":
         both = both[:, tc.self_shuffle(a.shape[1], both.shape[1])]
-    S = upload(eng, shape, both)
-    got = S.check(oracle, upper=True)
+    S = Side(eng, shape, both)
+    got = S.check(upper=True)
     hits = per_row(got, S.n)
     assert (hits <= tc.SHORT_HITS).any() and ((hits > tc.SHORT_HITS) & (hits <= tc.MID_HITS)).any() and (hits > tc.MID_HITS).any()
     S.free()
@@ -148,7 +140,7 @@ def test_capacity_inside_each_route(eng, scenes, shape, covers):
     """a capacity that ends in front of, one entry into, one entry short of and at the end of a row of each route: the list is the
     full list's prefix, the count the total, and nothing is written past the capacity (run checks the guard entries)"""
     a, b, info = scenes[covers]
-    A, B = upload(eng, shape, a), upload(eng, shape, b)
+    A, B = Side(eng, shape, a), Side(eng, shape, b)
     full, total = A.run("broad", B, False)
     assert total == len(full) == int((info["h"] + covers).sum())
     assert np.array_equal(full, A.run("cross", B, False)[0])

@@ -11,11 +11,13 @@ import sys
 import numpy as np
 import pytest
 
+import pair_search_harness as psh
+from pair_search_harness import SENTINEL
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_PAIRS = 4_000_000       # above this the reference is the pairwise GPU kernel
 SIZES = [1, 63, 64, 65, 255, 256, 257, 1000, 4099]
-SENTINEL = np.uint64(0xA5A5A5A5A5A5A5A5)
 FUZZ_SEED = 2026
 
 
@@ -74,17 +76,6 @@ def run_mask(eng, pa, n_a, pb, n_b, ld=None, upper=False, row_base=0, col_base=0
     d_mask.free()
     d_cnt.free()
     return m, c
-
-
-def run_pairs(eng, pa, n_a, pb, n_b, capacity, upper=False, row_base=0, col_base=0):
-    d_pairs = eng.empty((capacity + 4, 2), np.uint32)
-    eng.memset(d_pairs, 0xA5, d_pairs.nbytes)
-    d_cnt = eng.zeros(1, np.uint64)
-    eng.sat_rect_cross_pairs(pa, n_a, pb, n_b, d_pairs, capacity, d_cnt, row_base=row_base, col_base=col_base, upper=upper)
-    p, c = d_pairs.get(), int(d_cnt.get()[0])
-    d_pairs.free()
-    d_cnt.free()
-    return p, c
 
 
 @pytest.fixture(scope="module")
@@ -234,14 +225,13 @@ def test_pair_list(eng, oracle, wl):
         m, total = run_mask(eng, pa, n_a, pb, n_b, upper=upper, row_base=rb, col_base=cb)
         want = (np.argwhere(mask_bits(m, n_b)) + (rb, cb)).astype(np.uint32)
         assert total == len(want) and total > 1000
-        p, c = run_pairs(eng, pa, n_a, pb, n_b, total, upper=upper, row_base=rb, col_base=cb)
-        assert c == total and np.array_equal(p[:total], want)
-        assert (p[total:].view(np.uint64) == SENTINEL).all(), "written past the capacity"
+        call = psh.rect_cross(eng, pa, n_a, pb, n_b, upper, rb, cb)
+        p, c = psh.run(eng, call, total)            # (run checks the guard entries in front of the list and past the capacity)
+        assert c == total and np.array_equal(p, want)
         cap = total // 3 + 1
-        p, c = run_pairs(eng, pa, n_a, pb, n_b, cap, upper=upper, row_base=rb, col_base=cb)
-        assert c == total and np.array_equal(p[:cap], want[:cap])
-        assert (p[cap:].view(np.uint64) == SENTINEL).all(), "written past the capacity"
-        p2, _ = run_pairs(eng, pa, n_a, pb, n_b, cap, upper=upper, row_base=rb, col_base=cb)
+        p, c = psh.run(eng, call, cap)
+        assert c == total and np.array_equal(p, want[:cap])
+        p2, _ = psh.run(eng, call, cap)
         assert p.tobytes() == p2.tobytes()
     # capacity 0 with no buffer: a count-only call
     d_cnt = eng.zeros(1, np.uint64)
@@ -269,9 +259,9 @@ def test_pair_list_several_passes(eng, oracle, wl):
     per_row = ref_block.sum(1) * (n_b // blk) + ref_block[:, : n_b % blk].sum(1)
     total = int(per_row.sum())
     assert total > 10_000
-    p, c = run_pairs(eng, pa, n_a, pb, n_b, total)
+    p, c = psh.run(eng, psh.rect_cross(eng, pa, n_a, pb, n_b), total)
     assert c == total
-    p = p[:total].astype(np.int64)
+    p = p.astype(np.int64)
     assert np.array_equal(np.bincount(p[:, 0], minlength=n_a), per_row)
     assert (np.diff(p[:, 0] * n_b + p[:, 1]) > 0).all(), "not in row-major order"
     assert ref_block[p[:, 0], p[:, 1] % blk].all()

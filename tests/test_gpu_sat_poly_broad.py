@@ -12,7 +12,9 @@ import sys
 import numpy as np
 import pytest
 
-from test_gpu_sat_poly_cross import SENTINEL, Uploaded, degenerate_set, reference, touching_sets
+import pair_search_harness as psh
+from pair_search_harness import DeviceSet, nan_padded, sparse_set
+from sat_cross_harness import degenerate_set, reference, touching_sets
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -20,58 +22,13 @@ PKG_DIR = os.path.join(os.path.dirname(HERE), "convex-2d-gpu-collision-detection
 ORACLE_PAIRS = 2_000_000       # above this the reference is the cross list alone
 
 
-def nan_padded(s):
-    """the set with NaN in every vertex slot >= the polygon's count (counts outside 1..rows: every slot of a count of 0 stays)"""
-    vx, vy, k = s
-    if k is None:
-        return s
-    pad = np.arange(vx.shape[0])[:, None] >= np.clip(k.astype(np.int64), 1, None)[None, :]
-    return np.where(pad, np.float32(np.nan), vx), np.where(pad, np.float32(np.nan), vy), k
-
-
-def sparse_set(wl, n, seed, rows=16, kmax=16, density=1.0):
-    """the sparse scene of the polygon cross bench, its extent scaled so that the hits per polygon stay constant"""
-    extent = 200.0 * np.sqrt(max(n, 64) / 32768) / density
-    return nan_padded(wl.random_convex_polygon_set(n, seed=seed, kmin=min(3, kmax), kmax=kmax, extent=extent, rows=rows))
-
-
-def run(eng, fn, a, b, upper, capacity=None):
-    """(pairs u32[capacity][2], total) of fn = "cross" / "broad"; capacity None: count first, then exact.  The list sits between
-    four guard entries in front and four (plus everything past the capacity) behind."""
-    def call(pairs, cap, cnt):
-        if fn == "cross":
-            eng.sat_poly_cross_pairs(a, b, pairs, cap, cnt, upper=upper)
-        else:
-            eng.sat_poly_broad_pairs(a, b, pairs, cap, cnt, upper=upper)
-
-    d_cnt = eng.zeros(1, np.uint64)
-    if capacity is None:
-        call(None, 0, d_cnt)
-        capacity = int(d_cnt.get()[0])
-        eng.memset(d_cnt, 0, 8)
-    d_pairs = eng.empty((capacity + 8, 2), np.uint32)
-    eng.memset(d_pairs, 0xA5, d_pairs.nbytes)
-    call(d_pairs.ptr + 32, capacity, d_cnt)
-    p, c = d_pairs.get(), int(d_cnt.get()[0])
-    d_pairs.free()
-    d_cnt.free()
-    assert (p[:4].view(np.uint64) == SENTINEL).all(), f"{fn}: written in front of the list"
-    assert (p[4 + capacity:].view(np.uint64) == SENTINEL).all(), f"{fn}: written past the capacity"
-    return p[4:4 + capacity], c
-
-
 def check(eng, oracle, a, b=None, upper=False, min_pairs=1, ua=None, ub=None, use_oracle=True):
     """broad == cross (and == the oracle up to ORACLE_PAIRS) on a (against itself when b is None) and b; returns the list"""
     own = ua is None
     if own:
-        ua = Uploaded(eng, a, offset=1, stride=a[0].shape[1] + 3)
-        ub = ua if b is None else Uploaded(eng, b, offset=2)
-    want, wc = run(eng, "cross", ua.set, ub.set, upper)
-    got, gc = run(eng, "broad", ua.set, ub.set, upper)
-    assert gc == wc and len(got) == wc, (gc, wc)
-    if not np.array_equal(got, want):
-        gs, ws = set(map(tuple, got.tolist())), set(map(tuple, want.tolist()))
-        raise AssertionError(f"lists differ: {len(ws - gs)} missing, e.g. {sorted(ws - gs)[:3]}, {len(gs - ws)} extra, e.g. {sorted(gs - ws)[:3]}")
+        ua = DeviceSet(eng, a, offset=1, stride=a[0].shape[1] + 3)
+        ub = ua if b is None else DeviceSet(eng, b, offset=2)
+    got, wc = psh.same_as(eng, psh.poly_broad(eng, ua, ub, upper), psh.poly_cross(eng, ua, ub, upper))
     bb = a if b is None else b
     if use_oracle and a[0].shape[1] * bb[0].shape[1] <= ORACLE_PAIRS:
         m = reference(eng, oracle, a, bb)
@@ -102,11 +59,11 @@ def test_mixed_layouts(eng, oracle, wl):
     n_a, n_b = 1500, 1100
     a = sparse_set(wl, n_a, 31, rows=4, kmax=4, density=3.0)
     b = sparse_set(wl, n_b, 32, density=3.0)
-    ua, ub = Uploaded(eng, a, offset=3, stride=n_a + 11), Uploaded(eng, b, offset=1, stride=n_b + 5)
+    ua, ub = DeviceSet(eng, a, offset=3, stride=n_a + 11), DeviceSet(eng, b, offset=1, stride=n_b + 5)
     check(eng, oracle, a, b, ua=ua, ub=ub, min_pairs=200)
     check(eng, oracle, b, a, ua=ub, ub=ua, min_pairs=200, use_oracle=False)   # (the transposed scene)
     full = wl.random_convex_polygon_set(n_a, seed=33, kmin=4, kmax=4, extent=200.0 * np.sqrt(n_a / 32768) / 3, rows=4)
-    un = Uploaded(eng, (full[0], full[1], None))   # every polygon has exactly `rows` vertices: no count plane
+    un = DeviceSet(eng, (full[0], full[1], None))   # every polygon has exactly `rows` vertices: no count plane
     check(eng, oracle, (full[0], full[1], None), b, ua=un, ub=ub, min_pairs=200)
     check(eng, oracle, b, (full[0], full[1], None), ua=ub, ub=un, min_pairs=200, use_oracle=False)
     check(eng, oracle, (full[0], full[1], None), ua=un, ub=un, upper=True, min_pairs=100)
@@ -250,8 +207,8 @@ def test_out_of_range_counts(eng, pkg, oracle, wl):
     ref = reference(eng, oracle, a, b)   # (every polygon with its valid count)
     eng.check_async()
     for which in ("a", "b", "both"):
-        ua = Uploaded(eng, (a[0], a[1], ka if which != "b" else a[2]))
-        ub = Uploaded(eng, (b[0], b[1], kb if which != "a" else b[2]))
+        ua = DeviceSet(eng, (a[0], a[1], ka if which != "b" else a[2]))
+        ub = DeviceSet(eng, (b[0], b[1], kb if which != "a" else b[2]))
         want = ref.copy()
         if which != "b":
             want[bad_a] = False
@@ -259,27 +216,15 @@ def test_out_of_range_counts(eng, pkg, oracle, wl):
             want[:, bad_b] = False
         total = int(want.sum())
         assert total > 1000
-        lists = {}
-        for fn in ("cross", "broad"):
-            d_pairs = eng.empty((total + 8, 2), np.uint32)
-            eng.memset(d_pairs, 0xA5, d_pairs.nbytes)
-            d_cnt = eng.zeros(1, np.uint64)
-            getattr(eng, f"sat_poly_{fn}_pairs")(ua.set, ub.set, d_pairs.ptr + 32, total, d_cnt)
-            with pytest.raises(pkg.C2DError):
-                eng.synchronize()
-            eng.synchronize()
-            eng.check_async()   # reported once, then clear
-            p = d_pairs.get()
-            assert int(d_cnt.get()[0]) == total, fn
-            assert (p[:4].view(np.uint64) == SENTINEL).all() and (p[4 + total:].view(np.uint64) == SENTINEL).all(), fn
-            lists[fn] = p[4:4 + total]
-            d_pairs.free()
-            d_cnt.free()
-        assert np.array_equal(lists["broad"], lists["cross"]) and np.array_equal(lists["broad"], np.argwhere(want).astype(np.uint32))
+        for fn, search in (("cross", psh.poly_cross), ("broad", psh.poly_broad)):
+            p, c = psh.run(eng, search(eng, ua, ub), total, absent=True)   # (reported by the synchronise once, then clear)
+            eng.check_async()
+            why = psh.compare(p, c, np.argwhere(want))
+            assert why is None, (fn, why)
         ua.free()
         ub.free()
     # self mode with bad counts, and the next call on valid sets is clean
-    us = Uploaded(eng, (a[0], a[1], ka))
+    us = DeviceSet(eng, (a[0], a[1], ka))
     d_cnt = eng.zeros(1, np.uint64)
     eng.sat_poly_broad_pairs(us.set, us.set, None, 0, d_cnt, upper=True)
     with pytest.raises(pkg.C2DError):
@@ -296,10 +241,10 @@ def test_out_of_range_counts(eng, pkg, oracle, wl):
 def test_capacity_and_determinism(eng, oracle, wl):
     n_a, n_b = 9000, 7001
     a, b = sparse_set(wl, n_a, 111, density=3.0), sparse_set(wl, n_b, 112, density=3.0)
-    ua, ub = Uploaded(eng, a, offset=1), Uploaded(eng, b, stride=n_b + 7)
+    ua, ub = DeviceSet(eng, a, offset=1), DeviceSet(eng, b, stride=n_b + 7)
     for upper in (False, True):
-        full, total = run(eng, "broad", ua.set, ub.set, upper)
-        want, wc = run(eng, "cross", ua.set, ub.set, upper)
+        full, total = psh.run(eng, psh.poly_broad(eng, ua, ub, upper))
+        want, wc = psh.run(eng, psh.poly_cross(eng, ua, ub, upper))
         assert total == wc > 5000 and np.array_equal(full, want)
         d_cnt = eng.zeros(1, np.uint64)             # capacity 0, no buffer: count only
         eng.sat_poly_broad_pairs(ua.set, ub.set, None, 0, d_cnt, upper=upper)
@@ -308,15 +253,15 @@ def test_capacity_and_determinism(eng, oracle, wl):
         assert int(d_cnt.get()[0]) == 2 * total, "d_count is incremented, not set"
         d_cnt.free()
         for cap in (1, total // 3 + 1, total - 1, total):
-            p, c = run(eng, "broad", ua.set, ub.set, upper, capacity=cap)
+            p, c = psh.run(eng, psh.poly_broad(eng, ua, ub, upper), capacity=cap)
             assert c == total and np.array_equal(p, full[:cap])
-        p1, _ = run(eng, "broad", ua.set, ub.set, upper, capacity=total // 2)
-        p2, _ = run(eng, "broad", ua.set, ub.set, upper, capacity=total // 2)
+        p1, _ = psh.run(eng, psh.poly_broad(eng, ua, ub, upper), capacity=total // 2)
+        p2, _ = psh.run(eng, psh.poly_broad(eng, ua, ub, upper), capacity=total // 2)
         assert p1.tobytes() == p2.tobytes()
     got = eng.poly_broad_pairs_host(*a, *b)
-    assert got.dtype == np.uint32 and np.array_equal(got, run(eng, "cross", ua.set, ub.set, False)[0])
+    assert got.dtype == np.uint32 and np.array_equal(got, psh.run(eng, psh.poly_cross(eng, ua, ub))[0])
     got = eng.poly_broad_pairs_host(*a, upper=True)
-    assert np.array_equal(got, run(eng, "cross", ua.set, ua.set, True)[0]) and len(got) > 1000
+    assert np.array_equal(got, psh.run(eng, psh.poly_cross(eng, ua, ua, True))[0]) and len(got) > 1000
     ua.free()
     ub.free()
     eng.check_async()
@@ -324,7 +269,7 @@ def test_capacity_and_determinism(eng, oracle, wl):
 
 def test_argument_errors(eng, pkg, wl):
     a = wl.random_convex_polygon_set(100, seed=5, extent=3.0)
-    ua = Uploaded(eng, a)
+    ua = DeviceSet(eng, a)
     d_pairs = eng.zeros((16, 2), np.uint32)
     d_cnt = eng.zeros(1, np.uint64)
     S = ua.set
@@ -400,7 +345,7 @@ def test_fuzz_at_a_fixed_seed(eng):
 
 def test_graph_capture():
     """replay after a warm-up equals the direct call, two-set and self; a capture that would have to grow the scratch is refused
-    (tests/poly_broad_graph_check.py, its own process: torch has to be imported before libc2d.so)"""
-    out = subprocess.run([sys.executable, os.path.join(HERE, "poly_broad_graph_check.py")], capture_output=True, text=True, timeout=300)
+    (tests/pair_search_graph_check.py, its own process: torch has to be imported before libc2d.so)"""
+    out = subprocess.run([sys.executable, os.path.join(HERE, "pair_search_graph_check.py"), "poly_broad"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-1500:]
     assert "poly broad graph ok" in out.stdout

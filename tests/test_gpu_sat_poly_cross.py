@@ -1,8 +1,9 @@
 """GPU tests of the all-pairs convex polygon entry points (c2d_sat_poly_cross_mask / _pairs): result (i, j) must be the boolean of
 the pairwise polygon path on (A_i, B_j), bit for bit.  The reference materialises the pairs (np.repeat / np.tile, chunks of at most
 1e6 pairs) and runs the CPU oracle on them up to a few million pairs; above that the same pairs go through the pairwise GPU kernel
-(c2d_sat_poly_pairs_rows, itself pinned to the oracle by test_gpu_sat.py) in chunks.  Never the code under test.  Every mask and
-list buffer handed to the library sits between guard rows that are checked afterwards."""
+(c2d_sat_poly_pairs_rows, itself pinned to the oracle by test_gpu_sat.py) in chunks (tests/sat_cross_harness.py).  Never the code under
+test.  Every mask and list buffer handed to the library sits between guard rows that are checked afterwards (run_mask there, run
+of tests/pair_search_harness.py)."""
 import ctypes as C
 import importlib.util
 import os
@@ -13,133 +14,15 @@ import sys
 import numpy as np
 import pytest
 
+import pair_search_harness as psh
+from pair_search_harness import SENTINEL, DeviceSet
+from sat_cross_harness import check_mask, degenerate_set, mask_bits, reference, run_mask, touching_sets
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_DIR = os.path.join(os.path.dirname(HERE), "convex-2d-gpu-collision-detection_amd")
-ORACLE_PAIRS = 4_000_000       # above this the reference is the pairwise GPU kernel
-CHUNK = 1_000_000              # materialised pairs per reference chunk (about 260 MB of host memory at 16 rows)
 SIZES = [1, 63, 64, 65, 255, 256, 257, 1000, 4099]
-SENTINEL = np.uint64(0xA5A5A5A5A5A5A5A5)
 FUZZ_SEED = 2026
-
-
-def padded(s, rows):
-    """the set (vx, vy, k) in a layout of `rows` vertex rows (zeros above its own)"""
-    vx, vy, k = s
-    if vx.shape[0] == rows:
-        return s
-    ox, oy = np.zeros((rows, vx.shape[1]), np.float32), np.zeros((rows, vx.shape[1]), np.float32)
-    ox[:vx.shape[0]], oy[:vx.shape[0]] = vx, vy
-    return ox, oy, k
-
-
-def counts_of(s):
-    return np.full(s[0].shape[1], s[0].shape[0], np.uint8) if s[2] is None else s[2]
-
-
-def reference(eng, oracle, a, b, force_gpu=False, fe=None):
-    """bool [n_a][n_b]: result (i, j) of the pairwise path on (A_i, B_j); `fe`: another build's engine for the GPU reference"""
-    rows = max(a[0].shape[0], b[0].shape[0])
-    (ax, ay, _), (bx, by, _) = padded(a, rows), padded(b, rows)
-    ka, kb = counts_of(a), counts_of(b)
-    n_a, n_b = ax.shape[1], bx.shape[1]
-    out = np.empty((n_a, n_b), bool)
-    use_gpu = force_gpu or n_a * n_b > ORACLE_PAIRS
-    step = max(1, CHUNK // n_b)
-    run = fe or eng
-    for r0 in range(0, n_a, step):
-        r1 = min(n_a, r0 + step)
-        m = (r1 - r0) * n_b
-        vx = np.stack([np.repeat(ax[:, r0:r1], n_b, axis=1), np.tile(bx, r1 - r0)])
-        vy = np.stack([np.repeat(ay[:, r0:r1], n_b, axis=1), np.tile(by, r1 - r0)])
-        k = np.stack([np.repeat(ka[r0:r1], n_b), np.tile(kb, r1 - r0)])
-        if use_gpu:
-            d_vx, d_vy, d_k = run.to_device(vx), run.to_device(vy), run.to_device(k)
-            d_out = run.zeros(m, np.uint8)
-            run.sat_poly_pairs_rows(d_vx, d_vy, d_k, m, rows, d_out)
-            res = d_out.get()
-            for x in (d_vx, d_vy, d_k, d_out):
-                x.free()
-        else:
-            res, _ = oracle.sat_poly_pairs(vx, vy, k)
-        out[r0:r1] = res.reshape(r1 - r0, n_b).astype(bool)
-    return out
-
-
-class Uploaded:
-    """A set on the device: every plane row shifted by `offset` floats, `stride` >= n elements between vertex rows; the gaps hold
-    NaN.  .set is the c2d_poly_set; .sub(r0, r1) the shard of polygons [r0, r1) (pointer offset, the same stride)."""
-
-    def __init__(self, eng, s, offset=0, stride=None, with_k=True):
-        vx, vy, k = s
-        self.eng, self.rows, self.n = eng, vx.shape[0], vx.shape[1]
-        self.stride = self.n if stride is None else stride
-        host = np.full((2, self.rows * self.stride + 4), np.nan, np.float32)
-        for p, v in enumerate((vx, vy)):
-            for r in range(self.rows):
-                host[p, offset + r * self.stride: offset + r * self.stride + self.n] = v[r]
-        self.d = eng.to_device(host)
-        self.px, self.py = self.d.row(0) + 4 * offset, self.d.row(1) + 4 * offset
-        self.dk = eng.to_device(k) if (k is not None and with_k) else None
-        self.set = self.sub(0, self.n)
-
-    def sub(self, r0, r1):
-        return self.eng.poly_set(self.px + 4 * r0, self.py + 4 * r0, None if self.dk is None else self.dk.ptr + r0, r1 - r0, self.rows, self.stride)
-
-    def free(self):
-        self.d.free()
-        if self.dk is not None:
-            self.dk.free()
-
-
-def mask_bits(mask_words, n_b):
-    """u64 [rows][words] -> bool [rows][n_b] (bit j & 63 of word j >> 6)"""
-    bits = np.unpackbits(np.ascontiguousarray(mask_words).view(np.uint8), bitorder="little", axis=-1)
-    return bits.reshape(mask_words.shape[0], -1)[:, :n_b].astype(bool)
-
-
-def run_mask(eng, a, b, ld=None, upper=False, row_base=0, col_base=0, stream=0):
-    """(mask words u64 [n_a][ld], count); the mask sits between two guard rows"""
-    n_a, n_b = a.n, b.n
-    ld = (n_b + 63) // 64 if ld is None else ld
-    d_mask = eng.empty((n_a + 2, ld), np.uint64)
-    eng.memset(d_mask, 0xA5, d_mask.nbytes, stream)
-    d_cnt = eng.zeros(1, np.uint64, stream)
-    eng.sat_poly_cross_mask(a, b, d_mask.ptr + 8 * ld, ld_words=ld, row_base=row_base, col_base=col_base, upper=upper, count=d_cnt, stream=stream)
-    eng.synchronize(stream)
-    m, c = d_mask.get(), int(d_cnt.get()[0])
-    d_mask.free()
-    d_cnt.free()
-    assert (m[0] == SENTINEL).all() and (m[-1] == SENTINEL).all(), "written outside the mask"
-    return m[1:-1], c
-
-
-def run_pairs(eng, a, b, capacity, upper=False, row_base=0, col_base=0):
-    """(pairs u32 [capacity + 4][2], total); the list sits behind four guard entries, the entries past the capacity are guards too"""
-    d_pairs = eng.empty((capacity + 8, 2), np.uint32)
-    eng.memset(d_pairs, 0xA5, d_pairs.nbytes)
-    d_cnt = eng.zeros(1, np.uint64)
-    eng.sat_poly_cross_pairs(a, b, d_pairs.ptr + 32, capacity, d_cnt, row_base=row_base, col_base=col_base, upper=upper)
-    p, c = d_pairs.get(), int(d_cnt.get()[0])
-    d_pairs.free()
-    d_cnt.free()
-    assert (p[:4].view(np.uint64) == SENTINEL).all(), "written in front of the list"
-    return p[4:], c
-
-
-def check(eng, oracle, a, b, ref=None, offsets=((0, 1), (3, 0))):
-    """mask and count of a x b equal the reference, for two placements of the planes; returns the reference"""
-    ref = reference(eng, oracle, a, b) if ref is None else ref
-    for oa, ob in offsets:
-        ua, ub = Uploaded(eng, a, offset=oa, stride=a[0].shape[1] + oa), Uploaded(eng, b, offset=ob)
-        m, c = run_mask(eng, ua.set, ub.set)
-        got = mask_bits(m, ub.n)
-        assert np.array_equal(got, ref), f"{int((got != ref).sum())} results differ"
-        assert c == int(ref.sum())
-        ua.free()
-        ub.free()
-    eng.check_async()
-    return ref
 
 
 @pytest.fixture(scope="module")
@@ -160,8 +43,8 @@ def test_shape_of_the_call(eng, big_sets):
             for ib, n_b in enumerate(SIZES):
                 sa = tuple(x[..., :n_a] for x in a)
                 sb = tuple(x[..., :n_b] for x in b)
-                ua = Uploaded(eng, sa, offset=(ia + ib) % 4, stride=n_a + (7 if (ia + ib) % 2 else 0))
-                ub = Uploaded(eng, sb, offset=(ia + 2 * ib + 1) % 4, stride=n_b + (5 if ib % 2 else 0))
+                ua = DeviceSet(eng, sa, offset=(ia + ib) % 4, stride=n_a + (7 if (ia + ib) % 2 else 0))
+                ub = DeviceSet(eng, sb, offset=(ia + 2 * ib + 1) % 4, stride=n_b + (5 if ib % 2 else 0))
                 m, c = run_mask(eng, ua.set, ub.set, stream=s if (ia + ib) % 2 else 0)
                 want = ref[:n_a, :n_b]
                 bits = np.unpackbits(m.view(np.uint8), bitorder="little", axis=-1).reshape(n_a, -1)
@@ -180,7 +63,7 @@ def test_layout_padding_words_untouched(eng, oracle, wl):
     a, b = wl.random_convex_polygon_set(n_a, seed=21, extent=8.0), wl.random_convex_polygon_set(n_b, seed=22, extent=8.0)
     ref = reference(eng, oracle, a, b)
     assert 0.02 < ref.mean() < 0.15
-    ua, ub = Uploaded(eng, a), Uploaded(eng, b)
+    ua, ub = DeviceSet(eng, a), DeviceSet(eng, b)
     words = (n_b + 63) // 64
     m, c = run_mask(eng, ua.set, ub.set, ld=words + 3)
     assert (m[:, words:] == SENTINEL).all(), "padding words were written"
@@ -196,7 +79,7 @@ def test_upper_mode_and_shards(eng, oracle, wl):
     (full - n) / 2 pairs counted; row shards (pointer offset + stride, row_base) and column tiles (col_base) reproduce it."""
     n = 1000
     s = wl.random_convex_polygon_set(n, seed=31, extent=8.0)
-    us = Uploaded(eng, s, offset=1, stride=n + 3)
+    us = DeviceSet(eng, s, offset=1, stride=n + 3)
     full, full_c = run_mask(eng, us.set, us.set)
     full_bits = mask_bits(full, n)
     assert np.array_equal(full_bits, reference(eng, oracle, s, s))
@@ -253,7 +136,7 @@ def test_mixed_layouts(eng, oracle, wl):
         for rb in (4, 8, 12, 16):
             a = wl.random_convex_polygon_set(n, seed=50 + ra, kmin=min(3, ra), kmax=ra, extent=5.0, rows=ra)
             b = wl.random_convex_polygon_set(n, seed=70 + rb, kmin=min(3, rb), kmax=rb, extent=5.0, rows=rb)
-            total += int(check(eng, oracle, a, b, offsets=((ra % 4, rb % 3),)).sum())
+            total += int(check_mask(eng, oracle, a, b, offsets=((ra % 4, rb % 3),)).sum())
     assert total > 0.05 * 16 * n * n
     # every polygon has exactly `rows` vertices: no count plane on A, on B, on both
     a = wl.random_convex_polygon_set(400, seed=91, kmin=8, kmax=8, extent=5.0, rows=8)
@@ -264,7 +147,7 @@ def test_mixed_layouts(eng, oracle, wl):
         assert ref.mean() > 0.05
         nx = (x[0], x[1], None) if x is not c else x
         ny = (y[0], y[1], None) if y is not c else y
-        check(eng, oracle, nx, ny, ref=ref)
+        check_mask(eng, oracle, nx, ny, ref=ref)
     # clockwise polygons (inward-pointing (-ey, ex)) against counter-clockwise ones and against themselves
     rng = np.random.default_rng(94)
     m = 500
@@ -274,48 +157,18 @@ def test_mixed_layouts(eng, oracle, wl):
         vx[:k[q], q], vy[:k[q], q] = xs + np.float32(rng.uniform(-5, 5)), ys + np.float32(rng.uniform(-5, 5))
     cw = (vx, vy, k)
     for x, y in ((cw, c), (c, cw), (cw, cw)):
-        assert check(eng, oracle, x, y).mean() > 0.05
-
-
-def degenerate_set(wl, n, seed):
-    """points, segments, repeated vertices, collinear polygons, and ordinary ones, close together"""
-    rng = np.random.default_rng(seed)
-    vx, vy, k = wl.random_convex_polygon_set(n, seed=seed, extent=3.0)
-    vx, vy, k = vx.copy(), vy.copy(), k.copy()
-    kind = rng.integers(0, 6, n)
-    k[kind == 0] = 1
-    k[kind == 1] = 2
-    rep = np.flatnonzero(kind == 2)          # repeated vertices: vertex 1 = vertex 0, vertex 3 = vertex 2
-    vx[1, rep], vy[1, rep] = vx[0, rep], vy[0, rep]
-    vx[3, rep], vy[3, rep] = vx[2, rep], vy[2, rep]
-    col = np.flatnonzero(kind == 3)          # collinear: every vertex on one line through vertex 0
-    tt = rng.uniform(-2, 2, (16, col.size)).astype(np.float32)
-    dx, dy = rng.choice([0.0, 1.0, 0.5], col.size).astype(np.float32), rng.choice([1.0, 0.0, 0.25], col.size).astype(np.float32)
-    vx[:, col], vy[:, col] = vx[0, col] + tt * dx, vy[0, col] + tt * dy
-    return vx, vy, k
-
-
-def touching_sets(n):
-    """A_i and B_i are axis-aligned boxes (k = 4) built on an integer grid so that B_i shares an edge (i even) or exactly one
-    vertex (i odd) with A_i, every coordinate exact in float32."""
-    i = np.arange(n)
-    x0, y0 = (3 * (i % 50)).astype(np.float32), (3 * (i // 50)).astype(np.float32)
-    ax = np.stack([x0, x0 + 1, x0 + 1, x0])
-    ay = np.stack([y0, y0, y0 + 1, y0 + 1])
-    sx, sy = np.float32(1), np.where(i % 2 == 0, 0, 1).astype(np.float32)   # shifted right by 1 (edge) or right and up (vertex)
-    k = np.full(n, 4, np.uint8)
-    return (ax, ay, k), (ax + sx, ay + sy, k)
+        assert check_mask(eng, oracle, x, y).mean() > 0.05
 
 
 def test_degenerate_and_touching(eng, oracle, wl):
     n = 1200
     a, b = degenerate_set(wl, n, 101), degenerate_set(wl, n, 102)
-    ref = check(eng, oracle, a, b)
+    ref = check_mask(eng, oracle, a, b)
     assert 0.05 < ref.mean() < 0.95
     pts = np.flatnonzero(a[2] == 1)
     assert ref[pts][:, b[2] == 1].all(), "two points read 'collide' (their only axis is the zero vector)"
     ta, tb = touching_sets(1000)
-    ref = check(eng, oracle, ta, tb)
+    ref = check_mask(eng, oracle, ta, tb)
     assert ref.diagonal().all(), "pairs that share an edge or a vertex touch: strict < does not separate them"
     assert 0.0005 < ref.mean() < 0.02
 
@@ -330,7 +183,7 @@ def test_extreme_scales(eng, oracle, wl, scale):
         out.append(((vx.astype(np.float64) * scale).astype(np.float32), (vy.astype(np.float64) * scale).astype(np.float32), k))
     if scale < 1e-38:
         assert (np.abs(out[0][0][out[0][0] != 0]) < 1.2e-38).all()
-    ref = check(eng, oracle, *out)
+    ref = check_mask(eng, oracle, *out)
     assert ref.mean() > (0.02 if scale > 1e-38 else 0.0)
 
 
@@ -349,7 +202,7 @@ def test_non_finite_vertices(eng, oracle, wl):
     a[1][2, 30:40] = np.nan          # y of vertex 2 of A_30 .. A_39
     b[1][0, 50:60] = np.nan          # y of vertex 0 of B_50 .. B_59
     b[0][1, 70:80] = np.nan          # x of vertex 1 of B_70 .. B_79
-    ref = check(eng, oracle, a, b)
+    ref = check_mask(eng, oracle, a, b)
     assert (ref != fin).mean() > 0.01, "the injected values no longer change results"
     assert ref[10:20].all(), "a NaN at vertex 0 of A reads 'collide' with every B"
     assert ref[:, 50:60].all(), "a NaN at vertex 0 of B reads 'collide' with every A"
@@ -358,7 +211,7 @@ def test_non_finite_vertices(eng, oracle, wl):
 def test_dense_scene(eng, oracle, wl):
     n = 1500
     a, b = wl.random_convex_polygon_set(n, seed=131, extent=0.8), wl.random_convex_polygon_set(n, seed=132, extent=0.8)
-    ref = check(eng, oracle, a, b, offsets=((2, 1),))
+    ref = check_mask(eng, oracle, a, b, offsets=((2, 1),))
     assert ref.mean() > 0.5, ref.mean()
 
 
@@ -377,8 +230,8 @@ def test_out_of_range_counts(eng, pkg, oracle, wl):
     eng.check_async()
     words = (n_b + 63) // 64
     for which in ("a", "b", "both"):
-        ua = Uploaded(eng, (a[0], a[1], ka if which != "b" else a[2]))
-        ub = Uploaded(eng, (b[0], b[1], kb if which != "a" else b[2]))
+        ua = DeviceSet(eng, (a[0], a[1], ka if which != "b" else a[2]))
+        ub = DeviceSet(eng, (b[0], b[1], kb if which != "a" else b[2]))
         want = ref.copy()
         if which != "b":
             want[bad_a] = False
@@ -397,18 +250,10 @@ def test_out_of_range_counts(eng, pkg, oracle, wl):
         got = mask_bits(m[1:-1], n_b)
         assert np.array_equal(got, want) and int(d_cnt.get()[0]) == int(want.sum())
         # the list form counts and emits the same pairs
-        total = int(want.sum())
-        d_pairs = eng.empty((total + 4, 2), np.uint32)
-        eng.memset(d_pairs, 0xA5, d_pairs.nbytes)
-        eng.memset(d_cnt, 0, 8)
-        eng.sat_poly_cross_pairs(ua.set, ub.set, d_pairs, total, d_cnt)
-        with pytest.raises(pkg.C2DError):
-            eng.synchronize()
+        p, c = psh.run(eng, psh.poly_cross(eng, ua, ub), int(want.sum()), absent=True)
         eng.check_async()
-        p = d_pairs.get()
-        assert int(d_cnt.get()[0]) == total and np.array_equal(p[:total], np.argwhere(want).astype(np.uint32))
-        assert (p[total:].view(np.uint64) == SENTINEL).all()
-        for x in (d_mask, d_cnt, d_pairs, ua, ub):
+        assert psh.compare(p, c, np.argwhere(want)) is None
+        for x in (d_mask, d_cnt, ua, ub):
             x.free()
 
 
@@ -419,7 +264,7 @@ def test_pair_list(eng, oracle, wl):
     n_a, n_b = 700, 2100
     a, b = wl.random_convex_polygon_set(n_a, seed=151, extent=8.0), wl.random_convex_polygon_set(n_b, seed=152, extent=8.0, rows=16)
     ref = reference(eng, oracle, a, b)
-    ua, ub = Uploaded(eng, a, offset=2, stride=n_a + 9), Uploaded(eng, b, offset=1)
+    ua, ub = DeviceSet(eng, a, offset=2, stride=n_a + 9), DeviceSet(eng, b, offset=1)
     for upper, rb, cb in ((False, 0, 0), (False, 1000, 77), (True, 0, 0), (True, 500, 100)):
         m, total = run_mask(eng, ua.set, ub.set, upper=upper, row_base=rb, col_base=cb)
         bits = mask_bits(m, n_b)
@@ -429,14 +274,13 @@ def test_pair_list(eng, oracle, wl):
             assert np.array_equal(bits, ref & ((np.arange(n_b)[None, :] + cb) > (np.arange(n_a)[:, None] + rb)))
         want = (np.argwhere(bits) + (rb, cb)).astype(np.uint32)
         assert total == len(want) and total > 1000
-        p, c = run_pairs(eng, ua.set, ub.set, total, upper=upper, row_base=rb, col_base=cb)
-        assert c == total and np.array_equal(p[:total], want)
-        assert (p[total:].view(np.uint64) == SENTINEL).all(), "written past the capacity"
+        call = psh.poly_cross(eng, ua, ub, upper, rb, cb)
+        p, c = psh.run(eng, call, total)            # (run checks the guard entries in front of the list and past the capacity)
+        assert c == total and np.array_equal(p, want)
         cap = total // 3 + 1
-        p, c = run_pairs(eng, ua.set, ub.set, cap, upper=upper, row_base=rb, col_base=cb)
-        assert c == total and np.array_equal(p[:cap], want[:cap])
-        assert (p[cap:].view(np.uint64) == SENTINEL).all(), "written past the capacity"
-        p2, _ = run_pairs(eng, ua.set, ub.set, cap, upper=upper, row_base=rb, col_base=cb)
+        p, c = psh.run(eng, call, cap)
+        assert c == total and np.array_equal(p, want[:cap])
+        p2, _ = psh.run(eng, call, cap)
         assert p.tobytes() == p2.tobytes()
     d_cnt = eng.zeros(1, np.uint64)
     eng.sat_poly_cross_pairs(ua.set, ub.set, None, 0, d_cnt)   # capacity 0 with no buffer: a count-only call
@@ -460,14 +304,14 @@ def test_pair_list_several_passes(eng, oracle, wl):
     bb = wl.random_convex_polygon_set(blk, seed=162, kmax=4, extent=300.0, rows=4)
     reps = n_b // blk + 1
     b = (np.tile(bb[0], (1, reps))[:, :n_b], np.tile(bb[1], (1, reps))[:, :n_b], np.tile(bb[2], reps)[:n_b])
-    ua, ub = Uploaded(eng, a), Uploaded(eng, b)
+    ua, ub = DeviceSet(eng, a), DeviceSet(eng, b)
     ref_block = reference(eng, oracle, a, bb)
     per_row = ref_block.sum(1) * (n_b // blk) + ref_block[:, : n_b % blk].sum(1)
     total = int(per_row.sum())
     assert total > 10_000
-    p, c = run_pairs(eng, ua.set, ub.set, total)
+    p, c = psh.run(eng, psh.poly_cross(eng, ua, ub), total)
     assert c == total
-    p = p[:total].astype(np.int64)
+    p = p.astype(np.int64)
     assert np.array_equal(np.bincount(p[:, 0], minlength=n_a), per_row)
     assert (np.diff(p[:, 0] * n_b + p[:, 1]) > 0).all(), "not in row-major order"
     assert ref_block[p[:, 0], p[:, 1] % blk].all()
@@ -478,7 +322,7 @@ def test_pair_list_several_passes(eng, oracle, wl):
 
 def test_argument_errors(eng, pkg, wl):
     a = wl.random_convex_polygon_set(100, seed=5, extent=3.0)
-    ua = Uploaded(eng, a)
+    ua = DeviceSet(eng, a)
     d_mask = eng.zeros((100, 4), np.uint64)
     d_cnt = eng.zeros(1, np.uint64)
     S = ua.set
@@ -529,7 +373,7 @@ def test_fused_validation_builds_match_their_own_pairwise_kernel(eng, pkg, oracl
         a, b = wl.random_convex_polygon_set(600, seed=171, extent=4.0), wl.random_convex_polygon_set(700, seed=172, extent=4.0, rows=16)
         ref = reference(eng, oracle, a, b, force_gpu=True, fe=fe)
         assert 0.05 < ref.mean() < 0.9
-        ua, ub = Uploaded(fe, a, offset=1), Uploaded(fe, b)
+        ua, ub = DeviceSet(fe, a, offset=1), DeviceSet(fe, b)
         m, c = run_mask(fe, ua.set, ub.set)
         assert np.array_equal(mask_bits(m, ub.n), ref) and c == int(ref.sum())
         ua.free()

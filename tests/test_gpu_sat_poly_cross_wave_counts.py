@@ -2,12 +2,15 @@
 scene of tests/threshold_cases.py gives every wave one column for each count 0 .. 64, so phase 2 runs its lanes-over-axes form at
 1, 2, 3 .. 15 undecided rows and its per-lane form from kPcSerialMin = 16 on (csrc/c2d_poly_cross.hip), with bars of 4, 5 and 7
 vertices against rows of at most 3, 5 and 16.  tests/test_threshold_cases_cpu.py proves the collisions on the oracle and the undecided
-counts on a numpy restatement of phase 1.  Every comparison is mask against mask or list against list (run_mask / mask_bits of test_gpu_sat_poly_cross.py: guard rows, count)."""
+counts on a numpy restatement of phase 1.  Every comparison is mask against mask or list against list (run_mask / mask_bits of tests/sat_cross_harness.py, run of
+tests/pair_search_harness.py: guard rows and entries, count)."""
 import numpy as np
 import pytest
 
+import pair_search_harness as psh
 import threshold_cases as tc
-from test_gpu_sat_poly_cross import SENTINEL, Uploaded, check, mask_bits, reference, run_mask, run_pairs
+from pair_search_harness import DeviceSet
+from sat_cross_harness import check_mask, mask_bits, reference, run_mask
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +30,7 @@ def test_full_mask(eng, oracle, scene):
     for w, rows in enumerate(tc.WAVE_ROWS):      # from the oracle alone: wave w meets its own column m in min(m, rows)-many rows
         counts = (ref & own)[info["wave"] == w].sum(0)[info["col_wave"] == w]
         assert set(counts.tolist()) == set(range(rows + 1)) and not (ref & ~own).any()
-    check(eng, oracle, a, b, ref=ref)            # two plane placements; mask and count
+    check_mask(eng, oracle, a, b, ref=ref)            # two plane placements; mask and count
 
 
 @pytest.mark.parametrize("row_base,col_base", [(93, 100), (40, 10)])
@@ -40,7 +43,7 @@ def test_upper_with_a_shifted_diagonal(eng, scene, row_base, col_base):
     for w in (0, 2):   # some of the wave's rows lose tested bits of their own columns' words, others keep them all
         block = tested[info["wave"] == w][:, (info["col_wave"] == w) & (np.arange(n_b) // 64 == np.flatnonzero(info["col_wave"] == w)[0] // 64)]
         assert block.any() and not block.all() and len({int(r.sum()) for r in block}) > 8
-    ua, ub = Uploaded(eng, a, offset=1, stride=n_a + 3), Uploaded(eng, b, offset=2)
+    ua, ub = DeviceSet(eng, a, offset=1, stride=n_a + 3), DeviceSet(eng, b, offset=2)
     m, c = run_mask(eng, ua.set, ub.set, upper=True, row_base=row_base, col_base=col_base)
     got = mask_bits(m, n_b)
     assert np.array_equal(got, ref & tested), f"{int((got != (ref & tested)).sum())} results differ"
@@ -53,10 +56,9 @@ def test_upper_with_a_shifted_diagonal(eng, scene, row_base, col_base):
 def test_pair_list(eng, scene):
     a, b, _, ref = scene
     want = np.argwhere(ref).astype(np.uint32)
-    ua, ub = Uploaded(eng, a), Uploaded(eng, b, offset=3, stride=b[0].shape[1] + 5)
-    p, c = run_pairs(eng, ua.set, ub.set, len(want))
-    assert c == len(want) and np.array_equal(p[:c], want)
-    assert (p[c:].view(np.uint64) == SENTINEL).all(), "written past the capacity"
+    ua, ub = DeviceSet(eng, a), DeviceSet(eng, b, offset=3, stride=b[0].shape[1] + 5)
+    why = psh.compare(*psh.run(eng, psh.poly_cross(eng, ua, ub), len(want)), want)
+    assert why is None, why
     ua.free()
     ub.free()
     eng.check_async()
@@ -67,4 +69,4 @@ def test_shuffled_columns(eng, oracle, scene):
     a, b, info, ref = scene
     perm = np.random.default_rng(3).permutation(b[0].shape[1])
     assert len(set(info["col_m"][perm[:64]].tolist())) > 32 and set(b[2][perm[:64]].tolist()) == {4, 5, 7}
-    check(eng, oracle, a, (b[0][:, perm], b[1][:, perm], b[2][perm]), ref=ref[:, perm])
+    check_mask(eng, oracle, a, (b[0][:, perm], b[1][:, perm], b[2][perm]), ref=ref[:, perm])

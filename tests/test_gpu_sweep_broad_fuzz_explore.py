@@ -1,75 +1,17 @@
 """The exploring leg of the swept broad phase's fuzzer (tests/tools/sweep_broad_fuzz.py), after tests/test_gpu_cast_fuzz_explore.py: the
-generator of the fixed-seed leg (test_gpu_sweep_broad.py test_fuzz_at_a_fixed_seed), seeded from the commit under test (tests/tools/fuzz_seed.py)
-and run for a time budget instead of a configuration count.  Configuration i is drawn from np.random.default_rng([leg seed, i]), so
-    C2D_FUZZ_SEED=<base seed printed> C2D_FUZZ_INDEX=<i> python -m pytest tests/test_gpu_sweep_broad_fuzz_explore.py -m gpu
-runs exactly that one.  $C2D_FUZZ_SECONDS, default 40, is divided by eight as for the other per-configuration legs: 5 s.  The seed is
-printed BEFORE the leg starts (past pytest's capture) and every configuration is named, before it runs, in
-$C2D_FUZZ_TRACE_DIR/sweep_broad.txt (default: build/fuzz_trace under the repository, which git ignores).  Over its run the leg must have compared a
-pair that touches only in motion and a pair that never touches."""
-import importlib.util
-import os
-import time
-
-import numpy as np
+generator of the fixed-seed leg (test_gpu_sweep_broad.py test_fuzz_at_a_fixed_seed) through tests/fuzz_explore_leg.py, which says how it
+is seeded, replayed (C2D_FUZZ_SEED / C2D_FUZZ_INDEX with this file) and traced ($C2D_FUZZ_TRACE_DIR/sweep_broad.txt).  Over its run the
+leg must have compared a pair that touches only in motion and a pair that never touches."""
 import pytest
+
+import fuzz_explore_leg
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 LEG, LEG_INDEX = "sweep_broad", 18      # (the seed offset continues the table of tests/test_gpu_fuzz_explore.py; 17 is the casts')
-
-
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+TOOL = "sweep_broad_fuzz"
+PROOF = {"pairs that touch only in motion": ("moving_hits",), "misses": ("misses",)}      # what the run must have compared: wording -> keys of the tool's LAST
 
 
 def test_sweep_broad_differential_fuzz_at_this_commits_seed(eng, oracle, wl, capsys):   # (`oracle`: sizes the OpenMP team to the box's CPU share)
-    base, origin = _tool("fuzz_seed").commit_seed()
-    seed = (base + 0x3C6EF35F * LEG_INDEX) & 0x7FFFFFFF
-    budget = float(os.environ.get("C2D_FUZZ_SECONDS", "40")) / 8
-    only = os.environ.get("C2D_FUZZ_INDEX")
-    fz = _tool("sweep_broad_fuzz")
-    trace_dir = os.environ.get("C2D_FUZZ_TRACE_DIR") or os.path.join(ROOT, "build", "fuzz_trace")
-    try:
-        os.makedirs(trace_dir, exist_ok=True)
-        trace = open(os.path.join(trace_dir, LEG + ".txt"), "w")
-    except OSError:   # a read-only checkout: the trace goes where the box lets it
-        import tempfile
-
-        trace_dir = tempfile.mkdtemp(prefix="c2d_fuzz_trace_")
-        trace = open(os.path.join(trace_dir, LEG + ".txt"), "w")
-    with capsys.disabled():
-        print(f"\n[fuzz] {LEG}: seed {seed} = base seed {base} ({origin}) + leg offset, " + (f"{budget:.0f} s" if only is None else f"configuration {only} alone")
-              + f"; reproduce with C2D_FUZZ_SEED={base} C2D_FUZZ_INDEX=<index of the configuration>; configurations named in {trace.name}", flush=True)
-    trace.write(f"# {LEG}: seed {seed}, base seed {base} ({origin})\n")
-    last = {"text": "(none yet)"}
-
-    def announce(text):
-        last["text"] = text
-        trace.write(text + "\n")
-        trace.flush()
-        os.fsync(trace.fileno())
-
-    t0, i, done = time.time(), 0 if only is None else int(only), 0
-    hit = miss = False
-    try:
-        while time.time() - t0 < budget:
-            ok, what = fz.one(eng, np.random.default_rng([seed, i]), i, announce)
-            hit, miss = hit or fz.LAST["moving_hits"] > 0, miss or fz.LAST["misses"] > 0
-            assert ok, f"{LEG}: differs from the reference at seed {seed} (C2D_FUZZ_SEED={base} C2D_FUZZ_INDEX={i}, {origin}), {last['text']}; {what}"
-            i, done = i + 1, done + 1
-            if only is not None:
-                break
-    finally:
-        trace.write(f"# {done} configurations completed in {time.time() - t0:.1f} s\n")
-        trace.close()
-    with capsys.disabled():
-        print(f"[fuzz] {LEG}: {done} configurations in {time.time() - t0:.1f} s, 0 differences", flush=True)
-    if only is not None:
-        return
-    assert done >= 3, f"{LEG}: only {done} configurations fit into {budget} s"
-    assert hit and miss, f"{LEG}: {done} configurations compared pairs that touch only in motion: {hit}, misses: {miss}"
+    fuzz_explore_leg.run(eng, wl, capsys, LEG, LEG_INDEX, TOOL, PROOF)

@@ -7,6 +7,7 @@ import pytest
 import distance_ref
 import near_broad_harness as nh
 import near_broad_ref as ref
+import pair_search_harness as psh
 
 F32 = np.float32
 
@@ -14,8 +15,8 @@ F32 = np.float32
 @pytest.mark.parametrize("upper", [False, True])
 @pytest.mark.parametrize("max_dist", [0.0, 0.25, 2.5, 25.0])
 def test_prefiltered_route_equals_the_literal_one(wl, max_dist, upper):
-    a = nh.sparse_scene(wl, 150, 41)
-    b = a if upper else nh.sparse_scene(wl, 111, 42, rows=12, kmax=12)
+    a = psh.sparse_set(wl, 150, 41)
+    b = a if upper else psh.sparse_set(wl, 111, 42, rows=12, kmax=12)
     a = tuple(np.array(x) for x in a)
     if not upper:
         a[0][:, 5] *= F32(2.0 ** 55)              # not tame: never dropped by the prefilter
@@ -38,7 +39,7 @@ def test_prefiltered_route_equals_the_literal_one(wl, max_dist, upper):
 def test_the_bounds_decide_most_pairs_and_only_rightly(wl):
     """on a sparse scene at the GPU tests' largest margin the bounds are no dead code (most listed pairs are `near`, most others `apart`)
     and never contradict the judge"""
-    a, b = nh.sparse_scene(wl, 300, 43), nh.sparse_scene(wl, 187, 44, rows=8, kmax=8)
+    a, b = psh.sparse_set(wl, 300, 43), psh.sparse_set(wl, 187, 44, rows=8, kmax=8)
     ii, jj = np.repeat(np.arange(300), 187), np.tile(np.arange(187), 300)
     tame_a, tame_b = ref._extent(a)[5], ref._extent(b)[5]
     rec = distance_ref.poly_distances(a, b, ii, jj)
@@ -53,7 +54,7 @@ def test_the_bounds_decide_most_pairs_and_only_rightly(wl):
 def test_candidate_d2_restates_the_distance_rule_bit_for_bit(wl):
     """the smallest candidate_d2 over every edge and vertex of both sides is the record's dist, squared root and all, where the pair is
     no hit: on a sparse scene, on near-degenerate slivers and with points and segments"""
-    a, b = nh.sparse_scene(wl, 60, 45), nh.sparse_scene(wl, 50, 46, rows=12, kmax=12)
+    a, b = psh.sparse_set(wl, 60, 45), psh.sparse_set(wl, 50, 46, rows=12, kmax=12)
     a, b = tuple(np.array(x) for x in a), tuple(np.array(x) for x in b)
     a[1][:, :10] *= F32(1e-4)                      # slivers
     a[2][[11, 12]], b[2][[3, 4]] = [1, 2], [2, 1]
@@ -91,7 +92,7 @@ def test_exact_grid_cases_sit_on_the_compare():
 
 def test_consequences_on_the_judge(wl):
     """the list contains the hit pairs, grows with max_dist, and holds exactly the pairs whose record passes the compare"""
-    a, b = nh.sparse_scene(wl, 120, 51), nh.sparse_scene(wl, 90, 52)
+    a, b = psh.sparse_set(wl, 120, 51), psh.sparse_set(wl, 90, 52)
     ii, jj = np.repeat(np.arange(120), 90), np.tile(np.arange(90), 120)
     rec = distance_ref.poly_distances(a, b, ii, jj)
     last = set()

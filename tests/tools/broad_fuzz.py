@@ -17,14 +17,15 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path.insert(0, ROOT)
+for p in (os.path.dirname(HERE), ROOT):
+    if p not in sys.path:
+        sys.path.insert(0, p)
 from __graft_entry__ import load_package  # noqa: E402
+from pair_search_harness import GUARD, SENTINEL  # noqa: E402  (the guard entries around a list, as run() of the harness lays them)
 
 pkg = load_package()
 wl = importlib.import_module("c2d_amd.workloads")
 F = np.float32
-SENTINEL = np.uint64(0xA5A5A5A5A5A5A5A5)
-GUARD = 4
 PILES = [0, 0, 20, 40, 600, 1100, 1300]        # members per side: beyond 16 hits, beyond 512, beyond 1024 candidates
 LAST = {}
 

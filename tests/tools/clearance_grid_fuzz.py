@@ -22,6 +22,7 @@ for p in (TESTS, os.path.dirname(TESTS)):
 import clearance_grid_harness as gh  # noqa: E402
 import clearance_grid_ref as ref  # noqa: E402
 import near_broad_ref as nref  # noqa: E402
+import pair_search_harness as psh  # noqa: E402
 
 
 def _tool(name):
@@ -134,8 +135,8 @@ def one(eng, rng, idx, announce=None):
         announce(what)
     a, b, place = c["a"], c["b"], c["place"]
     n_a, n_b = a[0].shape[1], b[0].shape[1]
-    A = gh.Set(eng, a, None, offset=place[0][0], stride=n_a + place[0][1])
-    B = gh.Set(eng, b, None, offset=place[1][0], stride=n_b + place[1][1]) if c["mode"] == "two" and n_b else A
+    A = psh.DeviceSet(eng, a, offset=place[0][0], stride=n_a + place[0][1])
+    B = psh.DeviceSet(eng, b, offset=place[1][0], stride=n_b + place[1][1]) if c["mode"] == "two" and n_b else A
     b_set = B.set if n_b else eng.poly_set(A.px, A.py, None, 0, b[0].shape[0], 0)      # an empty B: only its `rows` is looked at
     try:
         got = gh.call(eng, A.set, b_set, n_a, c["max_dist"], expect_error=c["bad"], **c["kw"])

@@ -5,7 +5,7 @@ both sides of the wave, block and tile edges, row layouts, vertex-count ranges w
 polygons, outliers, huge coordinates, NaN / inf in real slots, junk in the padded slots), now and then a vertex count out of range,
 strides and pointer offsets, d_k == NULL, two sets, one set against itself (the same memory), C2D_CROSS_UPPER, and a margin per
 configuration: 0, -0, the smallest subnormal, a thousandth, a thirtieth, a third of and three times a polygon's size, a hundred
-sizes.  draw() makes a configuration and its reference list without a GPU; one() runs it; the judge is near_broad_harness.compare.
+sizes.  draw() makes a configuration and its reference list without a GPU; one() runs it; the judge is pair_search_harness.compare.
 Prints its seed; a mismatch names its configuration.
 usage: near_broad_fuzz.py [configs] [seed]"""
 import importlib.util
@@ -19,8 +19,8 @@ TESTS = os.path.dirname(HERE)
 for p in (TESTS, os.path.dirname(TESTS)):
     if p not in sys.path:
         sys.path.insert(0, p)
-import near_broad_harness as nh  # noqa: E402
 import near_broad_ref as ref  # noqa: E402
+import pair_search_harness as psh  # noqa: E402
 
 
 def _tool(name):
@@ -101,15 +101,15 @@ def one(eng, rng, idx, announce=None):
     if announce is not None:
         announce(what)
     a, b, place = c["a"], c["b"], c["place"]
-    A = nh.Set(eng, a, None, offset=place[0][0], stride=a[0].shape[1] + place[0][1])
-    B = nh.Set(eng, b, None, offset=place[1][0], stride=b[0].shape[1] + place[1][1]) if c["mode"] == "two" else A
+    A = psh.DeviceSet(eng, a, offset=place[0][0], stride=a[0].shape[1] + place[0][1])
+    B = psh.DeviceSet(eng, b, offset=place[1][0], stride=b[0].shape[1] + place[1][1]) if c["mode"] == "two" else A
     try:
-        got, total = nh.run(eng, A, B, c["max_dist"], c["upper"], absent=c["bad"])     # (a vertex count out of range must be reported, by each call)
+        got, total = psh.run(eng, psh.near_broad(eng, A, B, c["max_dist"], c["upper"]), absent=c["bad"])     # (a vertex count out of range must be reported, by each call)
     finally:
         A.free()
         if B is not A:
             B.free()
-    why = nh.compare(got, total, c["want"])
+    why = psh.compare(got, total, c["want"])
     if why is not None:
         return False, what + ": " + why
     return True, what + f" [{LAST['listed']} pairs, {LAST['apart']} of them apart, {LAST['misses']} misses]"

@@ -9,10 +9,13 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+TESTS = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (TESTS, os.path.dirname(TESTS)):
+    if p not in sys.path:
+        sys.path.insert(0, p)
 from __graft_entry__ import load_package  # noqa: E402
 import importlib  # noqa: E402
+import pair_search_harness as psh  # noqa: E402
 
 pkg = load_package()
 wl = importlib.import_module("c2d_amd.workloads")
@@ -50,14 +53,9 @@ def random_set(rng, n, rows):
 
 
 def upload(eng, s, offset, stride):
-    vx, vy, k = s
-    rows, n = vx.shape
-    host = np.full((2, rows * stride + 4), np.nan, np.float32)
-    for p, v in enumerate((vx, vy)):
-        for r in range(rows):
-            host[p, offset + r * stride: offset + r * stride + n] = v[r]
-    d, dk = eng.to_device(host), eng.to_device(k)
-    return eng.poly_set(d.row(0) + 4 * offset, d.row(1) + 4 * offset, dk, n, rows, stride), (d, dk)
+    """(c2d_poly_set, the device arrays to free) in pair_search_harness.DeviceSet's layout, for the tools that manage their own buffers"""
+    u = psh.DeviceSet(eng, s, offset=offset, stride=stride)
+    return u.set, (u.d, u.dk)
 
 
 def one(eng, rng, idx, announce=None):
@@ -67,31 +65,27 @@ def one(eng, rng, idx, announce=None):
     n_a, n_b = int(rng.choice(sizes)), int(rng.choice(sizes))
     self_mode, upper = bool(rng.random() < 0.4), bool(rng.random() < 0.5)
     a, da = random_set(rng, n_a, int(rng.integers(1, 17)))
-    sa, keep = upload(eng, a, int(rng.integers(0, 4)), n_a + int(rng.integers(0, 9)))
+    A = B = psh.DeviceSet(eng, a, offset=int(rng.integers(0, 4)), stride=n_a + int(rng.integers(0, 9)))
     if self_mode:
-        sb, desc = sa, f"config {idx}: self n {n_a} {da} upper {upper}"
+        desc = f"config {idx}: self n {n_a} {da} upper {upper}"
     else:
         b, db = random_set(rng, n_b, int(rng.integers(1, 17)))
-        sb, keep_b = upload(eng, b, int(rng.integers(0, 4)), n_b + int(rng.integers(0, 9)))
-        keep += keep_b
+        B = psh.DeviceSet(eng, b, offset=int(rng.integers(0, 4)), stride=n_b + int(rng.integers(0, 9)))
         desc = f"config {idx}: {n_a} x {n_b}, A {da}, B {db}, upper {upper}"
     if announce is not None:
         announce(desc)
-    d_cnt = eng.zeros(2, np.uint64)
-    eng.sat_poly_cross_pairs(sa, sb, None, 0, d_cnt.ptr, upper=upper)
-    eng.sat_poly_broad_pairs(sa, sb, None, 0, d_cnt.ptr + 8, upper=upper)
-    want_n, got_n = (int(x) for x in d_cnt.get())
-    d_want, d_got = eng.zeros((want_n + 1, 2), np.uint32), eng.zeros((want_n + 1, 2), np.uint32)
-    eng.sat_poly_cross_pairs(sa, sb, d_want, want_n, d_cnt.ptr, upper=upper)
-    eng.sat_poly_broad_pairs(sa, sb, d_got, want_n, d_cnt.ptr + 8, upper=upper)
-    want, got = d_want.get(), d_got.get()
-    for x in list(keep) + [d_cnt, d_want, d_got]:
-        x.free()
-    ok = want_n == got_n and np.array_equal(want, got)
-    LAST.update(hits=want_n, misses=(n_a * sb.n if not upper else sum(max(0, sb.n - 1 - i) for i in range(n_a))) - want_n)
-    if not ok:
-        print(f"MISMATCH {desc}: cross counts {want_n}, broad {got_n}; {int((want != got).any(1).sum())} list entries differ")
-    return ok, (desc, want_n)
+    try:                                                       # (each: a count-only call, then the list between guard entries)
+        want, want_n = psh.run(eng, psh.poly_cross(eng, A, B, upper))
+        got, got_n = psh.run(eng, psh.poly_broad(eng, A, B, upper))
+    finally:
+        A.free()
+        if B is not A:
+            B.free()
+    why = psh.compare(got, got_n, want)
+    LAST.update(hits=want_n, misses=(n_a * B.n if not upper else sum(max(0, B.n - 1 - i) for i in range(n_a))) - want_n)
+    if why is not None:
+        print(f"MISMATCH {desc}: cross counts {want_n}; {why}")
+    return why is None, (desc, want_n)
 
 
 def main():

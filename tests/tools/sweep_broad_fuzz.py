@@ -6,7 +6,7 @@ outliers, huge coordinates, NaN / inf in real slots, junk in the padded slots), 
 and pointer offsets, d_k == NULL, two sets, one set against itself with its own motion (the same memory) and with another motion
 (two sets), C2D_CROSS_UPPER, and the motions of sweep_fuzz.py per set (standing still, all zero, the scale of the scene, a
 hundredth of it, far larger, mixed scales with exact zeros and non-finite components).  draw() makes a configuration and its
-reference list without a GPU; one() runs it; the judge is sweep_broad_harness.compare.  Prints its seed; a mismatch names its
+reference list without a GPU; one() runs it; the judge is pair_search_harness.compare.  Prints its seed; a mismatch names its
 configuration.
 usage: sweep_broad_fuzz.py [configs] [seed]"""
 import importlib.util
@@ -20,7 +20,7 @@ TESTS = os.path.dirname(HERE)
 for p in (TESTS, os.path.dirname(TESTS)):
     if p not in sys.path:
         sys.path.insert(0, p)
-import sweep_broad_harness as sh  # noqa: E402
+import pair_search_harness as psh  # noqa: E402
 import sweep_broad_ref as ref  # noqa: E402
 import sweep_ref  # noqa: E402
 
@@ -97,20 +97,20 @@ def one(eng, rng, idx, announce=None):
     if announce is not None:
         announce(what)
     a, b, place = c["a"], c["b"], c["place"]
-    A = sh.MovingSet(eng, a, c["ma"], offset=place[0][0], stride=a[0].shape[1] + place[0][1])
+    A = psh.DeviceSet(eng, a, c["ma"], offset=place[0][0], stride=a[0].shape[1] + place[0][1])
     if c["mode"] == "two":
-        B = sh.MovingSet(eng, b, c["mb"], offset=place[1][0], stride=b[0].shape[1] + place[1][1])
+        B = psh.DeviceSet(eng, b, c["mb"], offset=place[1][0], stride=b[0].shape[1] + place[1][1])
     elif c["mode"] == "self":
         B = A
     else:                                                      # the same vertex memory, other motion planes
         B = A.with_motion(c["mb"])
     try:
-        got, total = sh.run(eng, A, B, c["upper"], absent=c["bad"])     # (a vertex count out of range must be reported, by each call)
+        got, total = psh.run(eng, psh.sweep_broad(eng, A, B, c["upper"]), absent=c["bad"])     # (a vertex count out of range must be reported, by each call)
     finally:
         A.free()
         if B is not A:
             B.free()
-    why = sh.compare(got, total, c["want"])
+    why = psh.compare(got, total, c["want"])
     if why is not None:
         return False, what + ": " + why
     return True, what + f" [{LAST['hits']} pairs, {LAST['moving_hits']} of them apart at t = 0, {LAST['misses']} misses]"
