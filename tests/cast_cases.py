@@ -1,4 +1,4 @@
-"""Inputs shared by the tests of the shape casts (test_cast_ref_cpu.py, test_cast_cases_cpu.py, test_gpu_casts.py, cast_graph_check.py,
+"""Inputs shared by the tests of the shape casts (test_cast_ref_cpu.py, test_cast_cases_cpu.py, test_gpu_casts.py, best_key_graph_check.py,
 tools/cast_fuzz.py): hand cases that are exact in binary32 with what the contract says of them, the sparse scene with its motions,
 and the constructions that make the main kernel's own decisions visible in `poly`: the slid near-ties of clearance_cases.py set in
 motion (every pair touches at toi = 1/2 in exact arithmetic) and boxes on a 1/64 grid that graze (t_in == t_out) or miss by one grid

@@ -1,6 +1,6 @@
-"""What the tests of c2d_poly_set_casts_grid share (test_gpu_casts_grid.py, test_cast_grid_cases_cpu.py, cast_grid_graph_check.py,
-tools/cast_grid_fuzz.py), built on cast_harness.py and clearance_grid_harness.py without editing either: the call between guard
-bands (the grid call or, for the byte compare, c2d_poly_set_casts on the same arguments), the check that runs both, the sparse scene
+"""What the tests of c2d_poly_set_casts_grid share (test_gpu_casts_grid.py, test_cast_grid_cases_cpu.py, tools/cast_grid_fuzz.py),
+built on cast_harness.py and clearance_grid_harness.py: the frame's call between guard bands (tests/best_key_harness.py) bound to the
+query, the check that runs it beside c2d_poly_set_casts on the same arguments, the sparse scene
 with its per-pair records computed once, the deals of B's indices, and the constructions whose answer depends on the order in which
 the candidates are met.  The judge is cast_ref, unchanged.  The scenes are numpy only, so the CPU tests can reach them; nothing here
 loads libc2d.so."""
@@ -9,6 +9,7 @@ import itertools
 
 import numpy as np
 
+import best_key_harness as best
 import cast_cases as cases
 import cast_harness as ch
 import cast_ref as ref
@@ -30,27 +31,18 @@ Scene, take, take_motion, assert_same = ch.Scene, ch.take, ch.take_motion, ch.as
 
 
 # ---- the device side ----------------------------------------------------------------------------------------------------------
-def call(eng, a_set, b_set, n_a, a_motion=None, b_motion=None, capacity=None, expect_error=False, band=None, grid=True, **kw):
-    """c2d_poly_set_casts_grid (grid=False: c2d_poly_set_casts) into a buffer between guard bands -> the n_a records; the bands and
-    every record at or beyond n_a must be untouched; under expect_error the next synchronise reports status -1, once.
-    band: a buffer of h.banded(eng, cap, DT) to use again."""
-    cap = max(n_a, 4) if capacity is None else capacity
-    method = eng.poly_set_casts_grid if grid else eng.poly_set_casts
-    return h.banded_call(eng, DT, n_a, lambda ptr: method(a_set, b_set, a_motion, b_motion, out=ptr, **kw), cap, expect_error, band)[:n_a].copy()
+call = functools.partial(best.call, best.CASTS_GRID)                # call(eng, a_set, b_set, n_a, a_motion=None, b_motion=None, capacity=None, expect_error=False, band=None, **kw)
+twice = functools.partial(best.twice, best.CASTS_GRID)              # twice(eng, a_set, b_set, n_a, what, **kw): the call, run twice: the same bytes
 
 
 def check(eng, a_set, b_set, n_a, want, what, nxm=True, **kw):
     """the grid call, twice (the same bytes), against the reference's records `want` (None: not judged here); then
     c2d_poly_set_casts on the same arguments in the same run: the same bytes.  Returns the records."""
-    got, again = call(eng, a_set, b_set, n_a, **kw), call(eng, a_set, b_set, n_a, **kw)
-    assert got.tobytes() == again.tobytes(), f"{what}: two runs differ"
+    got = twice(eng, a_set, b_set, n_a, what, **kw)
     if want is not None:
         assert_same(got, want, what)
     if nxm:
-        full = call(eng, a_set, b_set, n_a, grid=False, **kw)
-        if got.tobytes() != full.tobytes():
-            q = int(np.flatnonzero((got.view(np.uint8).reshape(n_a, -1) != full.view(np.uint8).reshape(n_a, -1)).any(axis=1))[0])
-            raise AssertionError(f"{what}: the bytes differ from c2d_poly_set_casts'; first at {q}: grid {got[q]}, N x M {full[q]}")
+        best.check_against_sibling(got, ch.call(eng, a_set, b_set, n_a, **kw), what, ("grid", "c2d_poly_set_casts"))
     return got
 
 

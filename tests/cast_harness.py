@@ -1,6 +1,6 @@
-"""What the GPU tests of the shape casts share (test_gpu_casts.py, tools/cast_fuzz.py), after clearance_harness.py: the call between
-guard bands, the reference of a scene whose polygons repeat (computed on the distinct polygons and indexed), and the comparison with
-its message.  The per-pair records of the constructions of cast_cases.py are computed once per process here, for
+"""What the GPU tests of the shape casts share (test_gpu_casts.py, tools/cast_fuzz.py), after clearance_harness.py: the frame's
+call between guard bands and its comparison (tests/best_key_harness.py) bound to c2d_poly_set_casts, and the reference of a scene whose
+polygons repeat (computed on the distinct polygons and indexed).  The per-pair records of the constructions of cast_cases.py are computed once per process here, for
 test_cast_cases_cpu.py and the GPU tests alike.  A plain module on numpy and the numpy references: it never loads libc2d.so."""
 import functools
 
@@ -16,16 +16,9 @@ from clearance_harness import take  # noqa: F401  (the set of polygons s[idx[0]]
 DT = ref.CAST_DT
 
 
-def call(eng, a_set, b_set, n_a, a_motion=None, b_motion=None, capacity=None, expect_error=False, band=None, **kw):
-    """c2d_poly_set_casts into a buffer between guard bands -> the n_a records; the bands and every record at or beyond n_a must be
-    untouched; under expect_error the next synchronise reports status -1, once.  a_motion, b_motion: None or the two plane pointers.
-    band: a buffer of h.banded(eng, cap, DT) to use again (it is filled with the band's byte first and stays the caller's)"""
-    cap = max(n_a, 4) if capacity is None else capacity
-    return h.banded_call(eng, DT, n_a, lambda ptr: eng.poly_set_casts(a_set, b_set, a_motion, b_motion, out=ptr, **kw), cap, expect_error, band)[:n_a].copy()
-
-
-twice = functools.partial(best.twice, call)             # twice(eng, a_set, b_set, n_a, what, **kw): the call, run twice: the same bytes
-assert_same = functools.partial(best.assert_same, ref)  # assert_same(got, want, what)
+call = functools.partial(best.call, best.CASTS)                # call(eng, a_set, b_set, n_a, a_motion=None, b_motion=None, capacity=None, expect_error=False, band=None, **kw)
+twice = functools.partial(best.twice, best.CASTS)              # twice(eng, a_set, b_set, n_a, what, **kw): the call, run twice: the same bytes
+assert_same = functools.partial(best.assert_same, best.CASTS)  # assert_same(got, want, what)
 
 
 def take_motion(m, idx):

@@ -1,5 +1,5 @@
 """Inputs shared by the tests of the clearance query (test_clearance_ref_cpu.py, test_clearance_bound_cpu.py, test_gpu_clearances.py,
-clearance_graph_check.py, tools/clearance_fuzz.py): hand cases that are exact in binary32 with what the contract says of them, the
+best_key_graph_check.py, tools/clearance_fuzz.py): hand cases that are exact in binary32 with what the contract says of them, the
 sparse clearance scene, the adversarial set of the certified bound, the numpy statement of a polygon's vertex box, and two
 constructions that make the main kernel's own decisions visible in `poly`: the hard input classes of contact_cases.py beside a witness
 (witness_batches) and obstacles that tie within a few ulp of dist (slid_near_ties); tests/test_clearance_cases_cpu.py holds what they

@@ -1,16 +1,16 @@
-"""What the tests of c2d_poly_set_clearances_grid share (test_gpu_clearances_grid.py, clearance_grid_graph_check.py,
-tools/clearance_grid_fuzz.py), modelled on clearance_harness.py: the call between guard bands, the comparison with its message, the
-sparse scenes with the margins taken from the judge's own distances, and the constructions whose answer depends on the order in which
+"""What the tests of c2d_poly_set_clearances_grid share (test_gpu_clearances_grid.py, tools/clearance_grid_fuzz.py), modelled on
+clearance_harness.py: the frame's call between guard bands and its comparisons (tests/best_key_harness.py) bound to the query, the
+check that runs it beside c2d_poly_set_clearances, the sparse scenes with the margins taken from the judge's own distances, and the constructions whose answer depends on the order in which
 the candidates are met.  The scenes and the judge are numpy only, so the CPU tests can reach them; nothing here loads libc2d.so."""
 import functools
 import itertools
 
 import numpy as np
 
+import best_key_harness as best
 import clearance_grid_ref as ref
 import near_broad_harness as nh
 import near_broad_ref as nref
-import pair_list_harness as h
 import pair_search_harness as psh
 
 DT = ref.CLEARANCE_DT
@@ -23,23 +23,9 @@ REACH = 3.0 * nh.SIZE          # the judge looks this far for the scenes' neares
 
 
 # ---- the device side ----------------------------------------------------------------------------------------------------------
-def call(eng, a_set, b_set, n_a, max_dist, capacity=None, expect_error=False, band=None, grid=True, **kw):
-    """c2d_poly_set_clearances_grid (grid=False: c2d_poly_set_clearances, which has no max_dist) into a buffer between guard bands ->
-    the n_a records; the bands and every record at or beyond n_a must be untouched; under expect_error the next synchronise reports
-    status -1, once.  band: a buffer of h.banded(eng, cap, DT) to use again."""
-    cap = max(n_a, 4) if capacity is None else capacity
-    if grid:
-        launch = lambda ptr: eng.poly_set_clearances_grid(a_set, b_set, max_dist, ptr, **kw)   # noqa: E731
-    else:
-        launch = lambda ptr: eng.poly_set_clearances(a_set, b_set, ptr, **kw)   # noqa: E731
-    return h.banded_call(eng, DT, n_a, launch, cap, expect_error, band)[:n_a].copy()
-
-
-def assert_same(got, want, what):
-    ok = ref.same(got, want)
-    if not ok.all():
-        q = int(np.flatnonzero(~ok)[0])
-        raise AssertionError(f"{what}: {int((~ok).sum())} of {len(want)} records differ; first at {q}: got {got[q]}, want {want[q]}")
+call = functools.partial(best.call, best.CLEARANCES_GRID)                # call(eng, a_set, b_set, n_a, max_dist, capacity=None, expect_error=False, band=None, **kw)
+twice = functools.partial(best.twice, best.CLEARANCES_GRID)              # twice(eng, a_set, b_set, n_a, max_dist, what, **kw): the call, run twice: the same bytes
+assert_same = functools.partial(best.assert_same, best.CLEARANCES_GRID)  # assert_same(got, want, what)
 
 
 def check(eng, a, b, max_dist, what, want=None, place_a=(1, 3), place_b=(2, 0), with_k=True, expect_error=False, all_winners=None, **kw):
@@ -50,9 +36,7 @@ def check(eng, a, b, max_dist, what, want=None, place_a=(1, 3), place_b=(2, 0), 
     B = A if b is None else psh.DeviceSet(eng, b, offset=place_b[0], stride=b[0].shape[1] + place_b[1], with_k=with_k)
     n_a = a[0].shape[1]
     try:
-        got = call(eng, A.set, B.set, n_a, max_dist, expect_error=expect_error, **kw)
-        again = call(eng, A.set, B.set, n_a, max_dist, expect_error=expect_error, **kw)
-        assert got.tobytes() == again.tobytes(), f"{what}: two runs differ"
+        got = twice(eng, A.set, B.set, n_a, max_dist, what, expect_error=expect_error, **kw)
         if want is None:
             want = ref.clearances(a, a if b is None else b, max_dist, **kw)
         assert_same(got, want, what)
@@ -60,8 +44,8 @@ def check(eng, a, b, max_dist, what, want=None, place_a=(1, 3), place_b=(2, 0), 
             all_winners = bool((want["poly"] != NO_POLY).all())
         if all_winners and n_a:
             assert (want["poly"] != NO_POLY).all(), what
-            full = call(eng, A.set, B.set, n_a, None, grid=False, expect_error=expect_error, **kw)
-            assert got.tobytes() == full.tobytes(), f"{what}: every query has a winner, and the bytes differ from c2d_poly_set_clearances'"
+            full = best.call(best.CLEARANCES, eng, A.set, B.set, n_a, expect_error=expect_error, **kw)
+            best.check_against_sibling(got, full, what + ": every query has a winner", ("grid", "c2d_poly_set_clearances"))
     finally:
         A.free()
         if B is not A:

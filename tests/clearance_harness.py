@@ -1,5 +1,6 @@
-"""What the GPU tests of the clearance query share (test_gpu_clearances.py, tools/clearance_fuzz.py): the call between guard bands, the
-reference of a scene whose polygons repeat (computed on the distinct polygons and indexed), and the comparison with its message.
+"""What the GPU tests of the clearance query share (test_gpu_clearances.py, tools/clearance_fuzz.py): the frame's call between guard
+bands and its comparison (tests/best_key_harness.py) bound to c2d_poly_set_clearances, and the reference of a scene whose polygons
+repeat (computed on the distinct polygons and indexed).
 The per-pair records of the constructions of clearance_cases.py (witness_batches, slid_near_ties) are computed once per process here, for
 test_clearance_cases_cpu.py and the GPU tests alike.  A plain module on numpy and the numpy references: it never loads libc2d.so."""
 import functools
@@ -9,21 +10,13 @@ import numpy as np
 import best_key_harness as best
 import clearance_cases as cases
 import clearance_ref as ref
-import pair_list_harness as h
 
 DT = ref.CLEARANCE_DT
 
 
-def call(eng, a_set, b_set, n_a, capacity=None, expect_error=False, band=None, **kw):
-    """c2d_poly_set_clearances into a buffer between guard bands -> the n_a records; the bands and every record at or beyond n_a
-    must be untouched; under expect_error the next synchronise reports status -1, once.  band: a buffer of h.banded(eng, cap, DT) to
-    use again (many small calls: it is filled with the band's byte first and stays the caller's)"""
-    cap = max(n_a, 4) if capacity is None else capacity
-    return h.banded_call(eng, DT, n_a, lambda ptr: eng.poly_set_clearances(a_set, b_set, ptr, **kw), cap, expect_error, band)[:n_a].copy()
-
-
-twice = functools.partial(best.twice, call)             # twice(eng, a_set, b_set, n_a, what, **kw): the call, run twice: the same bytes
-assert_same = functools.partial(best.assert_same, ref)  # assert_same(got, want, what)
+call = functools.partial(best.call, best.CLEARANCES)                # call(eng, a_set, b_set, n_a, capacity=None, expect_error=False, band=None, **kw) -> DT[n_a]
+twice = functools.partial(best.twice, best.CLEARANCES)              # twice(eng, a_set, b_set, n_a, what, **kw): the call, run twice: the same bytes
+assert_same = functools.partial(best.assert_same, best.CLEARANCES)  # assert_same(got, want, what)
 
 
 def take(s, idx):

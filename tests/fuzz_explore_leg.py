@@ -9,21 +9,15 @@ printed BEFORE the leg starts (past pytest's capture) and every configuration is
 $C2D_FUZZ_TRACE_DIR/<leg>.txt (default: build/fuzz_trace under the repository, which git ignores).  Each file states its leg's name,
 its index (the seed offset, which continues the table of tests/test_gpu_fuzz_explore.py: append only), its tool, and what the run
 must have compared for it not to be vacuous."""
-import importlib.util
 import os
 import time
 
 import numpy as np
 
+from best_key_harness import load_tool as _tool
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-
-
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def run(eng, wl, capsys, leg, leg_index, tool, proof, takes_wl=False):

@@ -1,10 +1,15 @@
-"""The frame of the GPU tests of c2d_poly_ray_casts: ray planes on the device at chosen 4-byte offsets, and cast() with guard bands
-around the output (tests/pair_list_harness.py: banded / unband).  A plain module on numpy and the numpy reference only: it never
-loads libc2d.so, so tests/ray_graph_check.py can import it after torch."""
+"""What the GPU tests of c2d_poly_ray_casts and c2d_poly_ray_casts_grid have of their own: ray planes on the device at chosen 4-byte
+offsets, and the grid check.  The call between guard bands, the call run twice and the comparison are the frame's
+(tests/best_key_harness.py), bound to the two ray queries here.  A plain module on numpy and the numpy references only: it never
+loads libc2d.so."""
+import functools
+
 import numpy as np
 
-import pair_list_harness as h
+import best_key_harness as best
+import ray_grid_ref as gref
 import ray_ref as ref
+from pair_list_harness import Uploaded
 
 DT = ref.RAY_HIT_DT
 
@@ -25,14 +30,25 @@ class RaysOnDevice:
         self.d.free()
 
 
-def cast(eng, rays, n_rays, b_set, col_base=0, capacity=None, expect_error=False):
-    """c2d_poly_ray_casts on the first n_rays rays of a RaysOnDevice into a banded output of `capacity` records -> RAY_HIT_DT[capacity];
-    the bands and every record at or beyond n_rays must be untouched; under expect_error the synchronise reports status -1, once"""
-    return h.banded_call(eng, DT, n_rays, lambda ptr: eng.poly_ray_casts(rays.ptrs, n_rays, b_set, ptr, col_base=col_base), capacity, expect_error)
+cast = functools.partial(best.call, best.RAY_CASTS)            # cast(eng, rays, n_rays, b_set, col_base=0, capacity=None, expect_error=False) -> DT[capacity]
+cast_grid = functools.partial(best.call, best.RAY_CASTS_GRID)  # the same through c2d_poly_ray_casts_grid
+twice = functools.partial(best.twice, best.RAY_CASTS)          # twice(eng, rays, n_rays, b_set, what, **kw): the call, run twice: the same bytes
+twice_grid = functools.partial(best.twice, best.RAY_CASTS_GRID)
+assert_same = functools.partial(best.assert_same, best.RAY_CASTS)      # assert_same(got, want, what): "... first at ray q ..."
 
 
-def assert_same(got, want, what):
-    ok = ref.same(got, want)
-    if not ok.all():
-        q = int(np.flatnonzero(~ok)[0])
-        raise AssertionError(f"{what}: {int((~ok).sum())} of {len(want)} records differ; first at ray {q}: got {got[q]}, want {want[q]}")
+def check_grid(eng, rays, b, what, n_rays=None, uploaded=None, on_device=None, **kw):
+    """upload (unless handed in), run c2d_poly_ray_casts_grid twice, compare with the grid reference -> (records, the call's counters)"""
+    n = len(rays[0]) if n_rays is None else n_rays
+    dr = RaysOnDevice(eng, rays) if on_device is None else on_device
+    ub = Uploaded(eng, b) if uploaded is None else uploaded
+    try:
+        got = twice_grid(eng, dr, n, ub.set, what, **kw)
+        stats = eng.poly_ray_casts_grid_stats()
+        assert_same(got, gref.ray_casts(tuple(r[:n] for r in rays), b, col_base=kw.get("col_base", 0)), what)
+    finally:
+        if on_device is None:
+            dr.free()
+        if uploaded is None:
+            ub.free()
+    return got, stats

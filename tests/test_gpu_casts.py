@@ -10,7 +10,6 @@ test_every_pairs_hit_at_zero_through_a_witness   every pair of the hard batches 
 test_near_ties_in_motion                         130 obstacles all touched at 1/2 in exact arithmetic, apart by rounding alone
 test_grazes                                      t_in == t_out hits beside misses by one grid step"""
 import ctypes as C
-import importlib.util
 import os
 import subprocess
 import sys
@@ -20,6 +19,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import best_key_harness as best  # noqa: E402
 import cast_cases as cases  # noqa: E402
 import cast_harness as ch  # noqa: E402
 import cast_ref as ref  # noqa: E402
@@ -32,16 +32,9 @@ from pair_list_harness import Motion, Uploaded  # noqa: E402
 pytestmark = pytest.mark.gpu
 F = np.float32
 FUZZ_SEED = 20518
-TILE_ROWS, TILE_COLS = 256, 64          # queries per block and polygons per staged tile of the kernel (csrc/c2d_cast.hip)
 N_B_SIZES = [1, 2, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513]
 HARD_NAMES = ["clockwise", "clockwise_both", "repeated_vertices", "k1_k2", "touching", "equal_shapes", "equal_boxes", "scale_1e30", "scale_1e-30",
               "scale_1e-42", "scale_1e18", "scale_1e-18", "non_finite_vertex0", "non_finite_later_vertex", "overflowing_len2"]
-
-
-def strips_of(eng, n_a, n_b):
-    """the strip rule of csrc/c2d_ray_strips.hpp with the library's target of eight blocks per CU"""
-    row_tiles, col_tiles = -(-n_a // TILE_ROWS), -(-n_b // TILE_COLS)
-    return min(col_tiles, max(1, 8 * eng.info()["compute_units"] // row_tiles))
 
 
 @pytest.fixture(scope="module")
@@ -79,7 +72,7 @@ def test_every_number_of_queries(eng, many_queries):
     for n in contact_cases.LIST_LENGTHS:
         got = ch.call(eng, sc.a.sub(0, n), sc.b.set, n, **sc.motions())
         ch.assert_same(got, want[:n], f"{n} queries")
-        assert strips_of(eng, max(n, 1), 24) == 1
+        assert best.strips_of(eng.info()["compute_units"], max(n, 1), 24) == 1
     eng.check_async()
     sc.free()
 
@@ -94,7 +87,7 @@ def test_every_number_of_polygons(eng, sparse):
         want = ref.reduce(S[:, :n_b], bad_a, bad_b[:n_b])
         got = ch.twice(eng, sc.a.set, sc.b.sub(0, n_b), 64, f"{n_b} polygons", **sc.motions())
         ch.assert_same(got, want, f"{n_b} polygons")
-        assert strips_of(eng, 64, n_b) == -(-n_b // TILE_COLS)
+        assert best.strips_of(eng.info()["compute_units"], 64, n_b) == -(-n_b // best.TILE_COLS)
     eng.check_async()
     sc.free()
 
@@ -108,7 +101,7 @@ def test_one_strip_walks_every_tile(eng, sparse):
     ub, db = Uploaded(eng, b), Motion(eng, mb)
     bad_a, bad_b = bads(a, b)
     for n_b in (64, 130):
-        assert strips_of(eng, n, n_b) == 1
+        assert best.strips_of(eng.info()["compute_units"], n, n_b) == 1
         want = ref.reduce(S[:, :n_b], bad_a, bad_b[:n_b])[ia]
         got = ch.call(eng, ua.set, ub.sub(0, n_b), n, a_motion=da.ptrs, b_motion=db.ptrs)
         ch.assert_same(got, want, f"2^19 + 5 queries against {n_b}")
@@ -125,8 +118,8 @@ def test_between_one_strip_and_one_per_tile(eng, sparse, s):
     a, b, ma, mb, S = sparse
     cus = eng.info()["compute_units"]
     row_tiles = 8 * cus // s
-    n = TILE_ROWS * row_tiles - 251
-    strips = strips_of(eng, n, 513) if n > 0 else 0
+    n = best.TILE_ROWS * row_tiles - 251
+    strips = best.strips_of(eng.info()["compute_units"], n, 513) if n > 0 else 0
     if not (1 < strips < 9 and 9 % strips != 0):
         pytest.skip(f"{cus} compute units give {strips} strips for 8 * cus / {s} row tiles against 9 column tiles: not strictly between, unevenly split")
     ia = np.random.default_rng(9561 + s).integers(0, 64, n)
@@ -236,7 +229,7 @@ def test_order_independence_by_construction(eng, sparse):
         want = ref.reduce(S[:, ib], bad_a, bad_b[ib])
         got = ch.twice(eng, ua.set, ub.set, 64, name, a_motion=da.ptrs, b_motion=db.ptrs)
         ch.assert_same(got, want, name)
-        assert strips_of(eng, 64, len(ib)) == -(-len(ib) // TILE_COLS)
+        assert best.strips_of(eng.info()["compute_units"], 64, len(ib)) == -(-len(ib) // best.TILE_COLS)
         ub.free()
         db.free()
     eng.check_async()
@@ -295,7 +288,7 @@ def test_every_pairs_hit_at_zero_through_a_witness(eng, wl, name):
         idx = np.repeat(np.arange(n_b), width)
         ms = tuple(np.where(is_w, F(0), m[idx]).astype(F) for m in mb)
         ub, db = Uploaded(eng, s), Motion(eng, ms)
-        assert strips_of(eng, n_a, width) == -(-width // TILE_COLS)
+        assert best.strips_of(eng.info()["compute_units"], n_a, width) == -(-width // best.TILE_COLS)
         for j in range(n_b):
             what = f"{name}, {layout}, obstacle {j}"
             got = ch.call(eng, ua.set, ub.sub(width * j, width * (j + 1)), n_a, band=band, col_base=width * j, a_motion=da.ptrs, b_motion=db.sub(width * j))
@@ -328,7 +321,7 @@ def test_near_ties_in_motion(eng):
                 ub = Uploaded(eng, ch.take(b, ib))
                 got = ch.twice(eng, ua.set, ub.set, 64, what, a_motion=da.ptrs)
                 ch.assert_same(got, ch.indexed_reference(a, ia, b, ib, S=S), what)
-                assert strips_of(eng, 64, len(ib)) == -(-len(ib) // TILE_COLS)
+                assert best.strips_of(eng.info()["compute_units"], 64, len(ib)) == -(-len(ib) // best.TILE_COLS)
                 ub.free()
             ua.free()
             da.free()
@@ -425,39 +418,23 @@ def test_argument_errors(eng, pkg):
     """every refusal with a ctx: status -1, a message that names the call, nothing enqueued"""
     lib, B = eng.lib, pkg.binding
     d = eng.zeros(1024, np.float32)
-    out = eng.empty(8, ref.CAST_DT)
+    out = eng.empty(9, ref.CAST_DT)                # (the last call below writes eight records eight bytes in)
     good = B._PolySet(16, 8, 0, d.ptr, d.ptr, 0)
     fn = lib.c2d_poly_set_casts
     P = C.c_void_p
 
-    def refused(a, b, m=(None, None, None, None), rb=0, cb=0, flags=0, o=None):
-        rc = fn(eng.h, None if a is None else C.byref(a), None if b is None else C.byref(b), *[None if x is None else P(x) for x in m], rb, cb, flags,
-                P(out.ptr if o is None else o), None)
-        assert rc == -1 and b"c2d_poly_set_casts" in lib.c2d_last_error(eng.h)
+    def status(a, b, rb=0, cb=0, flags=0, o=out.ptr, m=(None, None, None, None)):
+        return fn(eng.h, None if a is None else C.byref(a), None if b is None else C.byref(b), *[None if x is None else P(x) for x in m], rb, cb, flags, P(o), None)
 
-    refused(None, good)
-    refused(good, None)
-    refused(good, good, o=0)
-    for rows in (0, 17):
-        refused(B._PolySet(rows, 8, 0, d.ptr, d.ptr, 0), good)
-        refused(good, B._PolySet(rows, 8, 0, d.ptr, d.ptr, 0))
-        refused(good, B._PolySet(rows, 0, 0, 0, 0, 0))                 # (rows is checked even with n_b == 0)
-    refused(B._PolySet(16, 8, 0, d.ptr + 2, d.ptr, 0), good)           # misaligned planes
-    refused(good, B._PolySet(16, 8, 0, d.ptr, d.ptr + 1, 0))
-    refused(B._PolySet(16, 8, 0, 0, d.ptr, 0), good)                   # NULL plane
-    refused(good, good, o=out.ptr + 4)                                 # misaligned output
-    refused(B._PolySet(16, 8, 7, d.ptr, d.ptr, 0), good)               # stride < n
-    refused(good, B._PolySet(16, 8, 7, d.ptr, d.ptr, 0))
-    for flags in (2, 4, 16, -1):
-        refused(good, good, flags=flags)
-    refused(good, good, rb=(1 << 32) - 7)                              # row_base + n_a > 2^32
-    refused(good, good, cb=(1 << 32) - 7)
+    def refused(a, b, m):
+        assert status(a, b, m=m) == -1 and b"c2d_poly_set_casts" in lib.c2d_last_error(eng.h)
+
+    best.refused_set_arguments(status, B._PolySet, d.ptr, out.ptr, "c2d_poly_set_casts", lambda: lib.c2d_last_error(eng.h), off=4)
     for half in ((d.ptr, None, None, None), (None, d.ptr, None, None), (None, None, d.ptr, None), (d.ptr, d.ptr, None, d.ptr)):
         refused(good, good, m=half)                                    # half a motion
     for k in range(4):                                                 # a misaligned motion plane
         refused(good, good, m=tuple(d.ptr + (2 if q == k else 0) for q in range(4)))
-    assert fn(eng.h, C.byref(B._PolySet(16, 0, 0, 0, 0, 0)), C.byref(good), None, None, None, None, 0, 0, 0, P(out.ptr), None) == 0      # n_a == 0: a no-op
-    assert fn(eng.h, C.byref(good), C.byref(good), P(d.ptr), P(d.ptr), None, None, (1 << 32) - 8, (1 << 32) - 8, 1, P(out.ptr + 8), None) == 0   # exactly 2^32, 8-byte aligned
+    assert status(good, good, (1 << 32) - 8, (1 << 32) - 8, 1, out.ptr + 8, (d.ptr, d.ptr, None, None)) == 0      # exactly 2^32 with a motion, 8-byte aligned
     eng.synchronize()
     eng.check_async()
     d.free()
@@ -465,16 +442,14 @@ def test_argument_errors(eng, pkg):
 
 
 def test_graph_capture_in_a_fresh_process():
-    """capture and six replays with changed buffers (tests/cast_graph_check.py: torch is loaded before the library there)"""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "cast_graph_check.py")], capture_output=True, text=True, timeout=600)
+    """capture and six replays with changed buffers (tests/best_key_graph_check.py cast: torch is loaded before the library there)"""
+    r = subprocess.run([sys.executable, os.path.join(HERE, "best_key_graph_check.py"), "cast"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "cast graph ok" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
 
 
 @pytest.mark.parametrize("idx", range(16))
 def test_fixed_seed_fuzz(eng, wl, idx):
     """sixteen fixed-seed configurations of tests/tools/cast_fuzz.py"""
-    spec = importlib.util.spec_from_file_location("cast_fuzz", os.path.join(HERE, "tools", "cast_fuzz.py"))
-    fuzz = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(fuzz)
+    fuzz = best.load_tool("cast_fuzz")
     ok, what = fuzz.one(eng, wl, np.random.default_rng([FUZZ_SEED, idx]), idx)
     assert ok, what

@@ -8,7 +8,6 @@ What a grid can get wrong and the N x M walk cannot: the ORDER in which the cand
 lost to the boxes, the switch to the list kernel at the walk's cap, and wild polygons.  test_free_order and test_path_switches are
 about the first and the third."""
 import ctypes as C
-import importlib.util
 import os
 import subprocess
 import sys
@@ -18,6 +17,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import best_key_harness as best  # noqa: E402
 import cast_cases as cases  # noqa: E402
 import cast_grid_harness as cg  # noqa: E402
 import cast_harness as ch  # noqa: E402
@@ -203,8 +203,7 @@ def test_path_switches_at_the_candidate_cap(eng, covers):
         got = cg.check(eng, sc.a.set, sc.b.set, n_a, want, f"stations, covers {covers}", nxm=False, **sc.motions())
         st = eng.poly_set_casts_grid_stats()
         print(f"covers {covers}: {st}")
-        full = cg.call(eng, sc.a.set, sc.b.set, n_a, grid=False, **sc.motions())
-        assert got.tobytes() == full.tobytes(), "the bytes differ from c2d_poly_set_casts'"
+        best.check_against_sibling(got, ch.call(eng, sc.a.set, sc.b.set, n_a, **sc.motions()), f"stations, covers {covers}", ("grid", "c2d_poly_set_casts"))
     finally:
         sc.free()
     # a probe's walk reads its own pile and nothing else (tests/test_sweep_threshold_cases_cpu.py); the covers are wild (the tail, not the walk)
@@ -368,43 +367,29 @@ def test_argument_errors(eng, pkg):
     P = C.c_void_p
     err = lambda: lib.c2d_last_error(eng.h)      # noqa: E731
 
-    def refused(a, b, m=(None, None, None, None), rb=0, cb=0, flags=0, o=None, word=b""):
-        rc = fn(eng.h, None if a is None else C.byref(a), None if b is None else C.byref(b), *[None if x is None else P(x) for x in m], rb, cb, flags,
-                P(out.ptr if o is None else o), None)
-        assert rc == -1 and b"c2d_poly_set_casts_grid" in err() and word in err(), err()
+    def status(a, b, rb=0, cb=0, flags=0, o=out.ptr, m=(None, None, None, None)):
+        return fn(eng.h, None if a is None else C.byref(a), None if b is None else C.byref(b), *[None if x is None else P(x) for x in m], rb, cb, flags, P(o), None)
+
+    def refused(a, b, word, **kw):
+        assert status(a, b, **kw) == -1 and b"c2d_poly_set_casts_grid" in err() and word in err(), err()
 
     for half in ((d.ptr, None, None, None), (None, d.ptr, None, None), (None, None, d.ptr, None), (d.ptr, d.ptr, None, d.ptr)):
-        refused(good, good, m=half, word=b"motion")                    # half a motion
-        refused(None, None, m=half, flags=7, o=4, word=b"motion")      # ... comes first
+        refused(good, good, b"motion", m=half)                         # half a motion
+        refused(None, None, b"motion", m=half, flags=7, o=4)           # ... comes first
     for k in range(4):                                                 # a misaligned motion plane
-        refused(good, good, m=tuple(d.ptr + (2 if q == k else 0) for q in range(4)), word=b"aligned")
-    refused(None, good, word=b"NULL")
-    refused(good, None, word=b"NULL")
-    refused(good, good, o=0, word=b"NULL")
-    for rows in (0, 17):
-        refused(B._PolySet(rows, 8, 0, d.ptr, d.ptr, 0), good, word=b"rows")
-        refused(good, B._PolySet(rows, 8, 0, d.ptr, d.ptr, 0), word=b"rows")
-        refused(good, B._PolySet(rows, 0, 0, 0, 0, 0), word=b"rows")   # (rows is checked even with n_b == 0)
-    refused(B._PolySet(16, 8, 0, d.ptr + 2, d.ptr, 0), good)           # misaligned planes
-    refused(good, B._PolySet(16, 8, 0, d.ptr, d.ptr + 1, 0))
-    refused(B._PolySet(16, 8, 0, 0, d.ptr, 0), good)                   # NULL plane
-    refused(good, good, o=out.ptr + 4, word=b"8-byte")                 # misaligned output
-    refused(B._PolySet(16, 8, 7, d.ptr, d.ptr, 0), good)               # stride < n
-    refused(good, B._PolySet(16, 8, 7, d.ptr, d.ptr, 0))
-    for flags in (2, 4, 16, -1):
-        refused(good, good, flags=flags, word=b"flag")
-    refused(good, good, rb=(1 << 32) - 7, word=b"2^32")                # row_base + n_a > 2^32
-    refused(good, good, cb=(1 << 32) - 7, word=b"2^32")
-    refused(good, good, rb=(1 << 32) + 1, word=b"2^32")                # a base above 2^32
-    refused(B._PolySet(16, (1 << 32) + 1, 0, d.ptr, d.ptr, 0), good, word=b"2^32")      # n above 2^32
-    refused(good, B._PolySet(16, (1 << 32) + 1, 0, d.ptr, d.ptr, 0), word=b"2^32")
+        refused(good, good, b"aligned", m=tuple(d.ptr + (2 if q == k else 0) for q in range(4)))
+    best.refused_set_arguments(status, B._PolySet, d.ptr, out.ptr, "c2d_poly_set_casts_grid", err, off=4, accepted=False)
+    refused(good, good, b"8-byte", o=out.ptr + 4)                      # misaligned output
+    refused(good, good, b"2^32", rb=(1 << 32) + 1)                     # a base above 2^32
+    refused(B._PolySet(16, (1 << 32) + 1, 0, d.ptr, d.ptr, 0), good, b"2^32")      # n above 2^32
+    refused(good, B._PolySet(16, (1 << 32) + 1, 0, d.ptr, d.ptr, 0), b"2^32")
     eng.synchronize()
     assert out.get().tobytes() == b"\xa5" * out.nbytes, "a refused call wrote something"
-    assert fn(eng.h, C.byref(B._PolySet(16, 0, 0, 0, 0, 0)), C.byref(good), None, None, None, None, 0, 0, 0, P(out.ptr), None) == 0      # n_a == 0: a no-op
+    assert status(B._PolySet(16, 0, 0, 0, 0, 0), good) == 0          # n_a == 0: a no-op
     eng.synchronize()
     assert out.get().tobytes() == b"\xa5" * out.nbytes, "n_a == 0 wrote something"
     # exactly 2^32, an output that is 8- but not 16-byte aligned: eight all-zero octagons, each overlapping the ones before it
-    assert fn(eng.h, C.byref(good), C.byref(good), P(d.ptr), P(d.ptr), None, None, (1 << 32) - 8, (1 << 32) - 8, 1, P(out.ptr + 8), None) == 0
+    assert status(good, good, (1 << 32) - 8, (1 << 32) - 8, 1, out.ptr + 8, (d.ptr, d.ptr, None, None)) == 0
     eng.synchronize()
     eng.check_async()
     d.free()
@@ -480,17 +465,15 @@ def test_fused_validation_builds_match_their_own_casts(pkg, wl, k):
 # ---- graph capture and fuzzing ------------------------------------------------------------------------------------------------------
 def test_graph_capture_in_a_fresh_process():
     """a capture on a fresh ctx is refused before anything is enqueued; after a warm-up one capture and six replays with changed buffers
-    (tests/cast_grid_graph_check.py, its own process: torch has to be imported before libc2d.so)"""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "cast_grid_graph_check.py")], capture_output=True, text=True, timeout=600)
+    (tests/best_key_graph_check.py cast_grid, its own process: torch has to be imported before libc2d.so)"""
+    r = subprocess.run([sys.executable, os.path.join(HERE, "best_key_graph_check.py"), "cast_grid"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "cast grid graph ok" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
 
 
 @pytest.mark.parametrize("idx", range(12))
 def test_fixed_seed_fuzz(eng, wl, idx):
     """twelve fixed-seed configurations of tests/tools/cast_grid_fuzz.py"""
-    spec = importlib.util.spec_from_file_location("cast_grid_fuzz", os.path.join(HERE, "tools", "cast_grid_fuzz.py"))
-    fuzz = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(fuzz)
+    fuzz = best.load_tool("cast_grid_fuzz")
     ok, what = fuzz.one(eng, wl, np.random.default_rng([FUZZ_SEED, idx]), idx)
     assert ok, what
     eng.check_async()

@@ -14,7 +14,6 @@ test_near_ties_between_obstacles              130 different obstacles within a f
                                               built, reversed and spread over 17 strips
 test_between_one_strip_and_one_per_tile       1 < strips < column tiles, an uneven split, many row tiles"""
 import ctypes as C
-import importlib.util
 import os
 import subprocess
 import sys
@@ -24,6 +23,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import best_key_harness as best  # noqa: E402
 import clearance_cases as cases  # noqa: E402
 import clearance_harness as ch  # noqa: E402
 import clearance_ref as ref  # noqa: E402
@@ -36,14 +36,7 @@ pytestmark = pytest.mark.gpu
 F = np.float32
 FUZZ_SEED = 20318
 FUZZ_UNDERFLOW_CONFIGS = (0, 9)      # the configurations of FUZZ_SEED drawn in the band where d2 underflows to 0 (17 and 76 such winners)
-TILE_ROWS, TILE_COLS = 256, 64          # queries per block and polygons per staged tile of the kernel (csrc/c2d_clearance.hip)
 N_B_SIZES = [1, 2, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513]
-
-
-def strips_of(eng, n_a, n_b):
-    """the strip rule of csrc/c2d_ray_strips.hpp with the library's target of eight blocks per CU"""
-    row_tiles, col_tiles = -(-n_a // TILE_ROWS), -(-n_b // TILE_COLS)
-    return min(col_tiles, max(1, 8 * eng.info()["compute_units"] // row_tiles))
 
 
 @pytest.fixture(scope="module")
@@ -102,7 +95,7 @@ def test_every_pairs_boolean_through_a_witness(eng, wl, name):
     band = h.banded(eng, n_a, ch.DT)
     for layout, (s, width) in layouts.items():
         ub = Uploaded(eng, s)
-        assert strips_of(eng, n_a, width) == -(-width // TILE_COLS)
+        assert best.strips_of(eng.info()["compute_units"], n_a, width) == -(-width // best.TILE_COLS)
         for j in range(n_b):
             what = f"{name}, {layout}, obstacle {j}"
             got = ch.call(eng, ua.set, ub.sub(width * j, width * (j + 1)), n_a, band=band, col_base=width * j)
@@ -135,7 +128,7 @@ def test_near_ties_between_obstacles(eng):
                 ub = Uploaded(eng, ch.take(b, ib))
                 got = ch.twice(eng, ua.set, ub.set, 64, what)
                 ch.assert_same(got, ch.indexed_reference(a, ia, b, ib, D=D), what)
-                assert strips_of(eng, 64, len(ib)) == -(-len(ib) // TILE_COLS)
+                assert best.strips_of(eng.info()["compute_units"], 64, len(ib)) == -(-len(ib) // best.TILE_COLS)
                 ub.free()
             ua.free()
     eng.check_async()
@@ -150,8 +143,8 @@ def test_between_one_strip_and_one_per_tile(eng, sparse, s):
     a, b, D = sparse
     cus = eng.info()["compute_units"]
     row_tiles = 8 * cus // s
-    n = TILE_ROWS * row_tiles - 251
-    strips = strips_of(eng, n, 513) if n > 0 else 0
+    n = best.TILE_ROWS * row_tiles - 251
+    strips = best.strips_of(eng.info()["compute_units"], n, 513) if n > 0 else 0
     if not (1 < strips < 9 and 9 % strips != 0):
         pytest.skip(f"{cus} compute units give {strips} strips for 8 * cus / {s} row tiles against 9 column tiles: not strictly between, unevenly split")
     print(f"{cus} compute units, {row_tiles} row tiles, {n} queries: {strips} strips over 9 column tiles")
@@ -171,7 +164,7 @@ def test_every_number_of_queries(eng, many_queries):
     for n in contact_cases.LIST_LENGTHS:
         got = ch.call(eng, ua.sub(0, n), ub.set, n)
         ch.assert_same(got, want[:n], f"{n} queries")
-        assert strips_of(eng, max(n, 1), 24) == 1
+        assert best.strips_of(eng.info()["compute_units"], max(n, 1), 24) == 1
     eng.check_async()
     ua.free()
     ub.free()
@@ -187,7 +180,7 @@ def test_every_number_of_polygons(eng, sparse):
         want = ref.reduce(D[:, :n_b], bad_a, bad_b[:n_b])
         got = ch.twice(eng, ua.set, ub.sub(0, n_b), 64, f"{n_b} polygons")
         ch.assert_same(got, want, f"{n_b} polygons")
-        assert strips_of(eng, 64, n_b) == -(-n_b // TILE_COLS)
+        assert best.strips_of(eng.info()["compute_units"], 64, n_b) == -(-n_b // best.TILE_COLS)
     full = ref.reduce(D, bad_a, bad_b)
     assert (full["hit"] == 0).mean() > 0.3 and (full["hit"] == 1).mean() > 0.05 and len(np.unique(full["poly"])) > 20
     eng.check_async()
@@ -206,7 +199,7 @@ def test_one_strip_walks_every_tile(eng, sparse):
     ub = Uploaded(eng, b)
     bad_a, bad_b = ref.bad_counts(a), ref.bad_counts(b)
     for n_b in (2, 130):
-        assert strips_of(eng, n, n_b) == 1
+        assert best.strips_of(eng.info()["compute_units"], n, n_b) == 1
         want = ref.reduce(D[:, :n_b], bad_a, bad_b[:n_b])[ia]
         got = ch.call(eng, ua.set, ub.sub(0, n_b), n)
         ch.assert_same(got, want, f"2^19 + 5 queries against {n_b}")
@@ -276,7 +269,7 @@ def test_order_independence_by_construction(eng, sparse):
         want = ref.reduce(D[:, ib], bad_a, bad_b[ib])
         got = ch.twice(eng, ua.set, ub.set, 64, name)
         ch.assert_same(got, want, name)
-        assert strips_of(eng, 64, len(ib)) == 17
+        assert best.strips_of(eng.info()["compute_units"], 64, len(ib)) == 17
         ub.free()
     eng.check_async()
     ua.free()
@@ -409,32 +402,12 @@ def test_argument_errors(eng, pkg):
     lib, B = eng.lib, pkg.binding
     d = eng.zeros(1024, np.float32)
     out = eng.empty(8, ref.CLEARANCE_DT)
-    good = B._PolySet(16, 8, 0, d.ptr, d.ptr, 0)
     fn = lib.c2d_poly_set_clearances
 
-    def refused(a, b, rb=0, cb=0, flags=0, o=None):
-        rc = fn(eng.h, None if a is None else C.byref(a), None if b is None else C.byref(b), rb, cb, flags, C.c_void_p(out.ptr if o is None else o), None)
-        assert rc == -1 and b"c2d_poly_set_clearances" in lib.c2d_last_error(eng.h)
+    def status(a, b, rb, cb, flags, o):
+        return fn(eng.h, None if a is None else C.byref(a), None if b is None else C.byref(b), rb, cb, flags, C.c_void_p(o), None)
 
-    refused(None, good)
-    refused(good, None)
-    refused(good, good, o=0)
-    for rows in (0, 17):
-        refused(B._PolySet(rows, 8, 0, d.ptr, d.ptr, 0), good)
-        refused(good, B._PolySet(rows, 8, 0, d.ptr, d.ptr, 0))
-        refused(good, B._PolySet(rows, 0, 0, 0, 0, 0))                 # (rows is checked even with n_b == 0)
-    refused(B._PolySet(16, 8, 0, d.ptr + 2, d.ptr, 0), good)           # misaligned planes
-    refused(good, B._PolySet(16, 8, 0, d.ptr, d.ptr + 1, 0))
-    refused(B._PolySet(16, 8, 0, 0, d.ptr, 0), good)                   # NULL plane
-    refused(good, good, o=out.ptr + 8)                                 # misaligned output
-    refused(B._PolySet(16, 8, 7, d.ptr, d.ptr, 0), good)               # stride < n
-    refused(good, B._PolySet(16, 8, 7, d.ptr, d.ptr, 0))
-    for flags in (2, 4, 16, -1):
-        refused(good, good, flags=flags)
-    refused(good, good, rb=(1 << 32) - 7)                              # row_base + n_a > 2^32
-    refused(good, good, cb=(1 << 32) - 7)
-    assert fn(eng.h, C.byref(B._PolySet(16, 0, 0, 0, 0, 0)), C.byref(good), 0, 0, 0, C.c_void_p(out.ptr), None) == 0      # n_a == 0: a no-op
-    assert fn(eng.h, C.byref(good), C.byref(good), (1 << 32) - 8, (1 << 32) - 8, 1, C.c_void_p(out.ptr), None) == 0       # exactly 2^32
+    best.refused_set_arguments(status, B._PolySet, d.ptr, out.ptr, "c2d_poly_set_clearances", lambda: lib.c2d_last_error(eng.h))
     eng.synchronize()
     eng.check_async()
     d.free()
@@ -442,17 +415,15 @@ def test_argument_errors(eng, pkg):
 
 
 def test_graph_capture_in_a_fresh_process():
-    """capture and six replays with changed buffers (tests/clearance_graph_check.py: torch is loaded before the library there)"""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "clearance_graph_check.py")], capture_output=True, text=True, timeout=600)
+    """capture and six replays with changed buffers (tests/best_key_graph_check.py clearance: torch is loaded before the library there)"""
+    r = subprocess.run([sys.executable, os.path.join(HERE, "best_key_graph_check.py"), "clearance"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "clearance graph ok" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
 
 
 @pytest.mark.parametrize("idx", range(16))
 def test_fixed_seed_fuzz(eng, wl, idx):
     """sixteen fixed-seed configurations of tests/tools/clearance_fuzz.py"""
-    spec = importlib.util.spec_from_file_location("clearance_fuzz", os.path.join(HERE, "tools", "clearance_fuzz.py"))
-    fuzz = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(fuzz)
+    fuzz = best.load_tool("clearance_fuzz")
     ok, what = fuzz.one(eng, wl, np.random.default_rng([FUZZ_SEED, idx]), idx)
     assert ok, what
     if idx in FUZZ_UNDERFLOW_CONFIGS:      # scales 2^-73 .. 2^-75: winners that are separated at dist = +0 are really there

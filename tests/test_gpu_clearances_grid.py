@@ -4,7 +4,6 @@ tests/clearance_grid_ref.py — near_broad_ref's considered pairs, distance_ref'
 c2d_poly_set_clearances on the same GPU.  Every call writes between guard bands that are checked afterwards
 (tests/clearance_grid_harness.py), the vertex planes lie between gaps of NaN, padded vertex slots hold NaN."""
 import ctypes as C
-import importlib.util
 import os
 import subprocess
 import sys
@@ -12,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import best_key_harness as best
 import clearance_cases as cases
 import clearance_grid_harness as gh
 import clearance_grid_ref as ref
@@ -352,6 +352,11 @@ def test_argument_errors(eng, pkg, wl):
         with pytest.raises(pkg.C2DError) as e:
             f()
         assert e.value.status == -1, q
+
+    def status(x, y, rb, cb, flags, o):      # the refusals every two-set query shares, at a good max_dist
+        return raw(eng.h, None if x is None else C.byref(x), None if y is None else C.byref(y), 1.0, rb, cb, flags, o, None)
+
+    best.refused_set_arguments(status, pkg.binding._PolySet, A.px, d.ptr, "c2d_poly_set_clearances_grid", lambda: err().encode(), accepted=False)
     eng.synchronize()
     assert d.get().tobytes() == b"\xa5" * d.nbytes, "a refused call wrote something"
     assert raw(*ok, below(2.0 ** 60), 0, 0, 0, d.ptr, None) == 0     # the largest margin: everything finite is considered
@@ -359,6 +364,8 @@ def test_argument_errors(eng, pkg, wl):
     got = d.get()[:100]
     gh.assert_same(got, ref.cref.clearances(a, a), "the largest margin")
     assert (got["hit"] == 1).all()
+    assert raw(*ok, 1.0, (1 << 32) - 100, (1 << 32) - 100, 1, d.ptr, None) == 0      # both bases at exactly 2^32 - n
+    eng.synchronize()
     d.free()
     A.free()
     eng.check_async()
@@ -402,9 +409,7 @@ def test_fused_validation_builds_match_their_own_distances(pkg, wl, k):
 # ---- fuzzing and graph capture ------------------------------------------------------------------------------------------------------
 def test_fuzz_at_a_fixed_seed(eng):
     """tests/tools/clearance_grid_fuzz.py for a dozen configurations at a fixed seed: every record equals the reference's"""
-    spec = importlib.util.spec_from_file_location("clearance_grid_fuzz", os.path.join(HERE, "tools", "clearance_grid_fuzz.py"))
-    fz = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(fz)
+    fz = best.load_tool("clearance_grid_fuzz")
     tot = dict(winners=0, apart=0, none=0, bad=0)
     for i in range(12):
         ok, what = fz.one(eng, np.random.default_rng([20263, i]), i)

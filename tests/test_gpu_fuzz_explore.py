@@ -20,12 +20,13 @@ np.random.default_rng([leg seed, i]): there a configuration IS a function of (se
     C2D_FUZZ_SEED=<base seed> C2D_FUZZ_INDEX=<i> python -m pytest tests/test_gpu_fuzz_explore.py -m gpu -k <leg>
 runs exactly that one.  Over its run each of the twelve must have compared a colliding and a non-colliding result (rays and grid rays: a
 hit and a miss; clearances: a winner that is hit and one that is not; mc_poly: a scene with 0 < hits < samples)."""
-import importlib.util
 import os
 import time
 
 import numpy as np
 import pytest
+
+from best_key_harness import load_tool as _tool
 
 pytestmark = pytest.mark.gpu
 
@@ -41,13 +42,6 @@ TOOL = {"sat_rect_verts": "verts_fuzz", "sat_rect_pose": "pose_fuzz", "sat_poly_
         "ray_grid": "ray_grid_fuzz", "clearances": "clearance_fuzz"}
 TAKES_ORACLE = ("rect_cross", "poly_cross", "rect_broad", "manifolds")   # one(eng, rng, idx, announce, oracle)
 TAKES_WL = ("clearances",)   # one(eng, wl, rng, idx, announce)
-
-
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 @pytest.mark.parametrize("leg", LEGS)

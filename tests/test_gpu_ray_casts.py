@@ -3,8 +3,6 @@ the contract of include/c2d.h, pinned by tests/test_ray_ref_cpu.py — t and u b
 the engine's own N x M polygon test on the segments as 2-gons.  Every output buffer handed to the library sits between guard bands
 that are checked afterwards."""
 import ctypes as C
-import functools
-import importlib.util
 import os
 import subprocess
 import sys
@@ -14,25 +12,16 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-import best_key_harness  # noqa: E402
+import best_key_harness as best  # noqa: E402
 import contact_cases  # noqa: E402
 import ray_cases as cases  # noqa: E402
 import ray_ref as ref  # noqa: E402
 from pair_list_harness import Uploaded  # noqa: E402
-from ray_harness import RaysOnDevice, assert_same, cast  # noqa: E402
+from ray_harness import RaysOnDevice, assert_same, cast, twice  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 FUZZ_SEED = 20264
 F = np.float32
-TILE_ROWS, TILE_COLS = 256, 64          # rays per block and polygons per staged tile of the kernel (csrc/c2d_ray.hip)
-
-
-def strips_of(eng, n_rays, n_b):
-    """the strip rule of csrc/c2d_ray_strips.hpp with the library's target of eight blocks per CU"""
-    row_tiles, col_tiles = -(-n_rays // TILE_ROWS), -(-n_b // TILE_COLS)
-    return min(col_tiles, max(1, 8 * eng.info()["compute_units"] // row_tiles))
-
-
 @pytest.fixture(scope="module")
 def long_scene(wl):
     """the ray scene's polygons with 4099 rays of the same generator, and their reference records, computed once"""
@@ -43,9 +32,6 @@ def long_scene(wl):
     return rays, b, want
 
 
-twice = functools.partial(best_key_harness.twice, cast)  # twice(eng, rays, n_rays, b_set, what, **kw): the call, run twice: the same bytes
-
-
 def test_every_number_of_rays(eng, long_scene):
     """0, 1, 63, 64, 65, 255, 256, 257, 1000 and 4099 rays against the scene's 311 polygons (five column tiles, one strip each)."""
     rays, b, want = long_scene
@@ -53,7 +39,7 @@ def test_every_number_of_rays(eng, long_scene):
     for n in contact_cases.LIST_LENGTHS:
         got = cast(eng, dr, n, ub.set, capacity=max(n, 4))
         assert_same(got[:n], want[:n], f"{n} rays")
-        assert strips_of(eng, max(n, 1), 311) == 5
+        assert best.strips_of(eng.info()["compute_units"], max(n, 1), 311) == 5
     eng.check_async()
     ub.free()
     dr.free()
@@ -72,7 +58,7 @@ def test_every_number_of_polygons(eng, wl, long_scene):
         ub = Uploaded(eng, sub)
         want = ref.ray_casts(rays, sub)
         assert_same(twice(eng, dr, 257, ub.set, f"{n_b} polygons"), want, f"{n_b} polygons")
-        seen.add(strips_of(eng, 257, n_b))
+        seen.add(best.strips_of(eng.info()["compute_units"], 257, n_b))
         ub.free()
     assert {1, 2, 3, 4, 5, 9} <= seen
     eng.check_async()
@@ -88,9 +74,9 @@ def test_both_sides_of_the_strip_rule(eng, long_scene):
     ub = Uploaded(eng, b)
     wanted = set()
     for row_tiles in (8 * cus + 3, 8 * cus // 3):
-        reps = -(-row_tiles * TILE_ROWS // 2000)
+        reps = -(-row_tiles * best.TILE_ROWS // 2000)
         n = reps * 2000
-        wanted.add(strips_of(eng, n, 311))
+        wanted.add(best.strips_of(eng.info()["compute_units"], n, 311))
         dr = RaysOnDevice(eng, tuple(np.tile(r[:2000], reps) for r in rays))
         got = cast(eng, dr, n, ub.set)
         dr.free()
@@ -295,17 +281,15 @@ def test_argument_errors(eng, pkg, long_scene):
 
 
 def test_graph_capture_in_a_child_process():
-    """tests/ray_graph_check.py: capture the call, replay with changed rays and polygons"""
-    out = subprocess.run([sys.executable, os.path.join(HERE, "ray_graph_check.py")], capture_output=True, text=True, timeout=600)
+    """tests/best_key_graph_check.py ray: capture the call, replay with changed rays and polygons"""
+    out = subprocess.run([sys.executable, os.path.join(HERE, "best_key_graph_check.py"), "ray"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     assert "ray graph ok" in out.stdout
 
 
 def test_fuzzer_configurations_at_a_fixed_seed(eng):
     """tests/tools/ray_fuzz.py at a fixed seed, each configuration from its own stream (seed, index): sixteen configurations"""
-    spec = importlib.util.spec_from_file_location("ray_fuzz", os.path.join(HERE, "tools", "ray_fuzz.py"))
-    fz = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(fz)
+    fz = best.load_tool("ray_fuzz")
     compared = 0
     for i in range(16):
         ok, (desc, n) = fz.one(eng, np.random.default_rng([FUZZ_SEED, i]), i)

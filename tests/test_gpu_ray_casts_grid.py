@@ -3,8 +3,6 @@ numpy restatement of the contract of include/c2d.h, pinned by tests/test_ray_gri
 on the project's scenes the records also equal c2d_poly_ray_casts' byte for byte, in the same run.  Every output buffer handed to the
 library sits between guard bands that are checked afterwards (tests/ray_harness.py, tests/pair_list_harness.py)."""
 import ctypes as C
-import functools
-import importlib.util
 import os
 import subprocess
 import sys
@@ -14,45 +12,20 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-import best_key_harness  # noqa: E402
-import pair_list_harness as h  # noqa: E402
+import best_key_harness as best  # noqa: E402
 import ray_cases as cases  # noqa: E402
 import ray_grid_cases as gcases  # noqa: E402
 import ray_grid_ref as gref  # noqa: E402
 import ray_ref as ref  # noqa: E402
 from pair_list_harness import Uploaded  # noqa: E402
-from ray_harness import RaysOnDevice, assert_same, cast  # noqa: E402
+from ray_harness import RaysOnDevice, assert_same, cast, cast_grid  # noqa: E402
+from ray_harness import check_grid as check, twice_grid as twice  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 FUZZ_SEED = 20417
 F = np.float32
 DT = ref.RAY_HIT_DT
 CAP = gcases.WALK_CAP
-
-
-def cast_grid(eng, rays, n_rays, b_set, col_base=0, capacity=None, expect_error=False):
-    """ray_harness.cast for c2d_poly_ray_casts_grid: a banded output; the bands and every record at or beyond n_rays must be untouched;
-    under expect_error the synchronise reports status -1, once"""
-    return h.banded_call(eng, DT, n_rays, lambda ptr: eng.poly_ray_casts_grid(rays.ptrs, n_rays, b_set, ptr, col_base=col_base), capacity, expect_error)
-
-
-twice = functools.partial(best_key_harness.twice, cast_grid)  # twice(eng, rays, n_rays, b_set, what, **kw): the call, run twice: the same bytes
-
-
-def check(eng, rays, b, what, n_rays=None, uploaded=None, on_device=None, **kw):
-    """upload, run twice, compare with the grid reference -> (records, the call's counters)"""
-    n = len(rays[0]) if n_rays is None else n_rays
-    dr = RaysOnDevice(eng, rays) if on_device is None else on_device
-    ub = Uploaded(eng, b) if uploaded is None else uploaded
-    got = twice(eng, dr, n, ub.set, what, **kw)
-    stats = eng.poly_ray_casts_grid_stats()
-    want = gref.ray_casts(tuple(r[:n] for r in rays), b, col_base=kw.get("col_base", 0))
-    assert_same(got, want, what)
-    if on_device is None:
-        dr.free()
-    if uploaded is None:
-        ub.free()
-    return got, stats
 
 
 @pytest.fixture(scope="module")
@@ -276,17 +249,15 @@ def test_argument_errors(eng, pkg, scene):
 
 
 def test_graph_capture_in_a_child_process():
-    """tests/ray_grid_graph_check.py: a growing capture is refused; capture after an eager call, replay with changed rays and polygons"""
-    out = subprocess.run([sys.executable, os.path.join(HERE, "ray_grid_graph_check.py")], capture_output=True, text=True, timeout=600)
+    """tests/best_key_graph_check.py ray_grid: a growing capture is refused; capture after an eager call, replay with changed rays and polygons"""
+    out = subprocess.run([sys.executable, os.path.join(HERE, "best_key_graph_check.py"), "ray_grid"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     assert "ray grid graph ok" in out.stdout
 
 
 def test_fuzzer_configurations_at_a_fixed_seed(eng):
     """tests/tools/ray_grid_fuzz.py at a fixed seed, each configuration from its own stream (seed, index): sixteen configurations"""
-    spec = importlib.util.spec_from_file_location("ray_grid_fuzz", os.path.join(HERE, "tools", "ray_grid_fuzz.py"))
-    fz = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(fz)
+    fz = best.load_tool("ray_grid_fuzz")
     compared = listed = 0
     for i in range(16):
         ok, (desc, n) = fz.one(eng, np.random.default_rng([FUZZ_SEED, i]), i)

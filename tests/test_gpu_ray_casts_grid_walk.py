@@ -18,8 +18,7 @@ import ray_grid_ref as gref  # noqa: E402
 import ray_grid_walk_cases as wc  # noqa: E402
 import ray_ref as ref  # noqa: E402
 from pair_list_harness import Uploaded  # noqa: E402
-from ray_harness import RaysOnDevice, assert_same, cast  # noqa: E402
-from test_gpu_ray_casts_grid import twice  # noqa: E402
+from ray_harness import RaysOnDevice, assert_same, cast, twice_grid as twice  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

@@ -7,7 +7,6 @@ motions of sweep_fuzz.py per set (standing still, all zero, the scale of the sce
 exact zeros and non-finite components).  A motion belongs to a distinct polygon, so the reference is computed for the distinct
 polygons and indexed.  Prints its seed; a mismatch names its configuration.
 usage: cast_fuzz.py [configs] [seed]"""
-import importlib.util
 import os
 import sys
 
@@ -18,19 +17,13 @@ TESTS = os.path.dirname(HERE)
 for p in (TESTS, os.path.dirname(TESTS)):
     if p not in sys.path:
         sys.path.insert(0, p)
+import best_key_harness as best  # noqa: E402
 import cast_harness as ch  # noqa: E402
 import cast_ref as ref  # noqa: E402
 
 
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-clearance_fuzz = _tool("clearance_fuzz")      # its geometry
-sweep_fuzz = _tool("sweep_fuzz")              # its motions
+clearance_fuzz = best.load_tool("clearance_fuzz")      # its geometry
+sweep_fuzz = best.load_tool("sweep_fuzz")              # its motions
 
 LAST = {}   # of the last configuration: "hits" / "misses" = queries with / without a winner, "moving_hits" = winners with toi > 0
 
@@ -66,31 +59,11 @@ def one(eng, wl, rng, idx, announce=None):
         got = ch.twice(eng, sc.a.set, sc.b_set, len(ia), what, row_base=c["rb"], col_base=c["cb"], flags=c["flags"], expect_error=bad, **sc.motions())
     finally:
         sc.free()
-    ok = ref.same(got, want)
-    if not ok.all():
-        q = int(np.flatnonzero(~ok)[0])
-        return False, what + f": {int((~ok).sum())} records differ; first at {q}: got {got[q]}, want {want[q]}"
+    why = best.mismatch(got, want, ref.same, what)
+    if why is not None:
+        return False, why
     return True, what + f" [{LAST['hits']} hits, {LAST['moving_hits']} of them later than t = 0, {LAST['misses']} misses]"
 
 
-def main():
-    from __graft_entry__ import load_package
-    import importlib
-
-    pkg = load_package()
-    wl = importlib.import_module("c2d_amd.workloads")
-    configs = int(sys.argv[1]) if len(sys.argv) > 1 else 16
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else int.from_bytes(os.urandom(4), "little")
-    print(f"cast_fuzz: seed {seed}, {configs} configurations", flush=True)
-    eng = pkg.Engine(0)
-    bad = 0
-    for idx in range(configs):
-        ok, what = one(eng, wl, np.random.default_rng([seed, idx]), idx)
-        print(("ok   " if ok else "FAIL ") + what, flush=True)
-        bad += not ok
-    eng.close()
-    sys.exit(1 if bad else 0)
-
-
 if __name__ == "__main__":
-    main()
+    best.fuzz_main("cast_fuzz", one, needs_wl=True)

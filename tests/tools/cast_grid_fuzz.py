@@ -8,7 +8,6 @@ and a few movers that are fast (their swept boxes span many cells: wild in the p
 2^60 and more).  draw() makes a configuration and the reference's records without a GPU; one() runs it; judge() compares.  Prints its
 seed; a mismatch names its configuration.
 usage: cast_grid_fuzz.py [configs] [seed]"""
-import importlib.util
 import os
 import sys
 
@@ -19,19 +18,13 @@ TESTS = os.path.dirname(HERE)
 for p in (TESTS, os.path.dirname(TESTS)):
     if p not in sys.path:
         sys.path.insert(0, p)
+import best_key_harness as best  # noqa: E402
 import cast_grid_harness as cg  # noqa: E402
 import cast_harness as ch  # noqa: E402
 import cast_ref as ref  # noqa: E402
 
 
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-cast_fuzz = _tool("cast_fuzz")      # its generators: clearance_fuzz's geometry with sweep_fuzz's motions
+cast_fuzz = best.load_tool("cast_fuzz")      # its generators: clearance_fuzz's geometry with sweep_fuzz's motions
 
 LAST = {}   # of the last configuration: "hits" / "misses" = queries with / without a winner, "moving_hits" = winners with toi > 0
 ODD = np.array([np.nan, np.inf, -np.inf, 3e38, 2.0 ** 60, -2.0 ** 61], np.float32)
@@ -122,24 +115,5 @@ def one(eng, wl, rng, idx, announce=None):
     return True, what + f" [{LAST['hits']} hits, {LAST['moving_hits']} of them later than t = 0, {LAST['misses']} misses]"
 
 
-def main():
-    from __graft_entry__ import load_package
-    import importlib
-
-    pkg = load_package()
-    wl = importlib.import_module("c2d_amd.workloads")
-    configs = int(sys.argv[1]) if len(sys.argv) > 1 else 16
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else int.from_bytes(os.urandom(4), "little")
-    print(f"cast_grid_fuzz: seed {seed}, {configs} configurations", flush=True)
-    eng = pkg.Engine(0)
-    bad = 0
-    for idx in range(configs):
-        ok, what = one(eng, wl, np.random.default_rng([seed, idx]), idx)
-        print(("ok   " if ok else "FAIL ") + what, flush=True)
-        bad += not ok
-    eng.close()
-    sys.exit(1 if bad else 0)
-
-
 if __name__ == "__main__":
-    main()
+    best.fuzz_main("cast_grid_fuzz", one, needs_wl=True)

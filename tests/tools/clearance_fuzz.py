@@ -18,6 +18,7 @@ TESTS = os.path.dirname(HERE)
 for p in (TESTS, os.path.dirname(TESTS)):
     if p not in sys.path:
         sys.path.insert(0, p)
+import best_key_harness as best  # noqa: E402
 import clearance_harness as ch  # noqa: E402
 import clearance_ref as ref  # noqa: E402
 from pair_list_harness import Uploaded  # noqa: E402
@@ -27,12 +28,7 @@ F = np.float32
 
 LAST = {}   # of the last configuration: "zero_separated" = winners with hit = 0 and dist = +0 (a separated pair whose d2 underflowed),
             # "hits" / "misses" = winners with hit = 1 / hit = 0
-TILE_ROWS, TILE_COLS, BLOCKS_PER_CU = 256, 64, 8      # csrc/c2d_clearance.hip and the strip rule's target (csrc/c2d_ray_strips.hpp)
-
-
-def strips_of(cus, n_a, n_b):
-    row_tiles, col_tiles = -(-n_a // TILE_ROWS), -(-n_b // TILE_COLS)
-    return min(col_tiles, max(1, BLOCKS_PER_CU * cus // row_tiles))
+TILE_ROWS, TILE_COLS, BLOCKS_PER_CU, strips_of = best.TILE_ROWS, best.TILE_COLS, best.BLOCKS_PER_CU, best.strips_of
 
 
 def draw(wl, rng, idx, cus=None):
@@ -115,31 +111,11 @@ def one(eng, wl, rng, idx, announce=None):
         ua.free()
         if ub is not ua:
             ub.free()
-    ok = ref.same(got, want)
-    if not ok.all():
-        q = int(np.flatnonzero(~ok)[0])
-        return False, what + f": {int((~ok).sum())} records differ; first at {q}: got {got[q]}, want {want[q]}"
+    why = best.mismatch(got, want, ref.same, what)
+    if why is not None:
+        return False, why
     return True, what + f" [{LAST['zero_separated']} winners separated at dist 0]"
 
 
-def main():
-    from __graft_entry__ import load_package
-    import importlib
-
-    pkg = load_package()
-    wl = importlib.import_module("c2d_amd.workloads")
-    configs = int(sys.argv[1]) if len(sys.argv) > 1 else 16
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else int.from_bytes(os.urandom(4), "little")
-    print(f"clearance_fuzz: seed {seed}, {configs} configurations", flush=True)
-    eng = pkg.Engine(0)
-    bad = 0
-    for idx in range(configs):
-        ok, what = one(eng, wl, np.random.default_rng([seed, idx]), idx)
-        print(("ok   " if ok else "FAIL ") + what, flush=True)
-        bad += not ok
-    eng.close()
-    sys.exit(1 if bad else 0)
-
-
 if __name__ == "__main__":
-    main()
+    best.fuzz_main("clearance_fuzz", one, needs_wl=True)

@@ -8,7 +8,6 @@ itself (the same memory), row and column bases, C2D_CLEARANCE_SKIP_SELF, and a m
 extents.  draw() makes a configuration and the reference's records without a GPU; one() runs it; judge() compares.  Prints its seed; a
 mismatch names its configuration.
 usage: clearance_grid_fuzz.py [configs] [seed]"""
-import importlib.util
 import os
 import sys
 
@@ -19,20 +18,14 @@ TESTS = os.path.dirname(HERE)
 for p in (TESTS, os.path.dirname(TESTS)):
     if p not in sys.path:
         sys.path.insert(0, p)
+import best_key_harness as best  # noqa: E402
 import clearance_grid_harness as gh  # noqa: E402
 import clearance_grid_ref as ref  # noqa: E402
 import near_broad_ref as nref  # noqa: E402
 import pair_search_harness as psh  # noqa: E402
 
 
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-near_broad_fuzz = _tool("near_broad_fuzz")    # its sizes, its measure of a polygon's size and, through it, poly_broad_fuzz's random sets
+near_broad_fuzz = best.load_tool("near_broad_fuzz")    # its sizes, its measure of a polygon's size and, through it, poly_broad_fuzz's random sets
 poly_broad_fuzz = near_broad_fuzz.poly_broad_fuzz
 
 LAST = {}   # of the last configuration: "winners", "apart" = winners that are not hit, "none" = NONE records, "bad" = BAD_PAIR records
@@ -150,22 +143,5 @@ def one(eng, rng, idx, announce=None):
     return True, what + f" [{LAST['winners']} winners, {LAST['apart']} of them apart, {LAST['none']} none, {LAST['bad']} bad queries]"
 
 
-def main():
-    from __graft_entry__ import load_package
-
-    pkg = load_package()
-    configs = int(sys.argv[1]) if len(sys.argv) > 1 else 16
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else int.from_bytes(os.urandom(4), "little")
-    print(f"clearance_grid_fuzz: seed {seed}, {configs} configurations", flush=True)
-    eng = pkg.Engine(0)
-    bad = 0
-    for idx in range(configs):
-        ok, what = one(eng, np.random.default_rng([seed, idx]), idx)
-        print(("ok   " if ok else "FAIL ") + what, flush=True)
-        bad += not ok
-    eng.close()
-    sys.exit(1 if bad else 0)
-
-
 if __name__ == "__main__":
-    main()
+    best.fuzz_main("clearance_grid_fuzz", one, needs_wl=False)

@@ -7,7 +7,6 @@ now and then a vertex count out of range; rays that start on a vertex or on an e
 non-finite rays.  Prints its seed; a mismatch names its configuration.
 usage: ray_fuzz.py [configs] [seed]     (no seed: the commit's, tests/tools/fuzz_seed.py)"""
 import importlib
-import importlib.util
 import os
 import sys
 
@@ -18,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 from __graft_entry__ import load_package  # noqa: E402
+import best_key_harness as best  # noqa: E402
 import ray_ref as ref  # noqa: E402
 
 pkg = load_package()
@@ -25,15 +25,8 @@ wl = importlib.import_module("c2d_amd.workloads")
 F = np.float32
 
 
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-pbf = _tool("poly_broad_fuzz")      # its random sets and its upload
-fuzz_seed = _tool("fuzz_seed")
+pbf = best.load_tool("poly_broad_fuzz")      # its random sets and its upload
+fuzz_seed = best.load_tool("fuzz_seed")
 
 
 LAST = {}   # hits / misses of the last configuration, for the exploring leg's "not vacuous" check

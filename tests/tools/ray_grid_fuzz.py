@@ -7,7 +7,6 @@ walks, listed rays), polygons duplicated many times, and outsized polygons that 
 bounds.  Every configuration runs twice (the same bytes) and is compared with the reference.  Prints its seed; a mismatch names its
 configuration.
 usage: ray_grid_fuzz.py [configs] [seed]     (no seed: the commit's, tests/tools/fuzz_seed.py)"""
-import importlib.util
 import os
 import sys
 
@@ -15,17 +14,11 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+import best_key_harness as best  # noqa: E402
 import ray_grid_ref as gref  # noqa: E402
 
 
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-rf = _tool("ray_fuzz")              # its rays, its random sets (poly_broad_fuzz.py's) and its package
+rf = best.load_tool("ray_fuzz")              # its rays, its random sets (poly_broad_fuzz.py's) and its package
 pkg, pbf, fuzz_seed = rf.pkg, rf.pbf, rf.fuzz_seed
 F = np.float32
 
