@@ -7,9 +7,9 @@ HIPCC    ?= /opt/rocm/bin/hipcc
 # -fno-slp-vectorize: hipcc otherwise packs scalar f32 ops into v_pk_mul/add_f32, measured 2 % slower here.
 HIPFLAGS := -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -fPIC -Wall -Wextra -Wno-unused-parameter -Iinclude
 
-SRCS := $(CSRC)/c2d_api.hip $(CSRC)/c2d_host.hip $(CSRC)/c2d_sat.hip $(CSRC)/c2d_poly.hip $(CSRC)/c2d_poly_binned.hip $(CSRC)/c2d_mc.hip $(CSRC)/c2d_mc_poly.hip $(CSRC)/c2d_tables.hip $(CSRC)/c2d_dist.hip $(CSRC)/c2d_cross.hip $(CSRC)/c2d_broad.hip $(CSRC)/c2d_poly_cross.hip $(CSRC)/c2d_poly_broad.hip $(CSRC)/c2d_contact.hip $(CSRC)/c2d_distance.hip $(CSRC)/c2d_ray.hip $(CSRC)/c2d_ray_grid.hip $(CSRC)/c2d_sweep.hip $(CSRC)/c2d_clearance.hip $(CSRC)/c2d_cast.hip $(CSRC)/c2d_sweep_broad.hip $(CSRC)/c2d_near_broad.hip $(CSRC)/c2d_clearance_grid.hip $(CSRC)/c2d_cast_grid.hip
+SRCS := $(CSRC)/c2d_api.hip $(CSRC)/c2d_host.hip $(CSRC)/c2d_sat.hip $(CSRC)/c2d_poly.hip $(CSRC)/c2d_poly_binned.hip $(CSRC)/c2d_mc.hip $(CSRC)/c2d_mc_poly.hip $(CSRC)/c2d_tables.hip $(CSRC)/c2d_dist.hip $(CSRC)/c2d_cross.hip $(CSRC)/c2d_broad.hip $(CSRC)/c2d_poly_cross.hip $(CSRC)/c2d_poly_broad.hip $(CSRC)/c2d_contact.hip $(CSRC)/c2d_distance.hip $(CSRC)/c2d_overlap.hip $(CSRC)/c2d_ray.hip $(CSRC)/c2d_ray_grid.hip $(CSRC)/c2d_sweep.hip $(CSRC)/c2d_clearance.hip $(CSRC)/c2d_cast.hip $(CSRC)/c2d_sweep_broad.hip $(CSRC)/c2d_near_broad.hip $(CSRC)/c2d_clearance_grid.hip $(CSRC)/c2d_cast_grid.hip
 OBJS := $(SRCS:.hip=.o)
-HDRS := $(CSRC)/c2d_math.hpp $(CSRC)/c2d_mc_core.hpp $(CSRC)/c2d_count.hpp $(CSRC)/c2d_internal.hpp $(CSRC)/c2d_broad.hpp $(CSRC)/c2d_poly_pair.hpp $(CSRC)/c2d_poly_broad_box.hpp $(CSRC)/c2d_cross.hpp $(CSRC)/c2d_cross_tiles.hpp $(CSRC)/c2d_pair_list.hpp $(CSRC)/c2d_ray_strips.hpp $(CSRC)/c2d_ray_rule.hpp $(CSRC)/c2d_ray_walk.hpp $(CSRC)/c2d_distance_rule.hpp $(CSRC)/c2d_clearance_bound.hpp $(CSRC)/c2d_clearance_parts.hpp $(CSRC)/c2d_near_shape.hpp $(CSRC)/c2d_sweep_rule.hpp $(CSRC)/c2d_sweep_shape.hpp $(CSRC)/c2d_cast_parts.hpp $(CSRC)/c2d_grid_best.hpp $(CSRC)/c2d_set_best.hpp $(CSRC)/c2d_wave.hpp include/c2d.h include/utils.h
+HDRS := $(CSRC)/c2d_math.hpp $(CSRC)/c2d_mc_core.hpp $(CSRC)/c2d_count.hpp $(CSRC)/c2d_internal.hpp $(CSRC)/c2d_broad.hpp $(CSRC)/c2d_poly_pair.hpp $(CSRC)/c2d_poly_broad_box.hpp $(CSRC)/c2d_cross.hpp $(CSRC)/c2d_cross_tiles.hpp $(CSRC)/c2d_pair_list.hpp $(CSRC)/c2d_ray_strips.hpp $(CSRC)/c2d_ray_rule.hpp $(CSRC)/c2d_ray_walk.hpp $(CSRC)/c2d_distance_rule.hpp $(CSRC)/c2d_overlap_rule.hpp $(CSRC)/c2d_clearance_bound.hpp $(CSRC)/c2d_clearance_parts.hpp $(CSRC)/c2d_near_shape.hpp $(CSRC)/c2d_sweep_rule.hpp $(CSRC)/c2d_sweep_shape.hpp $(CSRC)/c2d_cast_parts.hpp $(CSRC)/c2d_grid_best.hpp $(CSRC)/c2d_set_best.hpp $(CSRC)/c2d_wave.hpp include/c2d.h include/utils.h
 
 all: lib oracle drivers lib-fmad lib-nopretest lib-rehearsal lib-movecheck lib-splitcheck
 

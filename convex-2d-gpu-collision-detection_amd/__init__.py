@@ -34,6 +34,11 @@ from .binding import (  # noqa: F401
     DISTANCE_INTERIOR,
     DISTANCE_NO_CANDIDATE,
     DISTANCE_BAD_PAIR,
+    OVERLAP_DT,
+    OVERLAP_DEGENERATE,
+    OVERLAP_CLAMPED,
+    OVERLAP_NO_CENTROID,
+    OVERLAP_BAD_PAIR,
     RAY_HIT_DT,
     RAY_START_INSIDE,
     CLEARANCE_DT,

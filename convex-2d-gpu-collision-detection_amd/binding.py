@@ -41,6 +41,11 @@ DISTANCE_DT = np.dtype([("dist", "<f4"), ("ax", "<f4"), ("ay", "<f4"), ("bx", "<
                         ("flags", "u1"), ("reserved0", "<u2"), ("reserved1", "<u4")])   # c2d_distance
 DISTANCE_EDGE_ON_B, DISTANCE_INTERIOR, DISTANCE_NO_CANDIDATE, DISTANCE_BAD_PAIR = 1, 2, 4, 8
 
+# overlap queries (include/c2d.h, "overlap queries: area, centroid and IoU of the intersection for listed pairs")
+OVERLAP_DT = np.dtype([("area", "<f4"), ("iou", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("area_a", "<f4"), ("area_b", "<f4"), ("hit", "u1"), ("flags", "u1"),
+                       ("pieces_a", "u1"), ("pieces_b", "u1"), ("reserved", "<u4")])   # c2d_overlap
+OVERLAP_DEGENERATE, OVERLAP_CLAMPED, OVERLAP_NO_CENTROID, OVERLAP_BAD_PAIR = 1, 2, 4, 8
+
 # ray queries (include/c2d.h, "ray queries: the nearest hit of every segment against a polygon set")
 RAY_HIT_DT = np.dtype([("poly", "<u4"), ("t", "<f4"), ("u", "<f4"), ("edge", "<u2"), ("hit", "u1"), ("flags", "u1")])   # c2d_ray_hit
 RAY_START_INSIDE = 1
@@ -196,6 +201,10 @@ _SIGNATURES = {
                                           C.c_void_p, C.c_void_p]),
     "c2d_rect_pair_distances": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                           C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "c2d_poly_pair_overlaps": (C.c_int, [C.c_void_p, C.POINTER(_PolySet), C.POINTER(_PolySet), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                         C.c_void_p, C.c_void_p]),
+    "c2d_rect_pair_overlaps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_ray_casts": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(_PolySet), C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_ray_casts_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(_PolySet), C.c_size_t, C.c_void_p, C.c_void_p]),
     "c2d_poly_ray_casts_grid_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
@@ -824,6 +833,24 @@ class Engine:
         a, b = self._cross_planes(a_planes, b_planes)
         self._check(self.lib.c2d_rect_pair_distances(self.h, a, n_a, b, n_b, _ptr_of(pairs), n_pairs, _ptr_of(n_pairs_dev), row_base, col_base,
                                                      _ptr_of(out), C.c_void_p(stream)), "c2d_rect_pair_distances")
+
+    # -- overlap queries (include/c2d.h "overlap queries: area, centroid and IoU of the intersection for listed pairs") -----------------
+    def poly_pair_overlaps(self, a: _PolySet, b: _PolySet, pairs, n_pairs: int, out, n_pairs_dev=None, row_base: int = 0, col_base: int = 0,
+                           stream: int = 0):
+        """c2d_poly_pair_overlaps: out[p] (OVERLAP_DT[n_pairs], 16-byte aligned) = the pairwise boolean of list entry p and, when it
+        is hit, the area of the intersection of the two polygons with its centroid, their own areas and the IoU; the list,
+        n_pairs_dev and the bases as for poly_pair_contacts"""
+        if not isinstance(a, _PolySet) or not isinstance(b, _PolySet):
+            raise ValueError("need two poly_set() descriptions")
+        self._check(self.lib.c2d_poly_pair_overlaps(self.h, C.byref(a), C.byref(b), _ptr_of(pairs), n_pairs, _ptr_of(n_pairs_dev), row_base, col_base,
+                                                    _ptr_of(out), C.c_void_p(stream)), "c2d_poly_pair_overlaps")
+
+    def rect_pair_overlaps(self, a_planes: Sequence, n_a: int, b_planes: Sequence, n_b: int, pairs, n_pairs: int, out, n_pairs_dev=None,
+                           row_base: int = 0, col_base: int = 0, stream: int = 0):
+        """c2d_rect_pair_overlaps: poly_pair_overlaps for two rectangle sets given as 8 vertex planes each"""
+        a, b = self._cross_planes(a_planes, b_planes)
+        self._check(self.lib.c2d_rect_pair_overlaps(self.h, a, n_a, b, n_b, _ptr_of(pairs), n_pairs, _ptr_of(n_pairs_dev), row_base, col_base,
+                                                    _ptr_of(out), C.c_void_p(stream)), "c2d_rect_pair_overlaps")
 
     # -- ray queries (include/c2d.h "ray queries: the nearest hit of every segment against a polygon set") -----------------
     def poly_ray_casts(self, rays: Sequence, n_rays: int, b: _PolySet, out, col_base: int = 0, stream: int = 0):

@@ -575,6 +575,80 @@ int c2d_rect_pair_distances(c2d_ctx* ctx, const float* const d_a[8], size_t n_a,
                             size_t row_base, size_t col_base,
                             c2d_distance* d_out, c2d_stream stream);
 
+/* ---- overlap queries: area, centroid and IoU of the intersection for listed pairs ----
+ * Additions to 0.6 (c2d_version() stays 6), found by symbol lookup like the contact calls.
+ *
+ * c2d_poly_pair_overlaps / c2d_rect_pair_overlaps: for each pair of a list the boolean of the pairwise test and, when the pair is
+ * hit, HOW MUCH of the two shapes overlaps: the area of A ∩ B, its centroid, the two shapes' own areas and the intersection over
+ * union (rotated-box and convex-polygon IoU; area-weighted penalty forces and buoyancy; "inside" told from "crossing" by the piece
+ * counts).  The sets, d_pairs, d_n_pairs, the bases, the records at or beyond min(n_pairs, *d_n_pairs) (untouched), bad pairs, the
+ * asynchronous error word, n_pairs == 0 (a no-op), the refused arguments (refused before a device is touched), "no ctx scratch", the
+ * single launch and graph capture are those of c2d_poly_pair_contacts / c2d_rect_pair_contacts.
+ *   d_out : c2d_overlap[n_pairs], 16-byte aligned; entry p is the overlap record of list entry p.
+ *
+ * Arithmetic contract.  Everything is IEEE binary32, round to nearest, subnormals kept, nothing contracted in any
+ * build; division is correctly rounded; cross(u, v) = u.x * v.y - u.y * v.x (two products, one difference); max and min below are
+ * compare and select (t0 = q > t0 ? q : t0), so a NaN operand moves nothing.  Vertex order may be clockwise or counter-clockwise,
+ * 1 <= k <= 16; rectangles are the four vertices of their planes, ka = kb = 4.
+ *   hit         the pairwise boolean itself, for every input bit pattern: exactly the `hit` of the contact calls.
+ *   setup       r = A's vertex 0.  Every vertex v of both shapes is replaced by v - r (one rounding per coordinate); everything below
+ *               uses the shifted vertices.  sum_A = the shoelace sum  cross(v_0, v_1) + cross(v_1, v_2) + ... + cross(v_ka-1, v_0),
+ *               accumulated from 0 in that order; sA = +1 if sum_A > 0, else -1; area_a = 0.5 * |sum_A|; likewise sum_B, sB, area_b.
+ *               hit == 0: the record is {area 0, iou 0, centroid (0, 0), area_a, area_b, hit 0, C2D_OVERLAP_NO_CENTROID, pieces 0, 0}.
+ *               Else, if sum_A or sum_B is 0 or NaN (a point, a segment, collinear vertices): area = iou = 0, centroid (0, 0),
+ *               flags = C2D_OVERLAP_DEGENERATE | C2D_OVERLAP_NO_CENTROID, pieces 0, 0.
+ *   the sides   side 0 walks A's edges e = 0..ka-1 as P (from vertex e to vertex (e + 1) mod ka) and clips each against all edges
+ *               of B as Q; side 1 walks B's edges against A.  For P's edge p0 -> p1: ex = p1 - p0, t0 = 0, t1 = 1.  For Q's edges
+ *               f = 0..kq-1 in order, q0 -> q1 with g = q1 - q0: a zero-length g imposes nothing.  Otherwise w = p0 - q0,
+ *               num = sQ * cross(g, w), den = sQ * cross(g, ex), and
+ *                   den > 0:   t0 = max(t0, (-num) / den)
+ *                   den < 0:   t1 = min(t1, (-num) / den)
+ *                   den == 0:  (parallel) the edge survives this half-plane if num > 0, and, on side 0 only, if num == 0 and
+ *                              sP * sQ * (ex.x * g.x + ex.y * g.y) > 0; otherwise it is dropped.  A boundary that the two shapes
+ *                              share is thus counted once, on A's side, and only where both interiors lie on the same side of it.
+ *                   (a NaN den does none of the three.)
+ *   a piece     a surviving edge with t0 < t1: a = p0 + t0 * ex, b = p0 + t1 * ex (product, then sum), c = sP * cross(a, b);
+ *               S += c, Mx += (a.x + b.x) * c, My += (a.y + b.y) * c, and the side's piece count goes up by one.  (A zero-length
+ *               edge of P that survives is a piece like any other: it adds 0 to the sums and 1 to the count.)  Each side
+ *               accumulates from 0 in edge order; then S = S0 + S1, Mx = Mx0 + Mx1, My = My0 + My1.
+ *   the record  raw = 0.5 * S; area = min(max(raw, 0), min(area_a, area_b)), C2D_OVERLAP_CLAMPED where area != raw.
+ *               iou = area / ((area_a + area_b) - area) where that denominator is > 0, else 0.
+ *               S > 0: cx = r.x + Mx / (3 * S), cy = r.y + My / (3 * S); else (0, 0) with C2D_OVERLAP_NO_CENTROID.
+ *               pieces_a, pieces_b: the pieces of side 0 and of side 1.  pieces_b == 0 && pieces_a == ka reads "A inside B".
+ *               A float of the record that is NaN is stored as 0x7FC00000, whatever its sign and payload.
+ *               A bad pair (as for the contact calls): everything 0, C2D_OVERLAP_BAD_PAIR.
+ * The implementation may skip work whose result cannot reach the record; the stored bytes equal this sequential rule
+ * (tests/overlap_ref.py restates it in numpy, every compare included).  For convex shapes with finite coordinates, with D the largest
+ * |coordinate - r| and u = 2^-24, |area - exact| stays within a small multiple of u * D^2 (DESIGN.md §5.27 has the measured
+ * constant).  For non-convex or non-finite input nothing is promised about what the numbers mean, only their bits.  overlaps(A, B)
+ * and overlaps(B, A) may differ in the last bits: r and the shared-boundary clause are A's. */
+#define C2D_OVERLAP_DEGENERATE  1  /* hit, but a shape has no area (its shoelace sum is 0 or NaN): area = iou = 0 */
+#define C2D_OVERLAP_CLAMPED     2  /* 0.5 * S fell outside [0, min(area_a, area_b)] and was clamped */
+#define C2D_OVERLAP_NO_CENTROID 4  /* no centroid: not hit, degenerate, or S <= 0 (shapes that only touch); cx = cy = 0 */
+#define C2D_OVERLAP_BAD_PAIR    8  /* as C2D_CONTACT_BAD_PAIR */
+
+typedef struct c2d_overlap {    /* 32 bytes, 16-byte aligned output */
+    float    area;              /*  0: area of A ∩ B; 0 when not hit */
+    float    iou;               /*  4: area / (area_a + area_b - area); 0 where that denominator is not > 0 */
+    float    cx, cy;            /*  8: centroid of A ∩ B; (0, 0) with C2D_OVERLAP_NO_CENTROID */
+    float    area_a, area_b;    /* 16: the two shapes' own areas (absolute) */
+    uint8_t  hit;               /* 24: the pairwise boolean, for every input bit pattern */
+    uint8_t  flags;             /* 25 */
+    uint8_t  pieces_a;          /* 26: boundary pieces of A ∩ B that lie on A's edges */
+    uint8_t  pieces_b;          /* 27: ... and on B's edges */
+    uint32_t reserved;          /* 28: written as 0 */
+} c2d_overlap;
+
+int c2d_poly_pair_overlaps(c2d_ctx* ctx, const c2d_poly_set* a, const c2d_poly_set* b,
+                           const uint32_t* d_pairs, size_t n_pairs, const unsigned long long* d_n_pairs,
+                           size_t row_base, size_t col_base,
+                           c2d_overlap* d_out, c2d_stream stream);
+
+int c2d_rect_pair_overlaps(c2d_ctx* ctx, const float* const d_a[8], size_t n_a, const float* const d_b[8], size_t n_b,
+                           const uint32_t* d_pairs, size_t n_pairs, const unsigned long long* d_n_pairs,
+                           size_t row_base, size_t col_base,
+                           c2d_overlap* d_out, c2d_stream stream);
+
 /* ---- ray queries: the nearest hit of every segment against a polygon set ---------
  * An addition to 0.6 (c2d_version() stays 6), found by symbol lookup like the calls above.
  *
