@@ -7,10 +7,16 @@
 // built, so nothing is indexed at run time.  Everything is binary32 and unfused, in the frame of r = A's vertex 0:
 //     sA, sB        the signs of the two shoelace sums (either winding is taken); area_a = 0.5 * |sum_A|
 //     side 0 / 1    every edge p0 -> p1 of A (of B) is clipped to [t0, t1] in [0, 1] by the half-planes of B's (A's) edges q0 -> q1:
-//                   g = q1 - q0 (a zero g imposes nothing), w = p0 - q0, num = sQ * cross(g, w), den = sQ * cross(g, p1 - p0);
+//                   g = q1 - q0 (a zero g imposes nothing), num = sQ * cross(g, p0 - q0), den = sQ * cross(g, p1 - p0);
 //                   den > 0: t0 = max(t0, -num / den); den < 0: t1 = min(t1, -num / den); den == 0: the edge lives on if num > 0,
-//                   and, on side 0 alone, if num == 0 and the two edges run the same way (a shared boundary is counted once, as A's)
-//     a piece       a surviving edge with t0 < t1: a = p0 + t0 * e, b = p0 + t1 * e, c = sP * cross(a, b);
+//                   and, on side 0 alone, if num == 0 and the two edges run the same way.  Where a quotient moves t0 or t1 the
+//                   piece's end becomes the crossing X of the two edges, and X is one point for both sides: p0 + t * e on A's
+//                   edge, which side 1 computes by side 0's operations on the same operands, so that the pieces close a loop
+//     on one line   all four of cross(g, p0 - q0), cross(g, p1 - q0), cross(e, q0 - p0), cross(e, q1 - p0) within 8 u D (|x| + |y|)
+//                   of 0 (the same four expressions on both sides): edges that run opposite ways are dropped; of two that run
+//                   the same way A's is the boundary where it is inside B's half-plane and B's elsewhere, split, where A's edge
+//                   passes through, at da / (da - db) of A's edge (da, db: its ends against B's half-plane)
+//     a piece       a surviving edge with t0 < t1, from a to b (an end that no clip moved is the vertex itself), c = sP * cross(a, b);
 //                   S += c, Mx += (a.x + b.x) * c, My += (a.y + b.y) * c
 //     the record    area = clamp(0.5 * S, 0, min(area_a, area_b)), centroid = r + M / (3 * S), iou = area / (area_a + area_b - area)
 //

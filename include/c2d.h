@@ -597,17 +597,42 @@ int c2d_rect_pair_distances(c2d_ctx* ctx, const float* const d_a[8], size_t n_a,
  *               hit == 0: the record is {area 0, iou 0, centroid (0, 0), area_a, area_b, hit 0, C2D_OVERLAP_NO_CENTROID, pieces 0, 0}.
  *               Else, if sum_A or sum_B is 0 or NaN (a point, a segment, collinear vertices): area = iou = 0, centroid (0, 0),
  *               flags = C2D_OVERLAP_DEGENERATE | C2D_OVERLAP_NO_CENTROID, pieces 0, 0.
+ *   setup (2)   D = the largest |coordinate| of the shifted real vertices of both shapes (compare and select from 0, so a NaN moves
+ *               nothing), kD = 2^-21 * D (8 u D, u = 2^-24).
  *   the sides   side 0 walks A's edges e = 0..ka-1 as P (from vertex e to vertex (e + 1) mod ka) and clips each against all edges
- *               of B as Q; side 1 walks B's edges against A.  For P's edge p0 -> p1: ex = p1 - p0, t0 = 0, t1 = 1.  For Q's edges
- *               f = 0..kq-1 in order, q0 -> q1 with g = q1 - q0: a zero-length g imposes nothing.  Otherwise w = p0 - q0,
- *               num = sQ * cross(g, w), den = sQ * cross(g, ex), and
- *                   den > 0:   t0 = max(t0, (-num) / den)
- *                   den < 0:   t1 = min(t1, (-num) / den)
+ *               of B as Q; side 1 walks B's edges against A.  For P's edge p0 -> p1: ex = p1 - p0, t0 = 0, t1 = 1, and the piece's
+ *               ends start as a = p0, b = p1.  For Q's edges f = 0..kq-1 in order, q0 -> q1 with g = q1 - q0: a zero-length g
+ *               imposes nothing.  Otherwise four cross products,
+ *                   c_p0 = cross(g, p0 - q0), c_p1 = cross(g, p1 - q0), c_q0 = cross(ex, q0 - p0), c_q1 = cross(ex, q1 - p0),
+ *               and the pair of edges lies ON ONE LINE when |c_p0| <= T_g, |c_p1| <= T_g, |c_q0| <= T_e and |c_q1| <= T_e with
+ *               T_x = kD * (|x.x| + |x.y|).  The two sides evaluate the same four expressions on the same operands for a pair of
+ *               edges (c_p of one side is c_q of the other), so this decision, and every one below that is taken from da and db,
+ *               has the same bits on both sides.  same_way = sP * sQ * (ex.x * g.x + ex.y * g.y) > 0.
+ *               Not on one line:  num = sQ * c_p0, den = sQ * cross(g, ex), q = (-num) / den, and
+ *                   den > 0 and q > t0:   t0 = q, a = X
+ *                   den < 0 and q < t1:   t1 = q, b = X
  *                   den == 0:  (parallel) the edge survives this half-plane if num > 0, and, on side 0 only, if num == 0 and
- *                              sP * sQ * (ex.x * g.x + ex.y * g.y) > 0; otherwise it is dropped.  A boundary that the two shapes
- *                              share is thus counted once, on A's side, and only where both interiors lie on the same side of it.
+ *                              same_way; otherwise it is dropped.
  *                   (a NaN den does none of the three.)
- *   a piece     a surviving edge with t0 < t1: a = p0 + t0 * ex, b = p0 + t1 * ex (product, then sum), c = sP * cross(a, b);
+ *               X is the crossing of the two edges, ONE point for both sides: the point on A's edge.  On side 0
+ *               X = p0 + q * ex (product, then sum).  On side 1, where A's edge is Q's, X = q0 + tq * g with
+ *               tq = (-(sP * c_q0)) / (sP * cross(ex, g)): the operations of side 0 for this pair of edges, on the same operands.
+ *               The pieces of the two sides then meet in the same bits, and the boundary closes, however badly the two quotients
+ *               are conditioned.
+ *               On one line and not same_way: the edge is dropped (the shapes only touch along it).
+ *               On one line and same_way: with da, db the ends of A's edge against B's half-plane (side 0: da = sQ * c_p0,
+ *               db = sQ * c_p1; side 1: da = sP * c_q0, db = sP * c_q1), A's edge is the boundary of A ∩ B where it is inside,
+ *               B's edge elsewhere, so that a boundary that the two shapes share is counted once:
+ *                   da >= 0 and db >= 0:              side 0: nothing is imposed; side 1: the edge is dropped
+ *                   else da <= 0 and db <= 0:         side 0: the edge is dropped; side 1: nothing is imposed
+ *                   da < 0 < db ("enters") or db < 0 < da ("leaves"): the edges split at ts = da / (da - db),
+ *                       Xs = (A's edge).p0 + ts * (A's edge) — side 0: p0 + ts * ex, s = ts; side 1: q0 + ts * g,
+ *                       s = ((Xs.x - p0.x) * ex.x + (Xs.y - p0.y) * ex.y) / (ex.x * ex.x + ex.y * ex.y).
+ *                       Side 0 keeps the inside part: enters and s > t0: t0 = s, a = Xs; leaves and s < t1: t1 = s, b = Xs.
+ *                       Side 1 keeps the other part; with sP * sQ > 0 (the edges run the same way as listed): leaves and s > t0:
+ *                       t0 = s, a = Xs; enters and s < t1: t1 = s, b = Xs; with sP * sQ < 0 enters and leaves change places.
+ *   a piece     a surviving edge with t0 < t1, from a to b as left by the clips (an end that no clip moved is the vertex itself):
+ *               c = sP * cross(a, b);
  *               S += c, Mx += (a.x + b.x) * c, My += (a.y + b.y) * c, and the side's piece count goes up by one.  (A zero-length
  *               edge of P that survives is a piece like any other: it adds 0 to the sums and 1 to the count.)  Each side
  *               accumulates from 0 in edge order; then S = S0 + S1, Mx = Mx0 + Mx1, My = My0 + My1.
@@ -620,7 +645,9 @@ int c2d_rect_pair_distances(c2d_ctx* ctx, const float* const d_a[8], size_t n_a,
  * The implementation may skip work whose result cannot reach the record; the stored bytes equal this sequential rule
  * (tests/overlap_ref.py restates it in numpy, every compare included).  For convex shapes with finite coordinates, with D the largest
  * |coordinate - r| and u = 2^-24, |area - exact| stays within a small multiple of u * D^2 (DESIGN.md §5.27 has the measured
- * constant).  For non-convex or non-finite input nothing is promised about what the numbers mean, only their bits.  overlaps(A, B)
+ * constant), also where edges of the two shapes lie on one line or nearly so (aligned boxes, equal shapes listed from another
+ * vertex): a pair of edges within 8 u D of one line is treated as on one line, and where both edges would do as the boundary A's
+ * is the one counted.  For non-convex or non-finite input nothing is promised about what the numbers mean, only their bits.  overlaps(A, B)
  * and overlaps(B, A) may differ in the last bits: r and the shared-boundary clause are A's. */
 #define C2D_OVERLAP_DEGENERATE  1  /* hit, but a shape has no area (its shoelace sum is 0 or NaN): area = iou = 0 */
 #define C2D_OVERLAP_CLAMPED     2  /* 0.5 * S fell outside [0, min(area_a, area_b)] and was clamped */

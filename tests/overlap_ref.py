@@ -2,7 +2,8 @@
 contract, not from the kernel: plain numpy float32, element-wise and unfused (numpy never contracts a * b + c), / correctly rounded,
 every max and min a compare and select (np.where), so that a NaN falls through each compare as the contract says.  The rule is a
 boundary integral: each edge of A is clipped to the part inside B, each edge of B to the part inside A, and the pieces are summed;
-the intersection polygon is never built.
+the intersection polygon is never built.  Where an edge is cut, the crossing is one point for both sides (A's p0 + t * e); two
+edges within 8 u D of one line are told apart by the ends of A's edge against B's half-plane, from the same bits on both sides.
 
 poly_overlaps(a, b, i, j) and rect_overlaps(a, b, i, j) take LOCAL indices (the list entry minus its bases) and return an OVERLAP_DT
 record per pair.  The sets are loaded as tests/contact_ref.py loads them, and `hit` and the BAD_PAIR entries are contact_ref's own
@@ -16,6 +17,7 @@ OVERLAP_DT = np.dtype([("area", "<f4"), ("iou", "<f4"), ("cx", "<f4"), ("cy", "<
 DEGENERATE, CLAMPED, NO_CENTROID, BAD_PAIR = 1, 2, 4, 8
 F = np.float32
 FLOATS = ("area", "iou", "cx", "cy", "area_a", "area_b")
+ON_LINE = F(2.0 ** -21)        # 8 u: two edges count as lying on one line within 8 u D (|x| + |y|) of each cross product
 QUIET_NAN = np.array([0x7FC00000], np.uint32).view(F)[0]
 
 
@@ -38,36 +40,85 @@ def _shoelace(x, y, k):
     return total
 
 
-def _side(px, py, kp, sp, qx, qy, kq, sq, side0):
+def _extent(ax, ay, ka, bx, by, kb):
+    """D: the largest |coordinate| of the shifted real slots, A's slots in order (x, then y), then B's; a compare and select"""
+    D = np.zeros(ax.shape[1], F)
+    for x, y, k in ((ax, ay, ka), (bx, by, kb)):
+        for v in range(x.shape[0]):
+            for c in (np.abs(x[v]), np.abs(y[v])):
+                D = np.where((v < k) & (c > D), c, D)
+    return D
+
+
+def _side(px, py, kp, sp, qx, qy, kq, sq, side0, kD):
     """the kp edges of P (x, y f32 [rows_p][m]), each clipped by the kq edges of Q -> S, Mx, My, pieces of this side"""
     m = px.shape[1]
     S, Mx, My = (np.zeros(m, F) for _ in range(3))
     pieces = np.zeros(m, np.int64)
-    edges = []          # Q's edges in order: q0, g and whether the edge imposes anything
+    edges = []          # Q's edges in order: q0, q1, g and whether the edge imposes anything
     for f in range(qx.shape[0]):
         a0, b0 = _vertex(qx, qy, np.where(f < kq, f, 0))
         a1, b1 = _vertex(qx, qy, np.where(f + 1 < kq, f + 1, 0))
         gx, gy = a1 - a0, b1 - b0
-        edges.append((a0, b0, gx, gy, (f < kq) & ~((gx == 0) & (gy == 0))))
+        edges.append((a0, b0, a1, b1, gx, gy, (f < kq) & ~((gx == 0) & (gy == 0))))
     for e in range(px.shape[0]):
         live_e = e < kp
         x0, y0 = _vertex(px, py, np.where(live_e, e, 0))
         x1, y1 = _vertex(px, py, np.where(e + 1 < kp, e + 1, 0))
         ex, ey = x1 - x0, y1 - y0
+        tol_e = kD * (np.abs(ex) + np.abs(ey))
         t0, t1 = np.zeros(m, F), np.ones(m, F)
+        ux, uy, vx, vy = x0, y0, x1, y1
         alive = np.ones(m, bool)
-        for a0, b0, gx, gy, real in edges:
-            wx, wy = x0 - a0, y0 - b0
-            num = sq * _cross(gx, gy, wx, wy)
+        for a0, b0, a1, b1, gx, gy, real in edges:
+            tol_g = kD * (np.abs(gx) + np.abs(gy))
+            c_p0 = _cross(gx, gy, x0 - a0, y0 - b0)
+            c_p1 = _cross(gx, gy, x1 - a0, y1 - b0)
+            c_q0 = _cross(ex, ey, a0 - x0, b0 - y0)
+            c_q1 = _cross(ex, ey, a1 - x0, b1 - y0)
+            on_line = real & (np.abs(c_p0) <= tol_g) & (np.abs(c_p1) <= tol_g) & (np.abs(c_q0) <= tol_e) & (np.abs(c_q1) <= tol_e)
+            same_way = (sp * sq) * (ex * gx + ey * gy) > 0
+            # two edges that cross: the half-plane of g cuts e at q, and the crossing is ONE point for both sides, A's p0 + t * e
+            num = sq * c_p0
             den = sq * _cross(gx, gy, ex, ey)
             q = (-num) / den
-            t0 = np.where(real & (den > 0) & (q > t0), q, t0)
-            t1 = np.where(real & (den < 0) & (q < t1), q, t1)
+            if side0:
+                cx, cy = x0 + q * ex, y0 + q * ey
+            else:           # A's edge is Q's here: the same operations on the same operands as side 0's of this pair of edges
+                tq = (-(sp * c_q0)) / (sp * _cross(ex, ey, gx, gy))
+                cx, cy = a0 + tq * gx, b0 + tq * gy
+            cuts = real & ~on_line
+            lower, upper = cuts & (den > 0) & (q > t0), cuts & (den < 0) & (q < t1)
+            t0, ux, uy = np.where(lower, q, t0), np.where(lower, cx, ux), np.where(lower, cy, uy)
+            t1, vx, vy = np.where(upper, q, t1), np.where(upper, cx, vx), np.where(upper, cy, vy)
             keeps = num > 0
             if side0:
-                keeps = keeps | ((num == 0) & ((sp * sq) * (ex * gx + ey * gy) > 0))
-            alive &= ~(real & (den == 0) & ~keeps)
-        ux, uy, vx, vy = x0 + t0 * ex, y0 + t0 * ey, x0 + t1 * ex, y0 + t1 * ey
+                keeps = keeps | ((num == 0) & same_way)
+            alive &= ~(cuts & (den == 0) & ~keeps)
+            # two edges on one line: the ends of A's edge against B's half-plane (da, db: the same bits on both sides) say which
+            # of the two is the boundary of A and B: A's where it is inside, B's elsewhere, split where A's edge passes through
+            if side0:
+                da, db = sq * c_p0, sq * c_p1
+            else:
+                da, db = sp * c_q0, sp * c_q1
+            inside = (da >= 0) & (db >= 0)
+            outside = ~inside & (da <= 0) & (db <= 0)
+            enters, leaves = (da < 0) & (db > 0), (da > 0) & (db < 0)
+            ts = da / (da - db)
+            if side0:
+                sx, sy = x0 + ts * ex, y0 + ts * ey
+                s = ts
+                from_s, to_s = enters, leaves
+                alive &= ~(on_line & ~(same_way & ~outside))
+            else:           # B's edge keeps the other part, up to the same point; s is that point's parameter on B's edge
+                sx, sy = a0 + ts * gx, b0 + ts * gy
+                s = ((sx - x0) * ex + (sy - y0) * ey) / (ex * ex + ey * ey)
+                along = (sp * sq) > 0         # (same_way: the two edges run the same way as listed iff the windings agree)
+                from_s, to_s = np.where(along, leaves, enters), np.where(along, enters, leaves)
+                alive &= ~(on_line & ~(same_way & ~inside))
+            lower, upper = on_line & same_way & from_s & (s > t0), on_line & same_way & to_s & (s < t1)
+            t0, ux, uy = np.where(lower, s, t0), np.where(lower, sx, ux), np.where(lower, sy, uy)
+            t1, vx, vy = np.where(upper, s, t1), np.where(upper, sx, vx), np.where(upper, sy, vy)
         c = sp * _cross(ux, uy, vx, vy)
         piece = live_e & alive & (t0 < t1)
         S = np.where(piece, S + c, S)
@@ -91,8 +142,9 @@ def _run(ax, ay, ka, bx, by, kb, hit, bad):
         sum_a, sum_b = _shoelace(ax, ay, ka), _shoelace(bx, by, kb)
         sa, sb = np.where(sum_a > 0, F(1), F(-1)), np.where(sum_b > 0, F(1), F(-1))
         area_a, area_b = F(0.5) * np.abs(sum_a), F(0.5) * np.abs(sum_b)
-        S0, Mx0, My0, pa = _side(ax, ay, ka, sa, bx, by, kb, sb, True)
-        S1, Mx1, My1, pb = _side(bx, by, kb, sb, ax, ay, ka, sa, False)
+        kD = ON_LINE * _extent(ax, ay, ka, bx, by, kb)
+        S0, Mx0, My0, pa = _side(ax, ay, ka, sa, bx, by, kb, sb, True, kD)
+        S1, Mx1, My1, pb = _side(bx, by, kb, sb, ax, ay, ka, sa, False, kD)
         S, Mx, My = S0 + S1, Mx0 + Mx1, My0 + My1
         raw = F(0.5) * S
         lo = np.where(raw > 0, raw, F(0))
